@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the MI355X PointRCNN eval path.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run measures the headline only: set-up (model, scenes, untimed set-up steps), W warm-up steps, ONE closed window of K timed
+steps, the detections of the last step under --dump-outputs, the JSON line.  --full adds everything else described below: `value` as
+the median of --windows (5) windows after a rehearsal of the whole window, and the context legs, rooflines and baselines.
 
 One STEP = one pass (software-pipelined over two HIP streams: geometry of the next batch overlaps the
 feature pass of the current one; each step does exactly one of each) of the joint RPN->RCNN hot path (eval_rcnn-equivalent: backbone SA/FP ops,
@@ -22,13 +26,13 @@ results are bit-identical -- tests/test_gpu_shadow.py).  How much that saves dep
 states the measured fraction per level, `config.scenes_per_s_all_rows` is the same step with every nsample row evaluated
 the way the reference does (PRCNN_NO_PACK / PRCNN_NO_POOL_DEDUP), measured in this run.
 
-`value` is the MEDIAN of `--windows` (5) closed windows of W + K steps each, all listed in `config.windows`; beside it, never apart
-from it, stands `config.lidar_like.scenes_per_s` -- the same engine, same windows, on LiDAR-SHAPED scenes (ray-cast 64-beam sweeps through
+`value` is the MEDIAN of `--windows` (plain run: 1; --full: 5) closed windows of W + K steps each, all listed in `config.windows`; beside it
+(--full), never apart from it, stands `config.lidar_like.scenes_per_s` -- the same engine, same windows, on LiDAR-SHAPED scenes (ray-cast 64-beam sweeps through
 the reference's sampler: balls near the sensor are full, 20-60 % of the grouped rows distinct instead of the uniform scene's 3-6 %):
 the uniform scene of SURVEY 8d is the distinct-row engine's BEST case, the LiDAR-shaped one its realistic one, and
 `config.scenes_per_s_all_rows` the same step with no row dropped.
 
-The JSON line also carries
+With --full the JSON line also carries
   roofline      the dominant kernel of the product step -- the largest single launch: the RPN's last stretch over all points
                 (prcnn_rpn_tail: interpolation + FP module 0 + both heads, csrc/rpn_tail.hip) on the engine's own inputs, timed
                 with HIP events on the launch stream; MFMA-bound: algorithmic flops / average duration against the dense
@@ -87,6 +91,7 @@ def launch_scenes():
 HOST_LAG = int(os.environ.get("PRCNN_BENCH_LAG", "3"))   # the host consumes a batch's detections this many batches late
 BATCH = int(os.environ.get("PRCNN_BENCH_BATCH", "8"))     # scenes per step per GPU (BASELINE configs[2]: 8; the override is for experiments and is echoed in config.env_overrides)
 NPOINTS = 16384
+REHEARSAL_STEPS = 100     # cap of the untimed rehearsal window of a plain (not --full) run
 
 
 def algorithmic_bytes_qg(n, m, c, ns):
@@ -519,23 +524,43 @@ def rccl_world1_leg():
         return {"ok": False, "error": repr(e)[:400]}
 
 
+def dump_outputs(out_dir, det):
+    """--dump-outputs: what the timed path handed back for its last step -- the detections of that step's batch of BATCH scenes
+    (boxes (B, M, 7), scores (B, M), num (B); rows >= num are zero) -- as float32 .npy files.  The scenes and the weights are
+    seeded, so two runs with the same arguments see the same inputs."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in zip(("boxes", "scores", "num"), det):
+        np.save(os.path.join(out_dir, name + ".npy"), t.numpy().astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-driver", action="store_true", help="skip the whole-driver leg (loader processes + writer)")
-    ap.add_argument("--no-lidar", action="store_true", help="skip the LiDAR-shaped-scene leg (config.lidar_like)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline as well: the median of --windows (5) closed windows after a rehearsal of the whole "
+                         "window, distinct rows, all-rows and K = 100 rates, the LiDAR-shaped and double.yaml legs, rooflines, the driver, the "
+                         "drop-in module path, RCCL at world size 1 and the CPU baseline (each leg can be dropped with its --no-* option). "
+                         "Without it: set-up, W warm-up steps, ONE window of K timed steps, the outputs, the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the detections of the last timed step (boxes, scores, num; rank 0) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="(--full) skip the rooflines and the context legs")
+    ap.add_argument("--no-driver", action="store_true", help="(--full) skip the whole-driver leg (loader processes + writer)")
+    ap.add_argument("--no-lidar", action="store_true", help="(--full) skip the LiDAR-shaped-scene leg (config.lidar_like)")
     ap.add_argument("--scene", choices=("uniform", "lidar"), default="uniform",
                     help="scene generator of the HEADLINE loop: SURVEY 8d's uniform synthetic scene (default, the contract) or "
-                         "synth.lidar_scene (for profiling that regime; the default run reports it under config.lidar_like)")
-    ap.add_argument("--windows", type=int, default=5, help="closed timed windows of W + K steps each; `value` is the MEDIAN window, config.windows lists them all (VERDICT r4 W9: one K = 20 window in six came out 8 % low)")
+                         "synth.lidar_scene (for profiling that regime; --full reports it under config.lidar_like)")
+    ap.add_argument("--windows", type=int, default=None, help="closed timed windows of W + K steps each (default: 1, with --full 5); `value` is the MEDIAN window, config.windows lists them all (VERDICT r4 W9: one K = 20 window in six came out 8 % low)")
     ap.add_argument("--points", type=int, default=16384, help="points per scene of the HEADLINE loop: 16384 = default.yaml (the contract); 32768 = tools/cfgs/double.yaml, "
-                                                              "for profiling that configuration (the default run reports it under config.double_yaml_scenes_per_s)")
+                                                              "for profiling that configuration (--full reports it under config.double_yaml_scenes_per_s)")
     ap.add_argument("--prewarm", type=int, default=24, help="untimed set-up steps before the W warm-up steps (allocator pool, code objects)")
     args = ap.parse_args()
+    if args.windows is None:
+        args.windows = 5 if args.full else 1
+    if not args.full:              # a plain run measures the headline only
+        args.no_cpu_baseline = args.no_roofline = args.no_driver = args.no_lidar = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` as ONE command: re-launch this script as N ranks (one process per GPU) under
@@ -712,9 +737,11 @@ def main():
         timed_run(args.prewarm, 0)
         # ... and one UNTIMED rehearsal of a whole window -- W warm-up + K steps, the detection tables packed and exchanged -- so that
         # the first timed window is not the first time this exact sequence runs (the first of five windows came out
-        # 26 % low on the driver's box: 5477 against 7366-7396 scenes/s; the median hid it, config.windows showed it)
-        _, dets0 = timed_run(args.steps, args.warmup)
-        E.all_gather_detections(*E.pack_detections(list(range(rank * args.steps * BATCH, (rank + 1) * args.steps * BATCH)), dets0, M), comm_dev)
+        # 26 % low on one box: 5477 against 7366-7396 scenes/s; the median hid it, config.windows showed it).  A plain run
+        # rehearses at most REHEARSAL_STEPS of the K steps: its time outside the timed steps must not grow with K
+        rk = args.steps if args.full else min(args.steps, REHEARSAL_STEPS)
+        _, dets0 = timed_run(rk, args.warmup)
+        E.all_gather_detections(*E.pack_detections(list(range(rank * rk * BATCH, (rank + 1) * rk * BATCH)), dets0, M), comm_dev)
         barrier()
         torch.cuda.synchronize()
         del dets0
@@ -745,6 +772,8 @@ def main():
     order = sorted(range(len(window_s)), key=lambda i: window_s[i])
     mid = order[(len(order) - 1) // 2]                  # the median window (the faster of the middle two for an even count)
     elapsed, allocs_main = window_s[mid], allocs_w[mid]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dets[-1])
 
     # ---- context for the headline (rank 0, untimed): how many grouped rows are distinct on this data, and the same step
     # with every nsample row evaluated (the reference's way)

@@ -1,7 +1,7 @@
 # Round 6: one-box sweep of the launch-geometry knobs around their defaults (bench.py, uniform + LiDAR-shaped, K = 20 median of 5 / K = 100)
 # usage (GPU box, repo root): bash profiles/knob_sweep6.sh > gpurun_out/r06/knob_sweep.md
 run() {
-  env "$@" python -W ignore bench.py --steps 20 --warmup 5 --windows 5 --no-cpu-baseline --no-roofline --no-driver 2>/dev/null | python -c "
+  env "$@" python -W ignore bench.py --full --steps 20 --warmup 5 --windows 5 --no-cpu-baseline --no-roofline --no-driver 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); c=d['config']; l=c['lidar_like']
 print('| %s | %.0f | %.0f | %.0f | %.0f |' % (' '.join(sys.argv[1:]) or 'defaults', d['value'], l['scenes_per_s'], 0, l['scenes_per_s_k100']))" "$@"

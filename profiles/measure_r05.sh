@@ -1,6 +1,6 @@
 # The command set behind the r05_* artefacts of profiles/ (run on the GPU box from the repo root: bash profiles/measure_r05.sh)
 O=gpurun_out/r05; mkdir -p $O; export TMPDIR=/tmp
-timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench_k20.json 2> $O/bench_k20.err
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/bench_k20.json 2> $O/bench_k20.err
 # per-step kernel tables of the bench, uniform and LiDAR-shaped scenes
 for sc in uniform lidar; do
   timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_$sc -- python bench.py --scene $sc --steps 40 --warmup 8 --prewarm 8 --windows 1 --no-cpu-baseline --no-roofline --no-driver --no-lidar > $O/kt_$sc.log 2>&1
@@ -11,7 +11,7 @@ for sc in uniform lidar; do
   rm -rf $O/kt_$sc
 done
 # rocprofv3 statistics of the DRIVER's own command (K = 20)
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_k20 -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-driver --no-lidar --no-roofline > $O/kt_k20.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_k20 -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-driver --no-lidar --no-roofline > $O/kt_k20.log 2>&1
 head -60 $(ls $O/kt_k20/*/*kernel_stats.csv | head -1) > $O/bench_k20_kernel_stats.csv; rm -rf $O/kt_k20
 # HBM traffic per kernel of the product step: one counter per pass (the TCC block cannot hold both), single stream
 for c in FETCH_SIZE WRITE_SIZE; do
@@ -35,5 +35,5 @@ for sc in uniform lidar; do timeout 300 python -W ignore profiles/fps_stamps.py 
 rm -rf /tmp/kt_occ; timeout 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/kt_occ -- python profiles/pmc_step_probe.py 3 > /dev/null 2>&1
 python profiles/occupancy_table.py /tmp/kt_occ/*/*kernel_trace.csv > $O/occupancy.md; python profiles/solo_kernel_times.py /tmp/kt_occ/*/*kernel_trace.csv 40 > $O/solo_kernel_times.md
 for sc in uniform lidar; do timeout 250 python -W ignore profiles/ball_pack_probe.py $sc 2>&1 | grep -v amdgpu.ids; done > $O/ball_pack_probe.md
-timeout 900 python bench.py --steps 100 --warmup 8 --windows 3 --no-cpu-baseline --no-roofline --no-driver > $O/bench_k100.json 2> $O/bench_k100.err
+timeout 900 python bench.py --full --steps 100 --warmup 8 --windows 3 --no-cpu-baseline --no-roofline --no-driver > $O/bench_k100.json 2> $O/bench_k100.err
 cut -c1-300 $O/bench_k20.json; head -12 $O/pmc_product_kernels.md

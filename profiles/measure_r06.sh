@@ -44,7 +44,7 @@ for sc in uniform lidar; do
   rm -rf $O/kt_$sc
 done
 # rocprofv3 statistics of the DRIVER's own command (K = 20)
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_k20 -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-driver --no-lidar --no-roofline > $O/kt_k20.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_k20 -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-driver --no-lidar --no-roofline > $O/kt_k20.log 2>&1
 head -60 $(ls $O/kt_k20/*/*kernel_stats.csv | head -1) > $O/bench_k20_kernel_stats.csv; rm -rf $O/kt_k20
 # HBM traffic per kernel of the product step: one counter per pass (the TCC block cannot hold both), single stream
 for c in FETCH_SIZE WRITE_SIZE; do
@@ -68,8 +68,8 @@ timeout 1500 python profiles/driver_probe6.py > $O/driver.md 2> $O/driver.err
 fi
 
 if has bench; then
-timeout 1200 python bench.py --steps 20 --warmup 5 > $O/bench_k20.json 2> $O/bench_k20.err
-timeout 900 python bench.py --steps 100 --warmup 8 --windows 3 --no-cpu-baseline --no-roofline --no-driver > $O/bench_k100.json 2> $O/bench_k100.err
+timeout 1200 python bench.py --full --steps 20 --warmup 5 > $O/bench_k20.json 2> $O/bench_k20.err
+timeout 900 python bench.py --full --steps 100 --warmup 8 --windows 3 --no-cpu-baseline --no-roofline --no-driver > $O/bench_k100.json 2> $O/bench_k100.err
 cut -c1-300 $O/bench_k20.json
 fi
 

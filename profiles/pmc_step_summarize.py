@@ -1,8 +1,8 @@
 """Per-kernel HBM traffic of the PRODUCT step from two rocprofv3 PMC passes of bench.py (one per counter: the TCC block
 cannot hold FETCH_SIZE and WRITE_SIZE together, MI355X_MICROARCH.md "rocprofv3 PMC slots").
 
-    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d A -- python bench.py --steps 8 --warmup 3 --no-cpu-baseline --no-roofline
-    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d B -- python bench.py ...
+    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d A -- python bench.py --full --steps 8 --warmup 3 --no-cpu-baseline --no-roofline
+    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d B -- python bench.py --full ...
     python profiles/pmc_step_summarize.py A/*/*counter_collection.csv B/*/*counter_collection.csv > profiles/r02_pmc_product_kernels.md
 
 FETCH_SIZE is doubled (gfx950 reports 1/2 of the bytes of wide coalesced reads: MI355X_MICROARCH.md, HBM section); WRITE_SIZE is

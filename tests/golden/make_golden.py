@@ -18,6 +18,9 @@ The fixtures are DATA (inputs + expected outputs); no reference source is stored
                        reproduced) on 256 x 256 centre-format boxes: random, identical, touching, nested, thin,
                        axis-aligned and far-apart pairs, all four criteria, plus the mask of pairs that overrun
                        the reference's 8-point intersection buffer (undefined behaviour on CUDA)
+  g9l_rotate_iou_sample_ref.npz  the same interpreter run on a second, independent random sample (70 x 20 boxes, criteria -1 / 1)
+  g14_kitti_labels_ref.npz  the reference's KittiRCNNDataset.filtrate_objects + objs_to_boxes3d (EVAL and TRAIN mode) on a
+                       seven-line label file (stored in the fixture)
   g10_ap_eval_ref.npz  the reference's AP evaluator (evaluate/eval2.py imported with ``numba.jit`` shimmed to the
                        identity, an empty ``skimage`` stand-in for kitti_common's unused import, and its ``rotate_iou`` dependency -- a numba.cuda module -- IMPORTED FROM THE
                        REFERENCE and run by the same interpreter; round 2 fed it the oracle's K18 restatement) on 60 synthetic label / result files (the reference needs >= 50 images: it cuts the split into 50 parts): label lines in, mAP arrays,
@@ -572,6 +575,52 @@ def g9():
     print("g9: pairs", und.size, "overlapping", int((iou[2] > 0).sum()), "undefined in the reference", int(und.sum()))
 
 
+def g9l():
+    """A second, independent sample for rotate_iou (tests/test_oracle.py::test_rotate_iou_live_reference_run_matches_oracle): 70 x 20
+    random boxes (rng 77; 70 rows = two thread blocks, the second one ragged), criteria -1 and 1, the reference's own rotate_iou.py
+    on the interpreter of numba_shim.py."""
+    import numba_shim as NS
+    mod, cu = NS.import_reference_rotate_iou()
+    rng = np.random.default_rng(77)
+
+    def cb(n):
+        return np.stack([rng.uniform(-4, 4, n), rng.uniform(-4, 4, n), rng.uniform(1.4, 2.2, n), rng.uniform(3, 5, n),
+                         rng.uniform(-np.pi, np.pi, n)], 1).astype(np.float32)
+    a, q = cb(70), cb(20)
+    out = {"boxes": a, "query_boxes": q}
+    for crit in (-1, 1):
+        out["iou_c%d" % crit], out["undefined_c%d" % crit] = NS.reference_rotate_iou_eval(mod, cu, a, q, crit)
+    np.savez_compressed(os.path.join(HERE, "g9l_rotate_iou_sample_ref.npz"), **out)
+    print("g9l: overlapping pairs", {c: int((out["iou_c%d" % c] > 0).sum()) for c in (-1, 1)})
+
+
+def g14():
+    """The reference's KittiRCNNDataset.filtrate_objects + kitti_utils.objs_to_boxes3d in EVAL and TRAIN mode on the label file of
+    tests/test_host_logic.py::test_recall_gt_set_is_class_only_in_eval_like_the_reference (LABELS_GT, stored beside the boxes)."""
+    import tempfile
+    from test_host_logic import LABELS_GT
+    H.install()
+    from lib.datasets.kitti_rcnn_dataset import KittiRCNNDataset
+    import lib.utils.kitti_utils as ku
+    from lib.config import cfg as rcfg
+    assert rcfg.PC_REDUCE_BY_RANGE
+    with tempfile.TemporaryDirectory() as d:
+        path = os.path.join(d, "000001.txt")
+        with open(path, "w") as f:
+            f.write(LABELS_GT)
+        objs = ku.get_objects_from_label(path)
+
+    class Fake:
+        classes = ("Background", "Car")
+        check_pc_range = staticmethod(KittiRCNNDataset.check_pc_range)
+    out = {"labels": np.array(LABELS_GT)}
+    for mode in ("EVAL", "TRAIN"):
+        Fake.mode = mode
+        out["boxes3d_" + mode.lower()] = ku.objs_to_boxes3d(KittiRCNNDataset.filtrate_objects(Fake, objs)).astype(np.float32)
+    np.savez_compressed(os.path.join(HERE, "g14_kitti_labels_ref.npz"), **out)
+    print("g14: kept", {m: len(out["boxes3d_" + m]) for m in ("eval", "train")})
+
+
 def g_ops():
     rng = np.random.default_rng(1)
     out = {}
@@ -619,9 +668,9 @@ def g_ops():
 
 if __name__ == "__main__":
     assert H.available(), "/root/reference is not mounted: fixtures can only be regenerated in the build container"
-    todo = sys.argv[1:] or ["g5", "g7", "g_ops", "g8", "g8i", "g9", "g10", "g11", "g12u", "g12l", "g12p", "g13"]      # e.g. ``make_golden.py g9 g10``
+    todo = sys.argv[1:] or ["g5", "g7", "g_ops", "g8", "g8i", "g9", "g9l", "g10", "g11", "g12u", "g12l", "g12p", "g13", "g14"]      # e.g. ``make_golden.py g9 g10``
     for name in todo:
-        {"g5": g5, "g7": g7, "g_ops": g_ops, "g8": g8, "g8i": lambda: g8(intensity=True), "g9": g9, "g10": g10, "g11": g11, "g12u": lambda: g12("u"), "g12l": lambda: g12("l"), "g12p": lambda: g12("p"), "g13": lambda: g12("d")}[name]()
+        {"g5": g5, "g7": g7, "g_ops": g_ops, "g8": g8, "g8i": lambda: g8(intensity=True), "g9": g9, "g9l": g9l, "g10": g10, "g11": g11, "g12u": lambda: g12("u"), "g12l": lambda: g12("l"), "g12p": lambda: g12("p"), "g13": lambda: g12("d"), "g14": g14}[name]()
     for f in sorted(os.listdir(HERE)):
         if f.endswith(".npz"):
             print(f, os.path.getsize(os.path.join(HERE, f)) // 1024, "KiB")

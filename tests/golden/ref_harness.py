@@ -1,6 +1,6 @@
 """IN-CONTAINER ONLY: import the reference's Python model (read-only, from /root/reference) on
 CPU with the oracle as its operator backend.  Used by make_golden.py to produce the committed
-fixtures and by tests that are skipped when /root/reference is absent (i.e. on the GPU box).
+fixtures; no test imports it.
 
 Shims (none copies reference code):
   1. ``easydict.EasyDict`` stand-in (attribute dict)          -- package absent from the image

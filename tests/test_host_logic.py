@@ -499,7 +499,7 @@ def test_recall_gt_set_is_class_only_in_eval_like_the_reference(tmp_path):
     """the --recall ground truth must be every labelled object of the class -- the reference's
     filtrate_objects applies check_pc_range in TRAIN mode only (kitti_rcnn_dataset.py:155-176).  The label file holds
     four Cars: one in range, one beyond x = -40, one beyond z = 70.4, one below y = 3 -> eval keeps all 4, train keeps 1.
-    In the build container the reference's own filtrate_objects is run on the same file and must agree."""
+    The reference's own filtrate_objects on the same file (fixture g14) must agree."""
     K = pkg("kitti_io")
     cfg = pkg("config").default_eval_cfg()
     d = tmp_path / "KITTI" / "object" / "training"
@@ -514,25 +514,10 @@ def test_recall_gt_set_is_class_only_in_eval_like_the_reference(tmp_path):
     assert ev.shape == (4, 7) and tr.shape == (1, 7)
     np.testing.assert_allclose(ev[1], [-55.0, 1.70, 30.0, 1.45, 1.55, 3.70, 0.30], rtol=1e-6)
     np.testing.assert_allclose(tr[0], ev[0])
-    if os.path.isdir("/root/reference/pointrcnn"):
-        import sys
-        sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden"))
-        import ref_harness as H
-        H.install()
-        from lib.datasets.kitti_rcnn_dataset import KittiRCNNDataset
-        import lib.utils.kitti_utils as ku
-        from lib.config import cfg as rcfg
-        assert rcfg.PC_REDUCE_BY_RANGE
-        objs = ku.get_objects_from_label(str(d / "label_2" / "000001.txt"))
-
-        class Fake:
-            classes = ("Background", "Car")
-            check_pc_range = staticmethod(KittiRCNNDataset.check_pc_range)
-        for mode, want in (("EVAL", ev), ("TRAIN", tr)):
-            Fake.mode = mode
-            kept = KittiRCNNDataset.filtrate_objects(Fake, objs)
-            ref = ku.objs_to_boxes3d(kept)
-            np.testing.assert_allclose(ref, want, rtol=1e-6)
+    g = load("g14_kitti_labels_ref.npz")                  # the reference's own filtrate_objects + objs_to_boxes3d on this file
+    assert str(g["labels"]) == LABELS_GT
+    for mode, want in (("eval", ev), ("train", tr)):
+        np.testing.assert_allclose(g["boxes3d_" + mode], want, rtol=1e-6)
 
 
 def test_compiled_extension_modules_load_and_export_the_reference_bindings():
@@ -632,11 +617,19 @@ def test_rcnn_use_intensity_in_the_joint_path_fails_as_the_reference_does(oracle
 
 
 class _FailingSource:
-    """a scene source whose third scene cannot be loaded (picklable: module level)"""
+    """a scene source whose third scene cannot be loaded (picklable: module level).  The broken scene waits until the file `gate`
+    exists, so that the failure of batch 1 cannot overtake batch 0 on its way to the parent (two loaders run the two batches)."""
     ids = list(range(16))
+
+    def __init__(self, gate):
+        self.gate = gate
 
     def load(self, i):
         if i == 10:
+            import time
+            t0 = time.monotonic()
+            while not os.path.exists(self.gate) and time.monotonic() - t0 < 60.0:
+                time.sleep(0.01)
             raise ValueError("scene %d is broken" % i)
         return np.full((64, 3), float(i), np.float32), pkg("synth").SyntheticCalib(), (375, 1242)
 
@@ -680,9 +673,13 @@ def test_shared_loader_feed_hands_over_the_loaders_bits_in_order(tmp_path):
             small.next()
     finally:
         small.close()
-    bad = E._ShmFeed(_FailingSource(), _FailingSource.ids, 8, False, 2, "fork", False, 8 * 64 * 3)
+    gate = tmp_path / "batch0_taken"
+    bad = E._ShmFeed(_FailingSource(str(gate)), _FailingSource.ids, 8, False, 2, "fork", False, 8 * 64 * 3)
     try:
-        bad.next()
+        host, slot, counts, calibs, shapes = bad.next()
+        assert np.array_equal(host.numpy()[:, 0, 0], np.arange(8, dtype=np.float32)) and counts == [64] * 8
+        bad.release(slot, None)
+        gate.write_text("")
         with pytest.raises(RuntimeError, match="scene 10 is broken"):
             bad.next()
     finally:
