@@ -122,6 +122,10 @@ SIGNATURES = {
     "prcnn_kitti_image_stats": [_I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _D, _D, _I, _I, _P, _P, _P, _P],
     "prcnn_kitti_collect_scores": [_I, _P, _P, _P, _P, _P, _P, _P, _I, _D, _P, _P],
     "prcnn_kitti_accumulate_pr": [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _D, _P, _I, _I, _P],
+    "prcnn_stat_norm_count": [_P, _P],
+    "prcnn_stat_norm_choose": [_P, _P],
+    "prcnn_stat_norm_write": [_P, _P],
+    "prcnn_stat_norm_occlusion": [_I, _I, _I, _I, _P, _P, _P, _P],
 }
 
 _lib = None

@@ -619,6 +619,36 @@ int prcnn_kitti_accumulate_pr(int n_img, const long long *gt_nums, const long lo
                               int metric, double min_overlap, const double *thresholds, int n_thresh, int compute_aos,
                               double *pr);
 
+/* Statistical normalization (stat_norm/norm.py:186-330 rescale_ptc) over a batch of ragged scenes (csrc/stat_norm.hip).
+ * Device pointers; offsets are prefix sums over the scenes (n_scenes + 1 entries).  Points: velo (sum n, 4) f32 raw .bin rows,
+ * pt_off; 64-point tiles: tile_off; rescaled boxes: box_off, boxd (n_box, 64) f64 records, boxi (n_box, 16) i32 state (zeroed),
+ * mm (n_box, 6) f64 min xyz / max xyz (+inf / -inf; avoid_conflict only); bt_cnt (sum nbox * ntile) i32 at bt_off per scene;
+ * rem_cnt (sum ntile) i32; scene_i (n_scenes, 4) i32 = [remainder, patch points, output points, -]; calib (n_scenes, 42) f64 =
+ * V2C, R0, inv(R0), C2V; out_off / out (sum n_out, 4) f32 for the write pass.  The field layout is stat_norm.py's _SnBatch. */
+typedef struct prcnn_sn_batch {
+    int n_scenes, max_tiles, max_boxes, avoid;
+    const int *pt_off, *tile_off, *box_off;
+    const long long *bt_off;
+    const float *velo;
+    const double *calib, *boxd;
+    int *boxi;
+    double *mm;
+    int *bt_cnt, *rem_cnt, *scene_i;
+    const long long *out_off;
+    float *out;
+} prcnn_sn_batch;
+/* pass 1: inside counts per (box, tile) -> ordered exclusive offsets, inside totals, env_mask0 counts, min / max, remainder */
+int prcnn_stat_norm_count(const prcnn_sn_batch *batch, void *stream);
+/* pass 2: (avoid_conflict) 11 env counts per box; then per box the ratio index (-1 = ratio 0, 0..10 = np.arange(1, -0.1, -0.1))
+ * and patch base, per scene the output size */
+int prcnn_stat_norm_choose(const prcnn_sn_batch *batch, void *stream);
+/* pass 3: the output clouds (x, y, z, 1) f32, boxd's write-pass fields (chosen scale, align_front shifts) filled by the host */
+int prcnn_stat_norm_write(const prcnn_sn_batch *batch, void *stream);
+/* postprocessing's occlusion map: rects (n_obj, 4) i32 = half-open [y0, y1) x [x0, x1) per object in painting order, obj_off per
+ * scene; counts (n_obj) i32 (zeroed) += pixels whose last painter is the object.  At most 2048 objects per scene. */
+int prcnn_stat_norm_occlusion(int n_scenes, int h, int w, int max_objects, const int *obj_off, const int *rects, int *counts,
+                              void *stream);
+
 #ifdef __cplusplus
 }
 #endif
