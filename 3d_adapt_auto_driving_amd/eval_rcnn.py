@@ -32,8 +32,6 @@ from .net.point_rcnn import PointRCNN
 from .net.fast_infer import FastPointRCNN
 from ._lib import has_entry
 
-# PRCNN_NO_RCNN_SPLIT=1: the RCNN stage's RoI pooling / sampling / grouping geometry stays on the feature stream (A/B switch)
-SPLIT_RCNN = os.environ.get("PRCNN_NO_RCNN_SPLIT") != "1"
 # (removed in round 4, results in DESIGN.md section 7: PRCNN_GEO_THREAD -- geometry chains enqueued by a helper thread, slower: the GIL;
 #  PRCNN_RCNN_GEO_STREAM -- the RCNN's geometry on a stream of its own, slower: a 5th busy stream shares a hardware queue; PRCNN_GATE --
 #  chains only started at the end of an RPN stage, slower since the stages are our own ticketed kernels; PRCNN_STREAM_SKEW)
@@ -63,8 +61,7 @@ FUSED_POSTPROCESS = True     # final stage through the fused HIP entry when the 
 # event waits.  Round 5, second session: back on the proposal stream by default -- with the pack launches, half of the RoI geometry and the
 # padded tiles gone that stream is busy 0.35-0.40 ms of a 0.97-ms step and the feature stream is the fullest (0.78): K = 20 7253 / 7238 /
 # 7226 -> 7323 / 7261 / 7256 scenes/s, LiDAR-shaped 5109 / 5134 / 5143 -> 5183 / 5175 / 5180 (three alternating runs of five windows each);
-# K = 100 unchanged.  PRCNN_FINAL_ON_FEATURE=1: behind the RCNN features on the feature stream (round 4).
-FINAL_ON_FEATURE = os.environ.get("PRCNN_FINAL_ON_FEATURE", "0") != "0"
+# K = 100 unchanged.
 # batches of a geometry group that share the launches of the stages behind the geometry in the graphed runner (GraphedRunner.pair):
 # 2 (measured: 6040-6150 / 6980-7050 scenes/s at K = 20 / 100 against 5800-5860 / 6730-6750 with 1, LiDAR-shaped 4270-4350 / 4930-4970
 # against 4140-4160 / 4830; 4: 6060 / 6780 and 4330 / 4750); 1: every batch its own launches
@@ -303,30 +300,25 @@ class PipelinedRunner:
         for t in (st["rpn_scores_raw"], st["rpn_reg"], st.get("rpn_boxes"), st["backbone_xyz"]):
             if t is not None:
                 t.record_stream(self.tail)
-        rois, roi_scores, ev_prop, rg = self._propose_on_tail(st, ev_rpn, main)
+        rois, roi_scores, ev_prop, rg = self._propose_on_tail(st, ev_rpn)
         done = self._finish_inflight()
         self._inflight = (cur, st, rois, roi_scores, ev_prop, None, None, rg)
         return done
 
-    def _propose_on_tail(self, st, ev_rpn, main):
+    def _propose_on_tail(self, st, ev_rpn):
         """Proposal layer of the batch whose RPN stage ends at `ev_rpn`, on the tail stream -- and right behind it the part of
         its RCNN stage that needs the RoIs and coordinates only (RoI pooling, FPS, ball queries, row lists: ten latency-bound
         launches, 0.3 ms of every step while they sat on the feature stream in front of the RCNN's MFMA kernels).
-        -> rois, scores, event (RoIs and, if split, the RCNN geometry are ready), RCNN geometry state or None."""
-        rg = None
+        -> rois, scores, event (RoIs and the RCNN geometry are ready), RCNN geometry state."""
         with torch.cuda.stream(self.tail):
             self.tail.wait_event(ev_rpn)
             rois, roi_scores = self.engine.propose(st)
-            if SPLIT_RCNN:
-                # reads st["rpn_features"] (feature-stream memory: st stays referenced until the feature stream has run this
-                # batch's RCNN stage, which waits for ev_prop) and makes ~15 tensors on the tail stream that the feature stream
-                # reads: they are kept in self._inflight until the tail stream has waited for that RCNN stage (_finish_inflight)
-                rg = self.engine.rcnn_geometry(st, rois)
+            # reads st["rpn_features"] (feature-stream memory: st stays referenced until the feature stream has run this
+            # batch's RCNN stage, which waits for ev_prop) and makes ~15 tensors on the tail stream that the feature stream
+            # reads: they are kept in self._inflight until the tail stream has waited for that RCNN stage (_finish_inflight)
+            rg = self.engine.rcnn_geometry(st, rois)
             ev_prop = torch.cuda.Event()
             ev_prop.record(self.tail)
-        if rg is None:
-            for t in (rois, st["seg_result"], st["pts_depth"], st["depth_norm"]):   # made on the tail stream, read by the RCNN stage on the feature stream
-                t.record_stream(main)
         return rois, roi_scores, ev_prop, rg
 
     # ---- grouped geometry: ONE chain per `group` batches -------------------------------------------------------
@@ -357,7 +349,7 @@ class PipelinedRunner:
             with torch.cuda.device(self.device), torch.cuda.stream(side):
                 # urgent (cold start: the first batch of this group is waited for right now): SA levels batch by batch, so that batch 0
                 # is ready before the other three are computed; otherwise over the group's clouds at once (a quarter of the launches)
-                geos = self.engine.geometry_group(batch_list, on_batch_done=mark, group_sa=False if urgent else None)
+                geos = self.engine.geometry_group(batch_list, on_batch_done=mark, group_sa=not urgent)
                 if len(evs) != len(geos):
                     ev = torch.cuda.Event()
                     ev.record(side)
@@ -392,7 +384,7 @@ class PipelinedRunner:
         for t in (st["rpn_scores_raw"], st["rpn_reg"], st.get("rpn_boxes"), st["backbone_xyz"]):
             if t is not None:
                 t.record_stream(self.tail)
-        rois, roi_scores, ev_prop, rg = self._propose_on_tail(st, ev_rpn, main)
+        rois, roi_scores, ev_prop, rg = self._propose_on_tail(st, ev_rpn)
         done = self._finish_inflight()
         self._inflight = (cur, st, rois, roi_scores, ev_prop, ch["side"], ch["geo"], rg)
         return done
@@ -446,30 +438,25 @@ class PipelinedRunner:
         cur, st, rois, roi_scores, ev_prop, side, geo, rg = self._inflight
         self._inflight = None
         main.wait_event(ev_prop)
-        out = self.engine.rcnn_stage(st, rois) if rg is None else self.engine.rcnn_features(rg)
+        out = self.engine.rcnn_features(rg)
         ev_rcnn = torch.cuda.Event()
         ev_rcnn.record(main)
         if side is not None:
             # the batch's geometry (read by its RPN stage, its spatial groups by this RCNN stage) retires: kept until the side
             # stream that owns the memory has been made to wait for this point (see _launch_group)
             self._retired.append((side, ev_rcnn, geo))
-        post = main if FINAL_ON_FEATURE else self.tail
-        if not FINAL_ON_FEATURE:
-            for t in (out["rcnn_cls"], out["rcnn_reg"]):
-                t.record_stream(self.tail)
-        with torch.cuda.stream(post):
-            if not FINAL_ON_FEATURE:
-                self.tail.wait_event(ev_rcnn)
+        for t in (out["rcnn_cls"], out["rcnn_reg"]):
+            t.record_stream(self.tail)
+        with torch.cuda.stream(self.tail):
+            self.tail.wait_event(ev_rcnn)
             ret = {"rois": rois, "rcnn_cls": out["rcnn_cls"], "rcnn_reg": out["rcnn_reg"]}
             det = postprocess(self.cfg, ret, cur.shape[0])
             det.update(ret)
             ready = torch.cuda.Event()
-            ready.record(post)
-        if FINAL_ON_FEATURE:
-            rois.record_stream(main)                  # produced on the proposal stream, read by the final stage here
+            ready.record(self.tail)
         del rg                                        # tail-stream memory, read on the feature stream up to ev_rcnn: the tail stream waits for it above
         det["ready"] = ready
-        det["stream"] = post
+        det["stream"] = self.tail
         return det
 
     @torch.no_grad()
@@ -636,8 +623,8 @@ class GraphedRunner:
       * a group slot holds the coordinates of `group` batches (copied in when their chain is launched: 1.5 MB per batch), the
         geometry graph of the group (FastPointRCNN.geometry_group: FPS / ball queries / row lists / three-NN / the early SA levels,
         on a side stream) and, per MEMBER of the group (`pair` consecutive batches: 2 by default), four graphs: RPN stage (feature
-        stream), proposal layer + RCNN geometry (tail stream), RCNN features (feature stream), final stage (behind them on the feature
-        stream; FINAL_ON_FEATURE = 0: tail stream) -- pair x B scenes per launch of each;
+        stream), proposal layer + RCNN geometry (tail stream), RCNN features (feature stream), final stage (behind them on the tail
+        stream) -- pair x B scenes per launch of each;
       * depth / group + 1 group slots rotate: a slot is rewritten only after the RCNN stages of its previous batches (an event wait
         on the side stream, normally long past);
       * submit() hands back the detections of an EARLIER batch, in submit order, or None (a member's stages are launched when its
@@ -745,10 +732,9 @@ class GraphedRunner:
         with torch.cuda.stream(self.feat):
             out = eng.rcnn_features(tl["rg"])
         self.feat.synchronize()
-        post_stream = self.feat if FINAL_ON_FEATURE else self.tail
-        with torch.cuda.stream(post_stream):
+        with torch.cuda.stream(self.tail):
             final_stage(tl, out)
-        post_stream.synchronize()
+        self.tail.synchronize()
         del geos, st, tl, out
 
         # ONE MEMORY POOL PER GRAPH.  Graphs that share a pool may only be replayed in the order of their capture with the outputs of
@@ -769,7 +755,7 @@ class GraphedRunner:
                 g_rcnn, out = self._capture(self.feat, pool(), lambda: eng.rcnn_features(tl["rg"]))
                 # (captured on the stream family it replays on: its kernels' library scratch is keyed by the capture stream, and graphs
                 #  that share scratch must replay on one stream, in order)
-                g_post, det = self._capture(post_stream, pool(), lambda: final_stage(tl, out))
+                g_post, det = self._capture(self.tail, pool(), lambda: final_stage(tl, out))
                 slot["members"].append({"g_rpn": g_rpn, "g_tail": g_tail, "g_rcnn": g_rcnn, "g_post": g_post,
                                         "st": st, "tl": tl, "out": out, "det": det,
                                         "ev_rpn": torch.cuda.Event(), "ev_prop": torch.cuda.Event(), "ev_rcnn": torch.cuda.Event(),
@@ -937,18 +923,16 @@ class GraphedRunner:
         if _GRAPH_DEBUG & 4:
             torch.cuda.synchronize(self.device)
             print("[graph debug] slot %d member %d rcnn done" % (s, mi), flush=True)
-        post = feat if FINAL_ON_FEATURE else tail
-        if not FINAL_ON_FEATURE:
-            tail.wait_event(m["ev_rcnn"])
-        with torch.cuda.stream(post):
+        tail.wait_event(m["ev_rcnn"])
+        with torch.cuda.stream(tail):
             m["g_post"].replay()
-            m["ready"].record(post)
+            m["ready"].record(tail)
         if _GRAPH_DEBUG & 4:
             torch.cuda.synchronize(self.device)
             print("[graph debug] slot %d member %d done" % (s, mi), flush=True)
         if self.pair == 1:
             det = dict(m["det"])
-            det["ready"], det["stream"] = m["ready"], post
+            det["ready"], det["stream"] = m["ready"], tail
             self._out.append(det)
             return
         B = self.shape[0]
@@ -965,7 +949,7 @@ class GraphedRunner:
                     det[key] = v[h * per:(h + 1) * per]
             # round 5: the final stage writes one blob per BATCH of the member (prcnn_rcnn_postprocess_blobs): one copy per batch
             det["blob"] = blobs[h] if blobs is not None else None
-            det["ready"], det["stream"] = m["ready"], post
+            det["ready"], det["stream"] = m["ready"], tail
             self._out.append(det)
 
     @torch.no_grad()

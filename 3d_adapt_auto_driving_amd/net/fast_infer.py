@@ -31,7 +31,7 @@ from .. import iou3d_utils
 
 
 USE_ROIPOOL_CANONICAL = True   # RCNN input assembly through roipool3d_canonical_kernel (False: torch-op sequence)
-USE_RCNN_POINT_MLP = os.environ.get("PRCNN_NO_POINT_MLP") is None      # RCNN entrance chain through csrc/rcnn_point_mlp.hip (False: library GEMMs + concat)
+USE_RCNN_POINT_MLP = True      # RCNN entrance chain through csrc/rcnn_point_mlp.hip (False: library GEMMs + concat; tests patch it)
 USE_XYZ_MLP = True      # coordinates-only SA scales through csrc/sa_xyz_mlp.hip (False: grouped GEMM chain)
 # SA levels over the DISTINCT grouped rows only (csrc/sa_packed.hip: the back-filled copies of a ball's first hit are
 # skipped, bit-identical results).  PRCNN_NO_PACK=1 is the A/B switch back to all nsample rows (csrc/sa_mlp_fused.hip).
@@ -39,17 +39,6 @@ USE_PACKED = os.environ.get("PRCNN_NO_PACK") is None
 # RoI pooling fills a box holding fewer than 512 points by repeating them (roipool3d_kernel.cu:152-159): the per-point
 # RCNN entrance chain and SA1 run over the DISTINCT pooled points only (bit-identical results).  PRCNN_NO_POOL_DEDUP=1: A/B.
 USE_POOL_DEDUP = os.environ.get("PRCNN_NO_POOL_DEDUP") is None
-# ... and the SA1 centres FPS picks among those copies are copies of one another (same coordinates, same ball, same SA1 output):
-# the deeper RCNN levels drop the rows of every point that is not the first of its kind (prcnn_dup_rep + prcnn_ball_pack_rep;
-# round 3: 7.5x fewer SA2 rows on LiDAR-shaped scenes, bit-identical results).  PRCNN_NO_CENTRE_DEDUP=1: A/B.
-USE_CENTRE_DEDUP = os.environ.get("PRCNN_NO_CENTRE_DEDUP") is None
-USE_CENTRE_SKIP = os.environ.get("PRCNN_NO_CENTRE_SKIP") is None       # ... and such a centre gets no rows of its own either (A/B)
-# sampling, ball query and representative map of both sampled RCNN levels for every RoI cloud in one launch; PRCNN_NO_ROI_GEOMETRY=1:
-# the six separate launches (A/B, same results)
-USE_ROI_GEOMETRY = os.environ.get("PRCNN_NO_ROI_GEOMETRY") is None
-USE_ROI_PACKS = os.environ.get("PRCNN_NO_ROI_PACKS") is None      # ... and their distinct-row lists out of the same launch (round 5)
-USE_CENTRE_ROWS = os.environ.get("PRCNN_NO_CENTRE_ROWS") is None  # the RCNN's second level: per-point layer over the representative level-1 centres only (round 5)
-USE_POOLED_ROWS = os.environ.get("PRCNN_NO_POOLED_ROWS") is None  # the RCNN entrance over the list of distinct pooled rows, not whole tiles per RoI (round 5)
 USE_POINT_LAYER = os.environ.get("PRCNN_LIB_GEMM") is None     # per-point layers (FP modules, heads) on the own MFMA layer kernel
 # every per-point width zero-padded to a multiple of 128 (SA level outputs, FP inputs, narrow head outputs), so that NO layer
 # of the engine is left to a GEMM library: fixed summation order everywhere, reproduced bit for bit by the oracle
@@ -60,13 +49,8 @@ USE_RPN_TAIL = os.environ.get("PRCNN_NO_RPN_TAIL") is None
 USE_SCALE_BATCH = True      # (a module constant since round 6; tests patch it)
 # layers 1-3 + pool of a wide scale in one kernel (csrc/sa_wide.hip); False: gather / layer / layer+pool launches
 USE_SA_NARROW = True        # RPN SA2's scales without their zero padding (csrc/sa_packed.hip), their per-point parts in one product
-USE_SA2_BATCH = os.environ.get("PRCNN_NO_SA2_BATCH") is None        # the two 128-wide scales of an MSG level (RPN SA2) in one launch per stage (round 5)
 USE_WIDE_FUSED = True       # (a module constant since round 6; tests/test_gpu_shadow.py patches it for the layer-by-layer variant)
-# ... and layer 1 inside as well where a level groups every point once (the RCNN's GroupAll level; csrc/sa_wide3.hip);
-# PRCNN_NO_WIDE_FUSED3=1: the per-point layer as a launch of its own in front of csrc/sa_wide.hip (A/B, same bits)
-USE_WIDE_FUSED3 = os.environ.get("PRCNN_NO_WIDE_FUSED3") is None
-# RoI pooling culls by 64-point spatial groups of the scene (built with the geometry chain); PRCNN_NO_POOL_GROUPS=1: full sweep
-USE_XYZ_LEVEL_EARLY = os.environ.get("PRCNN_NO_XYZ_EARLY") != "1"    # leading SA levels of a coordinates-only backbone computed with the geometry (side stream)
+# leading SA levels of a coordinates-only backbone computed with the geometry (side stream); 0: none
 EARLY_LEVELS = int(os.environ.get("PRCNN_EARLY_LEVELS", "4"))
 EARLY_FP = int(os.environ.get("PRCNN_EARLY_FP", "2"))                 # ... plus this many of the coarsest FP modules, over the 32 clouds of a group in one launch each (round 3: 1 -- the geometry chains were the longer side then; round 4: 3, see EARLY_TAIL; round 5: 2 -- with the RCNN's padded tiles gone the feature stream has room again and the geometry chains bind: profiles/sensitivity_probe.py, 7860 -> 7980 / LiDAR-shaped 5500 -> 5570 at K = 100)
 # ... and the finest FP module + both RPN heads as well (round 4 experiment, needs EARLY_FP >= number of FP modules - 1): the RPN backbone has
@@ -75,20 +59,11 @@ EARLY_FP = int(os.environ.get("PRCNN_EARLY_FP", "2"))                 # ... plus
 # the 32 clouds of a group) buys +4.6 % at K = 100 (6382 against 6103 scenes/s; K = 20: level).  The fused tail on top of it -- a 256-workgroup
 # MFMA kernel of 0.7 ms per group on a geometry stream -- costs it again: 6042 at K = 100, 5158 against 5314 at K = 20.  Off.
 # (round 6: the switch PRCNN_EARLY_TAIL and its branch are gone.)
-# ... in between: only the coarse-level product G of the finest FP module (4096 rows per cloud, K = 256) goes with the geometry; the fused
-# tail kernel, which reads it, stays on the feature stream
-EARLY_G0 = os.environ.get("PRCNN_EARLY_G0", "1") == "1"
-GROUP_SA = os.environ.get("PRCNN_NO_GROUP_SA") != "1"                 # ... and over all batches of a geometry group at once
-USE_POOL_GROUPS = os.environ.get("PRCNN_NO_POOL_GROUPS") is None
 # feature-propagation modules: the first layer is linear in front of its ReLU and the interpolation is a weighted sum, so the
 # interpolated columns of the layer are applied at the COARSE level (a quarter of the rows) and the product is interpolated in the
 # epilogue of the layer over the skip features (prcnn_packed_layer_interp).  Another association of the same sums than the
 # reference's (~1e-7 relative); PRCNN_NO_FP_LINEAR=1: interpolate, concatenate, then the layer, as the reference does (A/B).
 USE_FP_LINEAR = os.environ.get("PRCNN_NO_FP_LINEAR") is None
-# round 5: the proposal layer's box decode inside the fused RPN tail kernel (csrc/rpn_tail.hip rpn_tail_lin_kernel<true>): the (B, N, 76)
-# regression tensor never reaches HBM and rpn_decode_kernel leaves the proposal stream; 0: tail writes the rows, the proposal layer
-# decodes them (same boxes, bit for bit: A/B)
-USE_TAIL_DECODE = os.environ.get("PRCNN_TAIL_DECODE", "1") != "0"
 
 
 class ZeroArena:
@@ -172,8 +147,8 @@ _STRICT = [False]        # set while an engine whose every layer is covered by t
 
 
 def _lib_gemm_allowed():
-    """A GEMM library may only appear on the engine's path when an A/B switch asked for it (all-rows mode, PRCNN_LIB_GEMM,
-    PRCNN_NO_POINT_MLP, ...) or when the network's shapes are not the ones the hand-written kernels cover (tiny test
+    """A GEMM library may only appear on the engine's path when a switch asked for it (all-rows mode, PRCNN_LIB_GEMM,
+    USE_RCNN_POINT_MLP = False, ...) or when the network's shapes are not the ones the hand-written kernels cover (tiny test
     configurations).  With a covered network (default.yaml) and every product switch at its default, a layer that lands here means
     a silently different engine was about to run."""
     return (not _STRICT[0] or not USE_PACKED or not USE_POINT_LAYER or not USE_RCNN_POINT_MLP or not USE_POOL_DEDUP
@@ -518,10 +493,11 @@ class FastPointRCNN:
                        for ix, sc in zip(lev["idx"], self.sa[k][1])]
 
     @torch.no_grad()
-    def geometry_group(self, xyz_list, on_batch_done=None, group_sa=None):
+    def geometry_group(self, xyz_list, on_batch_done=None, group_sa=True):
         """The xyz-only chain for SEVERAL batches in one pass: the serial FPS of a scene occupies one CU for ~6 ms whatever
         the batch, so the chain's latency does not grow with the number of scenes -- its throughput does.  Returns one
-        geometry dict per batch (views into the group's tensors; the packed row lists are built per batch)."""
+        geometry dict per batch (views into the group's tensors; the packed row lists are built per batch).  group_sa=False:
+        the early SA levels batch by batch (the runner's cold start, where batch 0 is waited for right away)."""
         sizes = [x.shape[0] for x in xyz_list]
         if len(xyz_list) == 1:
             geo1 = [self.geometry(xyz_list[0])]
@@ -546,12 +522,12 @@ class FastPointRCNN:
         ext = pu.pointnet2
         same = len(set(sizes)) == 1 and has_entry(ext, "ball_pack_groups_wrapper")
         gpacks = None
-        # GROUP_SA: the early SA levels (see _xyz_level) over ALL clouds of the group in one pass -- one row list per (level, scale)
+        # group_sa: the early SA levels (see _xyz_level) over ALL clouds of the group in one pass -- one row list per (level, scale)
         # over the group's clouds, one launch per stage instead of one per batch: a quarter of the host's launches for these levels
         # (the host's enqueue time is what limits a step now).  A cloud's rows do not depend on which list holds them: same bits.
         # Every batch then gets views of the group's outputs and needs no row lists of its own for those levels.
         n_early = 0
-        if GROUP_SA if group_sa is None else group_sa:
+        if group_sa:
             for k in range(min(EARLY_LEVELS, len(self.sa))):
                 self._pack_level(k, geo["l_xyz"][k], geo["sa"][k], arena)
             self._xyz_level(geo, arena)
@@ -569,8 +545,6 @@ class FastPointRCNN:
                  "groups": None if groups is None else (groups[0][lo:hi], groups[1][lo:hi])}
             if geo.get("fp_out"):
                 g["fp_out"] = {kk: v[lo:hi] for kk, v in geo["fp_out"].items()}
-            if geo.get("tail_G") is not None:
-                g["tail_G"] = geo["tail_G"][lo:hi]
             for k, lev in enumerate(geo["sa"]):
                 part = {"sel": lev["sel"][lo:hi], "new_xyz": lev["new_xyz"][lo:hi], "idx": [ix[lo:hi] for ix in lev["idx"]],
                         "pack": [None] * len(lev["idx"])}
@@ -593,7 +567,7 @@ class FastPointRCNN:
         """Spatial groups of the input clouds for the RCNN's RoI pooling (csrc/fps.hip prcnn_point_groups): xyz only, so they
         ride with the geometry chain on its side stream."""
         rp = roipool3d_utils.roipool3d_cuda
-        if not (USE_POOL_GROUPS and self.cfg.RCNN.ENABLED and has_entry(rp, "point_groups") and xyz.shape[1] % 64 == 0 and xyz.shape[1] <= 65536):
+        if not (self.cfg.RCNN.ENABLED and has_entry(rp, "point_groups") and xyz.shape[1] % 64 == 0 and xyz.shape[1] <= 65536):
             return None
         return rp.point_groups(xyz)
 
@@ -610,7 +584,7 @@ class FastPointRCNN:
         and the model's weights only -- so does the whole backbone -- and are computed WITH the geometry, on the geometry's stream
         (the pipelined runner: a side stream that has slack, off the feature stream's critical path).  Stored as
         geo["sa"][k]["out"]; `_backbone` starts behind them.  Same kernels, same arguments as in `_backbone`: same bits."""
-        if not (USE_XYZ_LEVEL_EARLY and USE_PACKED and USE_XYZ_MLP and self.sa and self.sa[0][1] and
+        if not (USE_PACKED and USE_XYZ_MLP and self.sa and self.sa[0][1] and
                 all(sc[3] == 0 for sc in self.sa[0][1])):
             return
         l_xyz, prev = geo["l_xyz"], None
@@ -636,10 +610,6 @@ class FastPointRCNN:
                 kk = len(self.fp) + i
                 idx, weight = geo["fp"][kk]
                 l_feat[kk] = geo["fp_out"][kk] = self._fp_module(kk, l_feat[kk + 1], l_feat[kk], idx, weight)
-            if (EARLY_G0 and EARLY_FP >= len(self.fp) - 1 and self.rpn_tail is not None and self.in_feat == 0
-                    and l_feat[1].shape[2] == 256 and USE_FP_LINEAR and has_entry(pu.pointnet2, "rpn_tail_lin_wrapper")):
-                kf = l_feat[1]
-                geo["tail_G"] = point_layer(kf.view(-1, kf.shape[2]), self.rpn_tail["w1"], self.rpn_tail["zero128"], False).view(kf.shape[0], kf.shape[1], 128)
 
     # ------------------------------------------------------------------ building blocks
     @staticmethod
@@ -659,7 +629,7 @@ class FastPointRCNN:
             # wider level: the same distinct rows, layer by layer (gather+affine -> MFMA layer -> MFMA layer + segmented max)
             wf, wx, b1, w2, b2, w3, b3 = mlp.wide
             pk = pack if pack is not None else ext.ball_pack_wrapper(idx, xyz, new_xyz)
-            if (dense and USE_WIDE_FUSED and USE_WIDE_FUSED3 and has_entry(ext, "sa_wide_fused3_wrapper") and feats.is_contiguous() and
+            if (dense and USE_WIDE_FUSED and has_entry(ext, "sa_wide_fused3_wrapper") and feats.is_contiguous() and
                     feats.shape[2] == wf.shape[0] and ext.sa_wide_fused3_supported(wf.shape[0], wf.shape[1], w2.shape[1], w3.shape[1])):
                 # a level that groups every point once (GroupAll): layer 1 runs inside the kernel as well -- no per-point launch, no P
                 # through HBM (csrc/sa_wide3.hip); same bits as the two calls below
@@ -751,7 +721,7 @@ class FastPointRCNN:
         if (USE_SCALE_BATCH and USE_PACKED and 2 <= len(scales) <= 4 and all(sc[2].wide is not None for sc in scales) and
                 has_entry(pu.pointnet2, "packed_layer_batch_wrapper")):
             self._sa_level_wide(cur_xyz, lev["new_xyz"], cur_feat, scales, lev["idx"], packs, out, pre)
-        elif (USE_SCALE_BATCH and USE_SA2_BATCH and USE_PACKED and len(scales) == 2 and cur_feat is not None and cur_feat.shape[2] % 128 == 0 and
+        elif (USE_SCALE_BATCH and USE_PACKED and len(scales) == 2 and cur_feat is not None and cur_feat.shape[2] % 128 == 0 and
               all(sc[2].packed is not None and sc[2].packed[5].shape[1] == 128 and sc[2].packed[0].shape[0] == cur_feat.shape[2] for sc in scales) and
               all(pk is not None for pk in packs) and has_entry(pu.pointnet2, "sa_packed_mlp_batch_wrapper")
               and has_entry(pu.pointnet2, "packed_layer_batch_wrapper")):
@@ -870,7 +840,7 @@ class FastPointRCNN:
         cfg, pl = self.cfg, self.model.rpn.proposal_layer
         M = cfg[pl.mode].RPN_POST_NMS_TOP_N
         ext3 = pl_ext()
-        if not (USE_TAIL_DECODE and USE_FP_LINEAR and self.rpn_tail is not None and getattr(pl, "fused", False) and N <= 65536
+        if not (USE_FP_LINEAR and self.rpn_tail is not None and getattr(pl, "fused", False) and N <= 65536
                 and cfg.TEST.RPN_DISTANCE_BASED_PROPOSE and M <= 128 and cfg.RPN.NMS_TYPE in ("normal", "rotate")
                 and has_entry(pu.pointnet2, "rpn_tail_lin_boxes_wrapper") and has_entry(ext3, "rpn_proposals_boxes")
                 and pu.pointnet2.rpn_tail_boxes_supported(self.rpn_tail["n_reg"], cfg.RPN.LOC_SCOPE, cfg.RPN.LOC_BIN_SIZE,
@@ -912,9 +882,7 @@ class FastPointRCNN:
             if USE_FP_LINEAR and has_entry(pu.pointnet2, "rpn_tail_lin_wrapper"):
                 # FP layer 1 over the coarse points (a quarter of the rows), interpolated inside the fused kernel
                 m = known_feat.shape[1]
-                G = geo.get("tail_G")                          # came with the geometry (EARLY_G0)
-                if G is None:
-                    G = point_layer(known_feat.view(B * m, known_feat.shape[2]), tw["w1"], tw["zero128"], False).view(B, m, 128)
+                G = point_layer(known_feat.view(B * m, known_feat.shape[2]), tw["w1"], tw["zero128"], False).view(B, m, 128)
                 if dec is not None:
                     # ... and the proposal layer's decode too: the 7-float box leaves the kernel instead of the 76-float row
                     rpn_boxes = torch.empty((B, N, 7), dtype=torch.float32, device=xyz.device)
@@ -1024,7 +992,7 @@ class FastPointRCNN:
         """the GroupAll level runs on csrc/sa_wide3.hip (the only consumer of a list whose rows carry their cloud at that level):
         `_sa_scale`'s condition for that branch, known before the level's features exist (they are the level below's output)"""
         ext = pu.pointnet2
-        if not (USE_PACKED and mlp.packed is None and mlp.wide is not None and USE_WIDE_FUSED and USE_WIDE_FUSED3
+        if not (USE_PACKED and mlp.packed is None and mlp.wide is not None and USE_WIDE_FUSED
                 and has_entry(ext, "sa_wide_fused3_wrapper") and getattr(mlp, "wide_cat", None) is not None):
             return False
         wf, wx, b1, w2, b2, w3, b3 = mlp.wide
@@ -1078,8 +1046,7 @@ class FastPointRCNN:
             a[:, :nin] = rows[:, :nin]
             rpn_part = rows[:, nin:]
         point_mlp = bool(USE_RCNN_POINT_MLP and W == 136 and rows.shape[0] % 64 == 0 and self._point_mlp_ok())
-        use_rows = bool(point_mlp and pooled_cnt is not None and USE_POOLED_ROWS and has_entry(ext, "pooled_rows_wrapper"))
-        tiles = ext.pooled_tiles_wrapper(pooled_cnt.view(-1), P) if (point_mlp and pooled_cnt is not None and not use_rows) else None
+        use_rows = bool(point_mlp and pooled_cnt is not None and has_entry(ext, "pooled_rows_wrapper"))
         cur_xyz = xyz_dense.view(B * M, P, 3) if xyz_dense is not None else flat[:, :, 0:3].contiguous()
         levels = []
         # one zero fill for this stage: the headers of its three row lists and the pooled outputs of its levels (see ZeroArena)
@@ -1088,35 +1055,34 @@ class FastPointRCNN:
         rowlist = ext.pooled_rows_wrapper(pooled_cnt.view(-1), P, *zhdr()) if use_rows else None       # the distinct pooled rows of all RoIs, back to back
         # representative map of the CURRENT level's points (None: every point counts as distinct): which of them are exact copies
         # of one another.  Level 0: pooled point k >= count is a copy of k % count (`limit`); deeper: the centres the sampling
-        # picked from copies of one source are copies of one another -- coordinates, ball and therefore features (dup_rep).
-        centre_dedup = bool(USE_CENTRE_DEDUP and pooled_cnt is not None and point_mlp and has_entry(ext, "dup_rep_wrapper"))
+        # picked from copies of one source are copies of one another -- coordinates, ball and therefore features (dup_rep).  The
+        # deeper levels drop the rows of every point that is not the first of its kind, and such a centre gets no rows of its own
+        # either (prcnn_ball_pack_rep; round 3: 7.5x fewer SA2 rows on LiDAR-shaped scenes, bit-identical results).
+        centre_dedup = bool(pooled_cnt is not None and point_mlp and has_entry(ext, "dup_rep_wrapper"))
         rep = None
         # The two sampled levels' geometry for every RoI cloud in ONE launch (a wave per RoI: csrc/fps.hip rcnn_roi_geometry_kernel)
-        # instead of FPS, ball query, representative map -- twice -- as six latency-bound launches
+        # instead of FPS, ball query, representative map -- twice -- as six latency-bound launches; and both levels' row lists written by
+        # the wave that holds the hit lists (no pack launches for these levels)
         fused_geo = None
         sa = self.rcnn_sa
-        if (USE_ROI_GEOMETRY and centre_dedup and USE_CENTRE_SKIP and len(sa) >= 2 and sa[0][0] is not None and sa[1][0] is not None
-                and has_entry(ext, "rcnn_roi_geometry_wrapper") and USE_PACKED
+        if (centre_dedup and len(sa) >= 2 and sa[0][0] is not None and sa[1][0] is not None
+                and has_entry(ext, "rcnn_roi_geometry_packs_wrapper") and USE_PACKED
                 and all(m_[3].packed is not None or m_[3].wide is not None for m_ in sa[:2])
                 and ext.rcnn_roi_geometry_supported(cur_xyz.shape[1], sa[0][0], sa[0][2], sa[1][0], sa[1][2])):
-            if USE_ROI_PACKS and has_entry(ext, "rcnn_roi_geometry_packs_wrapper"):
-                # ... and both levels' row lists written by the wave that holds the hit lists (no pack launches for these levels)
-                # (the index tensors themselves are not written on the HIP path: the packed kernels read the lists, `idx` is asked for its shape;
-                #  the lists' rows carry their cloud: no padded last tile per RoI cloud)
-                hd = zhdr() + zhdr()
-                rc = all(m_[3].packed is not None for m_ in sa[:2])        # the consumers that read lists whose rows carry their cloud
-                # ... and, in that form, the list of the GroupAll level above them (one group per RoI: no clouds merged to fill tiles)
-                ga = bool(rc and hd and len(sa) == 3 and sa[2][0] is None and self._groupall_fused3_ok(sa[2][3], sa[1][3]))
-                # ... and the level-1 centres that are their own representatives as a row list: level 2's per-point layer over those rows only
-                cr = bool(rc and hd and USE_CENTRE_ROWS and has_entry(ext, "rows_gemm128_rows_wrapper") and sa[1][3].packed is not None
-                          and tuple(sa[1][3].packed[0].shape) == (128, 128))
-                extra = ()
-                if hd:
-                    extra = hd + (False, rc) + ((zhdr()[0], True) if ga else (None, False)) + ((zhdr()[0], True) if cr else ())
-                fused_geo = ext.rcnn_roi_geometry_packs_wrapper(cur_xyz, pooled_cnt.view(-1), sa[0][0], sa[0][1], sa[0][2], sa[1][0], sa[1][1],
-                                                                sa[1][2], *extra)
-            else:
-                fused_geo = ext.rcnn_roi_geometry_wrapper(cur_xyz, pooled_cnt.view(-1), sa[0][0], sa[0][1], sa[0][2], sa[1][0], sa[1][1], sa[1][2])
+            # (the index tensors themselves are not written on the HIP path: the packed kernels read the lists, `idx` is asked for its shape;
+            #  the lists' rows carry their cloud: no padded last tile per RoI cloud)
+            hd = zhdr() + zhdr()
+            rc = all(m_[3].packed is not None for m_ in sa[:2])        # the consumers that read lists whose rows carry their cloud
+            # ... and, in that form, the list of the GroupAll level above them (one group per RoI: no clouds merged to fill tiles)
+            ga = bool(rc and hd and len(sa) == 3 and sa[2][0] is None and self._groupall_fused3_ok(sa[2][3], sa[1][3]))
+            # ... and the level-1 centres that are their own representatives as a row list: level 2's per-point layer over those rows only
+            cr = bool(rc and hd and has_entry(ext, "rows_gemm128_rows_wrapper") and sa[1][3].packed is not None
+                      and tuple(sa[1][3].packed[0].shape) == (128, 128))
+            extra = ()
+            if hd:
+                extra = hd + (False, rc) + ((zhdr()[0], True) if ga else (None, False)) + ((zhdr()[0], True) if cr else ())
+            fused_geo = ext.rcnn_roi_geometry_packs_wrapper(cur_xyz, pooled_cnt.view(-1), sa[0][0], sa[0][1], sa[0][2], sa[1][0], sa[1][1],
+                                                            sa[1][2], *extra)
         fused_p3 = next((x for x in (fused_geo or ())[8:] if hasattr(x, "rowinfo")), None)
         fused_crows = next((x for x in (fused_geo or ())[8:] if isinstance(x, tuple)), None)
         for k, (npoint, radius, ns, mlp, cin) in enumerate(self.rcnn_sa):
@@ -1124,14 +1090,8 @@ class FastPointRCNN:
             if k == 1 and fused_crows is not None:
                 lev["crows"] = fused_crows
             if npoint is not None and fused_geo is not None and k < 2:
-                new_xyz, idx, rep_out = fused_geo[3 * k:3 * k + 3]
-                if len(fused_geo) >= 8:
-                    lev["pack"] = fused_geo[6 + k]
-                elif k == 0:
-                    lev["pack"] = ext.ball_pack_wrapper(idx, cur_xyz, new_xyz, pooled_cnt.view(-1), None, rep_out, *zhdr())
-                else:
-                    lev["pack"] = ext.ball_pack_wrapper(idx, cur_xyz, new_xyz, None, rep, rep_out, *zhdr())
-                rep = rep_out
+                new_xyz, idx, rep = fused_geo[3 * k:3 * k + 3]
+                lev["pack"] = fused_geo[6 + k]
                 lev["new_xyz"], lev["idx"] = new_xyz, idx
                 cur_xyz = new_xyz
             elif npoint is not None:
@@ -1156,11 +1116,10 @@ class FastPointRCNN:
                     rep = ext.dup_rep_wrapper(sel, n, pooled_cnt.view(-1) if k == 0 else None, rep_in if k > 0 else None)
                 else:
                     rep = None
-                crep = rep if USE_CENTRE_SKIP else None
                 if dedup:
-                    lev["pack"] = ext.ball_pack_wrapper(idx, cur_xyz, new_xyz, pooled_cnt.view(-1), None, crep)   # copies of pooled points are dropped too
+                    lev["pack"] = ext.ball_pack_wrapper(idx, cur_xyz, new_xyz, pooled_cnt.view(-1), None, rep)   # copies of pooled points are dropped too
                 elif USE_PACKED and (mlp.packed is not None or mlp.wide is not None) and has_entry(ext, "ball_pack_wrapper"):
-                    lev["pack"] = (ext.ball_pack_wrapper(idx, cur_xyz, new_xyz, None, rep_in, crep) if (rep_in is not None and ns <= 64)
+                    lev["pack"] = (ext.ball_pack_wrapper(idx, cur_xyz, new_xyz, None, rep_in, rep) if (rep_in is not None and ns <= 64)
                                    else ext.ball_pack_wrapper(idx, cur_xyz, new_xyz))
                 lev["new_xyz"], lev["idx"] = new_xyz, idx
                 cur_xyz = new_xyz
@@ -1214,7 +1173,7 @@ class FastPointRCNN:
             arena = {"zero": zarena, "parts": parts}
         zarena.done()
         return {"B": B, "M": M, "P": P, "W": W, "rows": rows, "a": a, "rpn_part": rpn_part, "pooled": pooled, "pooled_cnt": pooled_cnt,
-                "point_mlp": point_mlp, "tiles": tiles, "rowlist": rowlist, "levels": levels, "arena": arena, "arena_shapes": shapes}
+                "point_mlp": point_mlp, "rowlist": rowlist, "levels": levels, "arena": arena, "arena_shapes": shapes}
 
     def _rcnn_features(self, rg):
         """The MLPs of the RCNN stage over the rows and row lists of `_rcnn_geometry`: xyz_up + merge_down + SA levels + heads."""
@@ -1232,7 +1191,7 @@ class FastPointRCNN:
             if rg.get("rowlist") is not None:
                 ext.rcnn_point_mlp_rows_wrapper(rows, 8, wu1, bu1, wu2, bu2, wm, bm, wf, b1, P_pre, rg["rowlist"])     # only P, only the distinct rows
             else:
-                ext.rcnn_point_mlp_wrapper(rows, 8, wu1, bu1, wu2, bu2, wm, bm, wf, b1, None, None, P_pre, rg["tiles"])   # only P is needed
+                ext.rcnn_point_mlp_wrapper(rows, 8, wu1, bu1, wu2, bu2, wm, bm, wf, b1, None, None, P_pre)   # only P is needed
             P_pre = P_pre.view(B * M, P, 128)
             l_feat = [None]
         else:

@@ -42,28 +42,11 @@ SWITCHES = {
     "PRCNN_NO_PACK": ("numerics", "unset", "net/fast_infer.py", "all grouped rows instead of the distinct rows (prcnn_ball_pack) -- and, without the packed row lists, the per-point layers through the GEMM library (needs PRCNN_ALLOW_LIB_GEMM=1 on a covered network): the all-rows leg of bench.py"),
     "PRCNN_ROWS_GEMM": ("numerics", "unset", "net/fast_infer.py", "128-wide row layers through rows_gemm128 (round-1 form)"),
     # ---- scheduling A/B (same results)
-    "PRCNN_EARLY_LEVELS": ("ab", "4", "net/fast_infer.py", "leading SA levels computed with the geometry"),
+    "PRCNN_EARLY_LEVELS": ("ab", "4", "net/fast_infer.py", "leading SA levels computed with the geometry (0: none)"),
     "PRCNN_EARLY_FP": ("ab", "2", "net/fast_infer.py", "coarsest FP modules computed with the geometry (round 5: 2; 3 until then)"),
-    "PRCNN_EARLY_G0": ("ab", "1", "net/fast_infer.py", "the finest FP module's coarse product computed with the geometry (round 4: +1.2 %)"),
-    "PRCNN_NO_XYZ_EARLY": ("ab", "unset", "net/fast_infer.py", "1: no SA level rides with the geometry"),
-    "PRCNN_NO_GROUP_SA": ("ab", "unset", "net/fast_infer.py", "1: early SA levels per batch instead of per geometry group"),
-    "PRCNN_FINAL_ON_FEATURE": ("ab", "0", "eval_rcnn.py", "1: final stage behind the RCNN features on the feature stream (round 4's default); 0: on the proposal stream"),
-    "PRCNN_NO_RCNN_SPLIT": ("ab", "unset", "eval_rcnn.py", "1: RCNN geometry on the feature stream"),
     # ---- engine formulations A/B (same results)
     "PRCNN_NO_POOL_DEDUP": ("ab", "unset", "net/fast_infer.py", "RCNN point MLP over all 512 pooled rows"),
-    "PRCNN_NO_CENTRE_DEDUP": ("ab", "unset", "net/fast_infer.py", "no representative map over sampled centres"),
-    "PRCNN_NO_CENTRE_SKIP": ("ab", "unset", "net/fast_infer.py", "copies of a centre keep rows of their own"),
-    "PRCNN_NO_POOL_GROUPS": ("ab", "unset", "net/fast_infer.py", "RoI pooling sweeps all points (no spatial groups)"),
-    "PRCNN_NO_POINT_MLP": ("ab", "unset", "net/fast_infer.py", "RCNN entrance as separate layers"),
-    "PRCNN_NO_ROI_GEOMETRY": ("ab", "unset", "net/fast_infer.py", "RCNN sampling / ball queries as six launches"),
-    "PRCNN_NO_CENTRE_ROWS": ("ab", "unset", "net/fast_infer.py", "the RCNN second level's per-point layer over all 128 level-1 centres of every RoI instead of the listed representatives"),
-    "PRCNN_NO_POOLED_ROWS": ("ab", "unset", "net/fast_infer.py", "the RCNN entrance over whole 64-row tiles per RoI (prcnn_pooled_tiles) instead of the list of distinct pooled rows"),
-    "PRCNN_NO_ROI_PACKS": ("ab", "unset", "net/fast_infer.py", "the RoI clouds' two row lists by prcnn_ball_pack_ex launches instead of inside prcnn_rcnn_roi_geometry_packs"),
     "PRCNN_NO_RPN_TAIL": ("ab", "unset", "net/fast_infer.py", "finest FP module and RPN heads layer by layer (the bits of the fused tail under PRCNN_NO_FP_LINEAR=1: the layer-by-layer form keeps the reference's association)"),
-    "PRCNN_TAIL_DECODE": ("ab", "1", "net/fast_infer.py", "0: the fused RPN tail stores the (B, N, 76) regression rows and the proposal layer decodes them (rpn_decode_kernel) instead of decoding inside the tail kernel (round 5)"),
-    "PRCNN_NO_SA2_BATCH": ("ab", "unset", "net/fast_infer.py", "set: the two 128-wide scales of an MSG level (RPN SA2) as two launches per stage instead of one (prcnn_sa_packed_mlp_batch, round 5)"),
-    "PRCNN_NO_WIDE_FUSED3": ("ab", "unset", "net/fast_infer.py", "1: the GroupAll level's layer 1 as a per-point launch in front of csrc/sa_wide.hip instead of inside csrc/sa_wide3.hip"),
-    # ---- kernel forms A/B (C library; same results)
     # ---- tuning
     "PRCNN_MFMA_GRID": ("tuning", "512", "csrc/capi.hip", "workgroups of a persistent MFMA launch"),
     "PRCNN_SA_GRID": ("tuning", "512", "csrc/sa_packed.hip", "workgroups of the packed SA kernels"),
@@ -101,7 +84,7 @@ def check_environment():
 
 def table():
     # the last column names the test that RUNS the switch in its non-default form
-    held = {"ab": "`tests/test_gpu_switches.py::test_every_ab_switch_gives_the_same_detections` (bit for bit)",
+    held = {"ab": "`tests/test_gpu_switches.py::test_each_ab_switch_gives_the_same_detections` (bit for bit)",
             "numerics": "`tests/test_gpu_switches.py::test_numerics_switches_stay_inside_the_box_tolerance` (boxes within 1e-4)"}
     special = {"PRCNN_ALLOW_LIB_GEMM": "set together with the GEMM-library switches in the numerics test",
                "PRCNN_FPS2_CAPACITY": "`tests/test_gpu_ops.py::test_fps_two_workgroups_respects_the_co_resident_capacity`",

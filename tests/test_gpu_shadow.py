@@ -442,7 +442,7 @@ def spread_heads(model):
 
 
 @pytest.mark.parametrize("wide_fused,scene_kind", [(True, "uniform"), (False, "uniform"), (True, "lidar")])
-def test_batch8_step_every_kernel_call_equals_the_oracle(wide_fused, scene_kind, monkeypatch):
+def test_batch8_step_kernel_calls_equal_the_oracle(wide_fused, scene_kind, monkeypatch):
     """wide_fused = False: the RCNN's GroupAll level layer by layer (gather + affine, layer, layer + pool) like the RPN's wide levels,
     instead of the one-kernel form of csrc/sa_wide.hip.  scene_kind = "lidar": LiDAR-shaped scenes (dense near the sensor)."""
     C, E, F, S = pkg("config"), pkg("eval_rcnn"), pkg("net.fast_infer"), pkg("synth")
@@ -479,25 +479,23 @@ def test_batch8_step_every_kernel_call_equals_the_oracle(wide_fused, scene_kind,
         assert torch.isfinite(det[k].float()).all(), k
     assert (det["num"] > 0).all()
     # coverage: every kernel family of the step was exercised at the batch-8 shapes
-    fg = F.USE_ROI_GEOMETRY          # the RoI clouds' FPS / ball query / representative maps of both sampled levels in one launch
-    fp = fg and F.USE_ROI_PACKS      # ... and their two row lists out of that launch
-    want_calls = {"furthest_point_sampling_wrapper": 0, "fps_new_xyz_wrapper": 4 if fg else 6, "dup_rep_wrapper": 0 if fg else 2, "point_aux_wrapper": 1,
-                  "ball_query_full_wrapper": 8, "ball_query_wrapper": 0 if fg else 1, "ball_query_limit_wrapper": 0 if fg else 1, "rcnn_roi_geometry_wrapper": 1 if (fg and not fp) else 0, "rcnn_roi_geometry_packs_wrapper": 1 if fp else 0, "three_nn_wrapper": 0, "three_nn_weights_wrapper": 4, "ball_pack_wrapper": (8 if log["group_all_list_fused"] else 9) if fp else 11,
-                  "sa_xyz_mlp_packed_wrapper": 2, "sa_packed_mlp_wrapper": 2 if (F.USE_SCALE_BATCH and F.USE_SA2_BATCH) else 4, "sa_packed_mlp_batch_wrapper": 1 if (F.USE_SCALE_BATCH and F.USE_SA2_BATCH) else 0,
+    # the RoI clouds' FPS / ball query / representative maps of both sampled levels and their two row lists in one launch
+    want_calls = {"furthest_point_sampling_wrapper": 0, "fps_new_xyz_wrapper": 4, "dup_rep_wrapper": 0, "point_aux_wrapper": 1,
+                  "ball_query_full_wrapper": 8, "ball_query_wrapper": 0, "ball_query_limit_wrapper": 0, "rcnn_roi_geometry_wrapper": 0, "rcnn_roi_geometry_packs_wrapper": 1, "three_nn_wrapper": 0, "three_nn_weights_wrapper": 4, "ball_pack_wrapper": 8 if log["group_all_list_fused"] else 9,
+                  "sa_xyz_mlp_packed_wrapper": 2, "sa_packed_mlp_wrapper": 2 if F.USE_SCALE_BATCH else 4, "sa_packed_mlp_batch_wrapper": 1 if F.USE_SCALE_BATCH else 0,
                   "three_interpolate_cat_pm_wrapper": 0 if F.USE_FP_LINEAR else 3, "packed_layer_interp_wrapper": 3 if F.USE_FP_LINEAR else 0,
-                  "rpn_tail_wrapper": 0 if F.USE_FP_LINEAR else 1, "rpn_tail_lin_wrapper": 1 if F.USE_FP_LINEAR and not F.USE_TAIL_DECODE else 0,
-                  "rpn_tail_lin_boxes_wrapper": 1 if F.USE_FP_LINEAR and F.USE_TAIL_DECODE else 0, "rcnn_point_mlp_wrapper": 0 if F.USE_POOLED_ROWS else 1, "rcnn_point_mlp_rows_wrapper": 1 if F.USE_POOLED_ROWS else 0, "forward_canonical": 1,
-                  "rows_gemm128_rows_wrapper": 1 if (fp and F.USE_CENTRE_ROWS) else 0}
-    want_calls.update({"packed_layer_segmax_batch_wrapper": 2, "packed_gather_affine_batch_wrapper": 2, "packed_layer_batch_wrapper": 6 if (F.USE_SCALE_BATCH and F.USE_SA2_BATCH and not F.USE_SA_NARROW) else 5})   # RPN SA3, SA4; the two branches of the RCNN head (round 4); RPN SA2's per-point parts (round 5; one plain product for both scales with the narrow kernel)
-    if wide_fused:       # the RCNN's GroupAll level (every row distinct: 800 units of work) in one kernel
-        f3 = 1 if F.USE_WIDE_FUSED3 else 0   # ... and its per-point layer inside that kernel (csrc/sa_wide3.hip)
-        want_calls.update({"sa_wide_fused3_wrapper": f3, "sa_wide_fused_wrapper": 1 - f3, "packed_layer_segmax_wrapper": 0, "packed_gather_affine_wrapper": 0})
+                  "rpn_tail_wrapper": 0 if F.USE_FP_LINEAR else 1, "rpn_tail_lin_wrapper": 0,
+                  "rpn_tail_lin_boxes_wrapper": 1 if F.USE_FP_LINEAR else 0, "rcnn_point_mlp_wrapper": 0, "rcnn_point_mlp_rows_wrapper": 1, "forward_canonical": 1,
+                  "rows_gemm128_rows_wrapper": 1}
+    want_calls.update({"packed_layer_segmax_batch_wrapper": 2, "packed_gather_affine_batch_wrapper": 2, "packed_layer_batch_wrapper": 6 if (F.USE_SCALE_BATCH and not F.USE_SA_NARROW) else 5})   # RPN SA3, SA4; the two branches of the RCNN head (round 4); RPN SA2's per-point parts (round 5; one plain product for both scales with the narrow kernel)
+    if wide_fused:       # the RCNN's GroupAll level (every row distinct: 800 units of work) in one kernel, its per-point layer inside (csrc/sa_wide3.hip)
+        want_calls.update({"sa_wide_fused3_wrapper": 1, "sa_wide_fused_wrapper": 0, "packed_layer_segmax_wrapper": 0, "packed_gather_affine_wrapper": 0})
     else:
         want_calls.update({"sa_wide_fused3_wrapper": 0, "sa_wide_fused_wrapper": 0, "packed_layer_segmax_wrapper": 1, "packed_gather_affine_wrapper": 1})
     for name, n in want_calls.items():
         assert log[name] == n, (name, log[name], n)
     assert log["packed_layer_wrapper"] >= 3 and log["rows_dot_wrapper"] == 1
-    assert log["roi_idx_not_written"] == (1 if fp else 0) and log["row_cloud_lists"] == ((3 if wide_fused and F.USE_WIDE_FUSED3 else 2) if fp else 0)
+    assert log["roi_idx_not_written"] == 1 and log["row_cloud_lists"] == (3 if wide_fused else 2)
     assert log["rep_rows_dropped"] > 1000            # the deeper RCNN levels really dropped rows of copied centres
     assert log["centres_skipped"] > 1000             # ... and skipped the centres that copy an earlier one
     print("shadowed calls:", {k: v for k, v in log.items() if not k.startswith("elements:")})

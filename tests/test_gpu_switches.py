@@ -46,9 +46,9 @@ def run_child(path, env_extra):
 UNDER = {"PRCNN_NO_RPN_TAIL": {"PRCNN_NO_FP_LINEAR": "1"}}
 
 
-def test_every_ab_switch_gives_the_same_detections(tmp_path):
+def test_each_ab_switch_gives_the_same_detections(tmp_path):
     alts = alternatives()
-    assert len(alts) == 20                                        # round 6: 43 -> 20 A/B switches
+    assert len(alts) == 4                                         # round 6: 43 -> 20 A/B switches; then 20 -> 4
     wants = {}
     for tag, extra in [("default", {})] + [(n, e) for n, e in UNDER.items()]:
         base = str(tmp_path / ("base_%s.npz" % tag))
