@@ -126,6 +126,8 @@ SIGNATURES = {
     "prcnn_stat_norm_choose": [_P, _P],
     "prcnn_stat_norm_write": [_P, _P],
     "prcnn_stat_norm_occlusion": [_I, _I, _I, _I, _P, _P, _P, _P],
+    "prcnn_rpn_labels_workspace": [_I, _I, _P],
+    "prcnn_rpn_labels": [_I, _I, _I, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P],
 }
 
 _lib = None

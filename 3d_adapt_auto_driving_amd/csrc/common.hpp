@@ -117,6 +117,13 @@ __device__ __forceinline__ void three_nn_weights(float d0, float d1, float d2, f
     w[0] = __fdiv_rn(r0, s); w[1] = __fdiv_rn(r1, s); w[2] = __fdiv_rn(r2, s);
 }
 
+// The RPN's foreground decision of one point, sigmoid(raw) > thresh with one rounding per operation (point_rcnn.py:44-45): the
+// joint path's seg_result (proposal.hip point_aux_kernel) and the RPN evaluation's counters (rpn_labels.hip) share it.
+__device__ __forceinline__ bool rpn_seg_fg(float raw, float thresh)
+{
+    return __fdiv_rn(1.0f, __fadd_rn(1.0f, expf(-raw))) > thresh;
+}
+
 // f32 trig contract: correctly rounded from the f64 value (see oracle/prcnn_oracle.h).
 __device__ __forceinline__ float cos_f32(float x) { return (float)cos((double)x); }
 __device__ __forceinline__ float sin_f32(float x) { return (float)sin((double)x); }

@@ -560,8 +560,7 @@ __global__ __launch_bounds__(256) void point_aux_kernel(long rows, float thresh,
 {
     const long r = (long)blockIdx.x * 256 + threadIdx.x;
     if (r >= rows) return;
-    const float sg = __fdiv_rn(1.0f, __fadd_rn(1.0f, expf(-scores[r])));
-    seg[r] = sg > thresh ? 1.0f : 0.0f;
+    seg[r] = rpn_seg_fg(scores[r], thresh) ? 1.0f : 0.0f;
     const float x = xyz[3 * r], y = xyz[3 * r + 1], z = xyz[3 * r + 2];
     const float d = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(x, x), __fmul_rn(y, y)), __fmul_rn(z, z)));
     depth[r] = d;

@@ -599,8 +599,29 @@ class EngineRunner(ModuleRunner):
         return infer_batch(self.model, self.cfg, cur, engine=self.engine)
 
 
+class RpnRunner(ModuleRunner):
+    """--eval_mode rpn (cfg.RCNN.ENABLED = False): the engine's RPN stage and proposal layer, one batch after the other on the caller's
+    stream, with the same one-batch-late protocol.  A batch's dict holds rois / roi_scores_raw (B, M, 7) / (B, M), the raw scores
+    (B, N), the backbone's xyz (B, N, 3) and its point-major features (B, N, C)."""
+
+    def __init__(self, model, cfg, device, depth=None):
+        super().__init__(model, cfg, device, depth)
+        if cfg.RCNN.ENABLED:
+            raise ValueError("RpnRunner: cfg.RCNN.ENABLED must be False (--eval_mode rpn)")
+        self.engine = FastPointRCNN(model, cfg)
+
+    def _infer(self, cur):
+        st = self.engine.rpn_stage(cur)
+        rois, roi_scores = self.engine.propose(st)
+        return {"rois": rois, "roi_scores_raw": roi_scores, "rpn_scores_raw": st["rpn_scores_raw"],
+                "backbone_xyz": st["backbone_xyz"], "rpn_features": st["rpn_features"]}
+
+
 def make_runner(model, cfg, device, depth=None):
-    """The runner of the product path: hipGraph replay unless PRCNN_GRAPHS=0 (same streams, same kernels, same results)."""
+    """The runner of the product path: hipGraph replay unless PRCNN_GRAPHS=0 (same streams, same kernels, same results).
+    --eval_mode rpn (RCNN disabled): RpnRunner."""
+    if not cfg.RCNN.ENABLED:
+        return RpnRunner(model, cfg, device, depth)
     if not engine_covers(cfg):
         return ModuleRunner(model, cfg, device, depth)
     if cfg.RPN.USE_INTENSITY:
@@ -1670,6 +1691,105 @@ def steady_state_rate(stats, batch_size):
     return (len(t) - 1) * batch_size / max(t[-1] - t[0], 1e-9)
 
 
+def _write_rpn_batch(ids, calibs, shapes, rois, scores, seg, feats, output_dir, cls_name):
+    """one writer job of --eval_mode rpn (eval_rcnn.py:212-229): detections/data/%06d.txt (every RoI, save_kitti_format),
+    seg_result/%06d.npy and, with ``feats``, the features/ files of save_rpn_features (:104-117)"""
+    det_dir, seg_dir = os.path.join(output_dir, "detections", "data"), os.path.join(output_dir, "seg_result")
+    for k, sid in enumerate(ids):
+        save_kitti_format(sid, calibs[k], rois[k], det_dir, scores[k], shapes[k], cls_name)
+        np.save(os.path.join(seg_dir, "%06d.npy" % sid), seg[k].astype(np.float16))
+        if feats is not None:
+            fdir = os.path.join(output_dir, "features")
+            for suffix, arr in feats[k].items():
+                np.save(os.path.join(fdir, "%06d%s.npy" % (sid, suffix)), arr)
+    return len(ids)
+
+
+@torch.no_grad()
+def eval_scenes_rpn(model, cfg, device, source, scene_ids, batch_size=8, output_dir=None, test=False, save_feature=False,
+                    stats=None, labels=None):
+    """--eval_mode rpn over ``scene_ids`` (eval_one_epoch_rpn, eval_rcnn.py:120-260).  Per batch: the RPN stage and proposal layer
+    (RpnRunner); unless ``test``, the sources' EVAL-mode gt_boxes3d are packed and the label kernel (csrc/rpn_labels.hip) labels the
+    backbone's xyz and counts (correct, fg, pred) per scene; ``stats`` (rpn_eval.RpnStats) takes the counters and the recall of the
+    RoIs.  ``output_dir``: the reference's files (detections/data, seg_result, features/ with ``save_feature``), written by writer
+    processes.  ``labels``: a list that receives each batch's (ids, cls (B, N) int32 host array).  Returns per scene the host
+    (rois, roi_scores_raw) in scene order."""
+    from . import rpn_eval
+    import multiprocessing
+    from concurrent.futures import ProcessPoolExecutor
+    runner = make_runner(model, cfg, device)
+    thresh = float(cfg.RPN.SCORE_THRESH)
+    writers, jobs, out = None, [], []
+    if output_dir:
+        os.makedirs(os.path.join(output_dir, "detections", "data"), exist_ok=True)
+        os.makedirs(os.path.join(output_dir, "seg_result"), exist_ok=True)
+        if save_feature:
+            os.makedirs(os.path.join(output_dir, "features"), exist_ok=True)
+        writers = ProcessPoolExecutor(max_workers=max(1, min(4, host_budget()["writers"])), initializer=_limit_worker_threads,
+                                      mp_context=multiprocessing.get_context("forkserver"))
+
+    def finish(det, ids, meta, host_pts, intensity):
+        B = len(ids)
+        cls = None
+        if not test:
+            gt_list = [source.gt_boxes3d(i) for i in ids]
+            gt, counts, trig = rpn_eval.pack_gt(gt_list)
+            counters = torch.zeros((B, 3), dtype=torch.int32, device=device)
+            cls, _ = rpn_eval.rpn_labels(det["backbone_xyz"], gt, counts, device=device, want_reg=False, trig=trig,
+                                         scores_raw=det["rpn_scores_raw"], thresh=thresh, stats=counters)
+            if stats is not None:
+                stats.update_seg(counters)
+                stats.update_recall(det["rois"], gt_list)
+        rois, scores = det["rois"].cpu().numpy(), det["roi_scores_raw"].cpu().numpy()
+        out.extend(zip(rois, scores))
+        cls_h = cls.cpu().numpy() if cls is not None else None
+        if labels is not None and cls_h is not None:
+            labels.append((list(ids), cls_h))
+        if writers is not None:
+            raw = det["rpn_scores_raw"].cpu().numpy()
+            pred = rpn_eval.seg_decision(raw, thresh)
+            seg, feats = [], [] if save_feature else None
+            xyz = det["backbone_xyz"].cpu().numpy()
+            fts = det["rpn_features"].cpu().numpy() if save_feature else None
+            for k in range(B):
+                cols = [host_pts[k][:, :3], pred[k].reshape(-1, 1).astype(np.float32)]
+                if cls_h is not None:
+                    cols.insert(1, cls_h[k].reshape(-1, 1).astype(np.float32))
+                seg.append(np.concatenate(cols, axis=1))
+                if save_feature:
+                    f = {"": fts[k], "_xyz": xyz[k], "_seg": pred[k].astype(np.float32), "_rawscore": raw[k]}
+                    f["_intensity"] = intensity[k]             # pts_features[:, 0] = reflectance - 0.5, (N,) f32
+                    feats.append(f)
+            jobs.append(writers.submit(_write_rpn_batch, list(ids), [m[0] for m in meta], [m[1] for m in meta], list(rois),
+                                       list(scores), seg, feats, output_dir, cfg.CLASSES))
+
+    pending = None
+    try:
+        for s in range(0, len(scene_ids), batch_size):
+            ids = scene_ids[s:s + batch_size]
+            if save_feature:
+                loaded = [source.load_with_features(i) for i in ids]
+                intensity = [l[1] for l in loaded]
+                loaded = [(l[0], l[2], l[3]) for l in loaded]
+            else:
+                loaded, intensity = [source.load(i) for i in ids], None
+            host = np.stack([l[0] for l in loaded], 0)
+            pts = torch.from_numpy(host).pin_memory().to(device, non_blocking=True)
+            det = runner.submit(pts)
+            if det is not None:
+                finish(det, *pending)
+            pending = (ids, [(l[1], l[2]) for l in loaded], host, intensity)
+        det = runner.flush()
+        if det is not None:
+            finish(det, *pending)
+        for j in jobs:
+            j.result()
+    finally:
+        if writers is not None:
+            writers.shutdown(wait=True, cancel_futures=True)
+    return out
+
+
 def _write_batch(ids, calibs, shapes, boxes, scores, output_dir, cls_name):
     """one writer job: the KITTI result files of one batch (runs in a writer process)"""
     return sum(save_kitti_format(sid, c, b, output_dir, s, sh, cls_name) for sid, c, sh, b, s in zip(ids, calibs, shapes, boxes, scores))
@@ -1744,6 +1864,9 @@ def main(argv=None):
     ap.add_argument("--output_dir", type=str, default=None)
     ap.add_argument("--eval_ap", action="store_true", help="rank 0: KITTI AP of the gathered detections vs the labels")
     ap.add_argument("--recall", action="store_true", help="RoI / refined-box recall vs the ground truth (the reference's statistics without --test)")
+    ap.add_argument("--save_result", action="store_true", help="--eval_mode rpn: write detections/data and seg_result")
+    ap.add_argument("--save_rpn_feature", action="store_true", help="--eval_mode rpn: also write the backbone features (features/)")
+    ap.add_argument("--test", action="store_true", help="--eval_mode rpn: no ground truth (no labels, no statistics)")
     ap.add_argument("--set", dest="set_cfgs", default=None, nargs=argparse.REMAINDER)
     args = ap.parse_args(argv)
 
@@ -1771,6 +1894,8 @@ def main(argv=None):
     else:
         source = kitti_io.SyntheticSource(cfg, args.scenes, raw_points=args.raw_points)
     my_ids = [source.ids[i] for i in shard_scene_ids(len(source.ids), rank, world)]
+    if args.eval_mode == "rpn":
+        return _main_rpn(args, model, cfg, device, source, my_ids, rank)
     t0 = time.perf_counter()
     recall = RecallStats(device) if args.recall else None
     stats = {}
@@ -1792,6 +1917,26 @@ def main(argv=None):
             if args.output_dir:
                 with open(os.path.join(args.output_dir, "final_result", "ap.txt"), "w") as f:
                     f.write(text)
+
+
+def _main_rpn(args, model, cfg, device, source, my_ids, rank):
+    """--eval_mode rpn: eval_scenes_rpn on this rank's scenes and the reference's closing lines.  Returns the statistics dict
+    (None with --test).  With more than one rank each rank batches its own shard, so the recall quirk's padding rows (rpn_eval)
+    can differ from a single-process run."""
+    from . import rpn_eval
+    save = args.save_result or args.save_rpn_feature
+    result_dir = args.output_dir or "."
+    stats = None if args.test else rpn_eval.RpnStats(device)
+    t0 = time.perf_counter()
+    eval_scenes_rpn(model, cfg, device, source, my_ids, args.batch_size, result_dir if save else None, test=args.test,
+                    save_feature=args.save_rpn_feature, stats=stats)
+    elapsed = time.perf_counter() - t0
+    print("rank %d: ---- RPN EVALUATION ---- %d scenes (%.1f scenes/s)" % (rank, len(my_ids), len(my_ids) / max(elapsed, 1e-9)))
+    if stats is None:
+        return None
+    for line in stats.summary_lines(result_dir=result_dir):
+        print(line)
+    return stats.result()
 
 
 if __name__ == "__main__":

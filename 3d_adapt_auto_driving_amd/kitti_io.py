@@ -158,6 +158,19 @@ class KittiSource:
                                   rng=rng if rng is not None else np.random.RandomState(self.seed + idx))
         return np.ascontiguousarray(pts, dtype=np.float32), calib, shape
 
+    def load_with_features(self, idx, rng=None):
+        """load() plus the sampled reflectance - 0.5 as an (N,) f32 array whatever cfg.RPN.USE_INTENSITY is: the reference's
+        ``pts_features[:, 0]`` (kitti_rcnn_dataset.py:325-330), which save_rpn_features writes.  Same rows as load(): the sampler
+        decides on depth alone, so the extra column rides along."""
+        cfg = self.cfg
+        lidar, pts_rect, keep, calib, shape = self.rect_and_flags(idx)
+        rows = np.concatenate([pts_rect[keep][:, 0:3], lidar[keep][:, 3:4] - np.float32(0.5)], axis=1)
+        rows = synth.subsample_rpn(rows, cfg.RPN.NUM_POINTS, self.npoints_faraway,
+                                   rng=rng if rng is not None else np.random.RandomState(self.seed + idx))
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        pts = rows if cfg.RPN.USE_INTENSITY else np.ascontiguousarray(rows[:, 0:3])
+        return pts, np.ascontiguousarray(rows[:, 3]), calib, shape
+
 
 class DeviceInputStage:
     """The same stage on the device (csrc/input_stage.hip): raw points in, ``pts_input`` (B, npoints, 3) out.
@@ -361,6 +374,14 @@ class SyntheticSource:
         else:
             pts = synth.scene(idx, n)
         if self.cfg.RPN.USE_INTENSITY:                      # a synthetic reflectance column, already shifted to [-0.5, 0.5)
-            refl = np.random.default_rng(77000 + idx).random((len(pts), 1)).astype(np.float32) - np.float32(0.5)
-            pts = np.concatenate([pts, refl], axis=1)
+            pts = np.concatenate([pts, self._reflectance(idx, len(pts))[:, None]], axis=1)
         return pts, self.calib, self.calib.image_shape
+
+    @staticmethod
+    def _reflectance(idx, n):
+        return np.random.default_rng(77000 + idx).random(n).astype(np.float32) - np.float32(0.5)
+
+    def load_with_features(self, idx):
+        """load() plus the scene's reflectance - 0.5 as (N,) f32 whatever cfg.RPN.USE_INTENSITY is (KittiSource.load_with_features)"""
+        pts, calib, shape = self.load(idx)
+        return pts, (pts[:, 3].copy() if pts.shape[1] > 3 else self._reflectance(idx, len(pts))), calib, shape

@@ -900,8 +900,7 @@ class FastPointRCNN:
                 feats = feats[:, :, :self.fp[0].n_out].contiguous()
             rpn_boxes = None
         out = {"rpn_cls": rpn_cls, "rpn_reg": rpn_reg, "rpn_boxes": rpn_boxes, "backbone_xyz": xyz, "rpn_features": feats, "groups": geo.get("groups")}
-        if cfg.RCNN.ENABLED:
-            out["rpn_scores_raw"] = rpn_cls[:, :, 0].contiguous()
+        out["rpn_scores_raw"] = rpn_cls[:, :, 0].contiguous()     # the proposal layer's and the segmentation decision's input
         return out
 
     @torch.no_grad()
@@ -961,10 +960,10 @@ class FastPointRCNN:
         returned point-major under 'rpn_features' (B,N,C).  ``want_reg`` = False (eval_rcnn.infer_batch: only the detections are
         wanted): rpn_reg may be None -- the boxes were decoded inside the fused tail kernel (rpn_stage)."""
         out = self.rpn_stage(pts_input, geo, want_reg=want_reg)
-        if not self.cfg.RCNN.ENABLED:
-            return out
         rois, roi_scores_raw = self.propose(out)
         out.update({"rois": rois, "roi_scores_raw": roi_scores_raw})
+        if not self.cfg.RCNN.ENABLED:                        # --eval_mode rpn: the RPN's outputs and its proposals
+            return out
         out.update(self.rcnn_stage(out, rois))
         return out
 

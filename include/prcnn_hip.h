@@ -649,6 +649,14 @@ int prcnn_stat_norm_write(const prcnn_sn_batch *batch, void *stream);
 int prcnn_stat_norm_occlusion(int n_scenes, int h, int w, int max_objects, const int *obj_off, const int *rects, int *counts,
                               void *stream);
 
+/* RPN labels (kitti_rcnn_dataset.py:385-414 generate_rpn_training_labels) for a batch of ragged scenes (csrc/rpn_labels.hip).
+ * pts (b, n, 3) f32 rect frame; gt (b, g, 7) f32 [x, y_bottom, z, h, w, l, ry] with counts (b) i32 valid rows per scene; trig (b, g, 2)
+ * f32 = numpy's f32 (cos ry, sin ry); scores (b, n) raw RPN scores or NULL; cls (b, n) i32 -1 / 0 / 1; reg (b, n, 7) f32 or NULL;
+ * stats (b, 3) i32 (zeroed by the caller) += (correct, fg, pred) or NULL; work: prcnn_rpn_labels_workspace bytes (may be NULL if g = 0). */
+int prcnn_rpn_labels_workspace(int b, int g, long long *bytes);
+int prcnn_rpn_labels(int b, int n, int g, const float *pts, const float *gt, const int *counts, const float *trig, const float *scores,
+                     float thresh, int *cls, float *reg, int *stats, double *work, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
