@@ -119,6 +119,8 @@ SIGNATURES = {
     "prcnn_valid_flags": [_I, _I, _I, _I, _I, _P, _P, _P, _P, _F, _P, _P, _P],
     "prcnn_rotate_iou_eval": [_I, _I, _P, _P, _P, _I, _P],
     "prcnn_rotate_iou_eval_segmented": [_I, _L, _P, _P, _P, _P, _P, _P, _I, _P],
+    "prcnn_bev_best_match": [_I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P],
+    "prcnn_eval_align": [_I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P],
     "prcnn_kitti_image_stats": [_I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _D, _D, _I, _I, _P, _P, _P, _P],
     "prcnn_kitti_collect_scores": [_I, _P, _P, _P, _P, _P, _P, _P, _I, _D, _P, _P],
     "prcnn_kitti_accumulate_pr": [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _D, _P, _I, _I, _P],

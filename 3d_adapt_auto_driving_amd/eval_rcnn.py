@@ -1067,13 +1067,13 @@ def detections_to_annos(table, counts, source, cls_name="Car"):
     return ids, annos
 
 
-def evaluate_detections(table, counts, source, current_class=0, dataset="kitti", device_id=0):
+def evaluate_detections(table, counts, source, current_class=0, dataset="kitti", device_id=0, metric="new"):
     """Rank-0 tail of the sharded evaluation: AP of the gathered detections against the source's labels
     (tools/eval_rcnn.py:706-713 -> evaluate/evaluate.py).  Returns (result text, dict)."""
     from . import kitti_eval
     ids, dt_annos = detections_to_annos(table, counts, source)
     gt_annos = [kitti_eval.annos_from_lines(source.label_lines(i)) for i in ids]
-    return kitti_eval.get_official_eval_result(gt_annos, dt_annos, current_class, dataset, device_id=device_id)
+    return kitti_eval.get_official_eval_result(gt_annos, dt_annos, current_class, dataset, device_id=device_id, metric=metric)
 
 
 class RecallStats:
@@ -1863,6 +1863,10 @@ def main(argv=None):
     ap.add_argument("--split", type=str, default=None, help="ImageSets split (default cfg.TEST.SPLIT)")
     ap.add_argument("--output_dir", type=str, default=None)
     ap.add_argument("--eval_ap", action="store_true", help="rank 0: KITTI AP of the gathered detections vs the labels")
+    ap.add_argument("--ap_metric", type=str, default="new", choices=["new", "old"],
+                    help="--eval_ap difficulty rule: new = distance bands, old = KITTI's bbox-height levels")
+    ap.add_argument("--ap_dataset", type=str, default="kitti", choices=["kitti", "argo", "nusc", "lyft", "waymo"],
+                    help="--ap_metric old: whose focal length scales the 40 / 25 / 25 px height caps")
     ap.add_argument("--recall", action="store_true", help="RoI / refined-box recall vs the ground truth (the reference's statistics without --test)")
     ap.add_argument("--save_result", action="store_true", help="--eval_mode rpn: write detections/data and seg_result")
     ap.add_argument("--save_rpn_feature", action="store_true", help="--eval_mode rpn: also write the backbone features (features/)")
@@ -1912,7 +1916,8 @@ def main(argv=None):
               (table.shape[0], int(counts.sum()), len(my_ids) / max(elapsed, 1e-9),
                " and the result writer" if out else "", steady_state_rate(stats, args.batch_size)))
         if args.eval_ap:
-            text, _ = evaluate_detections(table, counts, source, device_id=device.index or 0)
+            text, _ = evaluate_detections(table, counts, source, dataset=args.ap_dataset, device_id=device.index or 0,
+                                          metric=args.ap_metric)
             print(text)
             if args.output_dir:
                 with open(os.path.join(args.output_dir, "final_result", "ap.txt"), "w") as f:

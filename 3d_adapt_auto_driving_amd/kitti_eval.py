@@ -1,8 +1,9 @@
 """Offline KITTI AP evaluator around the rotated-IoU HIP kernel (counterpart of evaluate/eval2.py:8-690,
-evaluate/kitti_common.py:307-360 and the ``evaluate()`` driver evaluate/evaluate.py:88-135 in its
-plain form: no re-scaling / grounding analysis switches).
+evaluate/eval_old.py, evaluate/kitti_common.py:293-360 and the ``evaluate()`` driver evaluate/evaluate.py:84-296 with its output
+transformations: grounding, re-scaling, size / front alignment against the best-overlapping ground truth, statistical mapping of
+the ground truth, per-box overlap columns, and the command line).
 
-Same protocol as the reference fork: 41 recall sample points, 11-point mAP (every 4th), six DISTANCE
+Protocol of the reference fork (``metric="new"``): 41 recall sample points, 11-point mAP (every 4th), six DISTANCE
 based "difficulties" instead of KITTI's easy/moderate/hard (eval2.py:48-52):
 
     level        0        1        2        3        4        5
@@ -15,11 +16,23 @@ rotated-IoU matrix per part on the GPU (cross-image pairs are discarded) and run
 numba-jitted Python.  Here every image is one segment of a single block-diagonal launch
 (``prcnn_rotate_iou_eval_segmented``), and the matching / PR accumulation are host functions of the same
 library (csrc/kitti_stats.hip) fed with the whole split at once.
+
+``metric="old"`` is evaluate/eval_old.py: KITTI's three difficulties with the image-height rule, the 40 / 25 / 25 px caps scaled by the
+dataset's focal length (FOCAL); no distance band.
+
+The transformations need, beyond host bookkeeping, one thing: every detection's best-overlapping ground-truth box of its image and
+that BEV overlap, and the same for every ground-truth box.  ``best_match(device="cuda")`` gets both from one fused launch
+(``prcnn_bev_best_match``, csrc/eval_match.hip) that never writes the pair matrix; ``device="cpu"`` is numpy's max / argmax over
+``calculate_iou(..., 1)``.  align_size / align_front then run on the device too (``prcnn_eval_align``).
+
+Command line:  python -m 3d_adapt_auto_driving_amd.kitti_eval --result_path ... --dataset_path ... [--metric old] [--align_size] ...
 """
 import ctypes
 import io
+import json
 import os
 import pathlib
+import pickle
 import re
 
 import numpy as np
@@ -32,6 +45,21 @@ DIST_BOUNDARY = np.array([[0, 0, 0, 0, 30, 50], [30, 70, 70, 30, 50, 70]], dtype
 MAX_OCCLUSION = [0, 1, 2, 2, 2, 2]
 MAX_TRUNCATION = [0.15, 0.3, 0.5, 0.5, 0.5, 0.5]
 N_SAMPLE_PTS = 41
+# metric="old" (eval_old.py:28-39): bbox-height caps of KITTI's easy / moderate / hard, scaled from KITTI's focal length to the dataset's
+FOCAL = {"kitti": 707.05, "argo": 1870.57, "nusc": 1266.42, "lyft": 811.16, "waymo": 2069.82}
+OLD_MAX_OCCLUSION = [0, 1, 2]
+OLD_MAX_TRUNCATION = [0.15, 0.3, 0.5]
+ALIGN_MIN_OVERLAP = 0.2          # evaluate.py:196,209: a detection is aligned when its best BEV overlap exceeds this
+
+
+def min_height(dataset):
+    return (np.array([40, 25, 25]) / FOCAL["kitti"] * FOCAL[dataset]).tolist()
+
+
+def _difficulties(metric):
+    if metric not in ("new", "old"):
+        raise ValueError("metric %r is neither 'new' (distance) nor 'old' (bbox height)" % (metric,))
+    return [0, 1, 2, 3, 4, 5] if metric == "new" else [0, 1, 2]
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -183,29 +211,41 @@ def calculate_iou(dt_annos, gt_annos, metric, device_id=0):
 # ---------------------------------------------------------------------------------------------------
 # per-image bookkeeping
 # ---------------------------------------------------------------------------------------------------
-def clean_data(gt_anno, dt_anno, current_class, dataset, difficulty):
+def clean_data(gt_anno, dt_anno, current_class, dataset, difficulty, metric="new"):
     """-> num_valid_gt, ignored_gt (n_gt) i64: 0 care / 1 ignore / -1 other class, ignored_dt (n_dt) i64, dc_bboxes (k, 4)
     (the per-image bookkeeping of evaluate/eval2.py:28-98, whole-array): a ground-truth box is CARED FOR when it carries the evaluated
     class name and passes the difficulty level's caps -- occlusion, truncation, and the distance band the reference uses instead of
     the official image-height rule; it is IGNORED (matches cost nothing) when it fails a cap or carries the neighbouring class
     (Van for Car, Person_sitting for Pedestrian); everything else is another class.  A detection outside the distance band is
-    ignored, one of another class does not take part.  DontCare boxes are handed back for the false-positive exemption."""
+    ignored, one of another class does not take part.  DontCare boxes are handed back for the false-positive exemption.
+    metric="old" (eval_old.py:28-91): three levels; instead of the distance band a ground-truth box is ignored when its bbox height
+    is <= min_height(dataset)[difficulty] and a detection when |height| is below it -- the only place ``dataset`` matters."""
     cls = CLASS_NAMES[current_class]
-    near, far = DIST_BOUNDARY[0, difficulty], DIST_BOUNDARY[1, difficulty]
+    _difficulties(metric)
     raw = np.asarray(gt_anno["name"], dtype=str).reshape(-1)
     names = np.char.lower(raw) if raw.size else raw
-    depth = np.asarray(gt_anno["location"], dtype=np.float64).reshape(-1, 3)[:, 2]
-    capped = ((np.asarray(gt_anno["occluded"]).reshape(-1) > MAX_OCCLUSION[difficulty]) |
-              (np.asarray(gt_anno["truncated"]).reshape(-1) > MAX_TRUNCATION[difficulty]) | ~((near < depth) & (depth < far)))
+    gt_bbox = np.asarray(gt_anno["bbox"], dtype=np.float64).reshape(-1, 4)
+    det = np.asarray(dt_anno["name"], dtype=str).reshape(-1)
+    if metric == "old":
+        cap = min_height(dataset)[difficulty]
+        capped = ((np.asarray(gt_anno["occluded"]).reshape(-1) > OLD_MAX_OCCLUSION[difficulty]) |
+                  (np.asarray(gt_anno["truncated"]).reshape(-1) > OLD_MAX_TRUNCATION[difficulty]) |
+                  (gt_bbox[:, 3] - gt_bbox[:, 1] <= cap))
+        dt_bbox = np.asarray(dt_anno["bbox"], dtype=np.float64).reshape(-1, 4)
+        in_band = ~(np.abs(dt_bbox[:, 3] - dt_bbox[:, 1]) < cap)
+    else:
+        near, far = DIST_BOUNDARY[0, difficulty], DIST_BOUNDARY[1, difficulty]
+        depth = np.asarray(gt_anno["location"], dtype=np.float64).reshape(-1, 3)[:, 2]
+        capped = ((np.asarray(gt_anno["occluded"]).reshape(-1) > MAX_OCCLUSION[difficulty]) |
+                  (np.asarray(gt_anno["truncated"]).reshape(-1) > MAX_TRUNCATION[difficulty]) | ~((near < depth) & (depth < far)))
+        det_depth = np.asarray(dt_anno["location"], dtype=np.float64).reshape(-1, 3)[:, 2]
+        in_band = (near < det_depth) & (det_depth < far)
     own = names == cls
     sibling = names == {"pedestrian": "person_sitting", "car": "van"}.get(cls, "\0")
     ignored_gt = np.full(names.shape, -1, dtype=np.int64)
     ignored_gt[sibling | (own & capped)] = 1
     ignored_gt[own & ~capped] = 0
-    dc_bboxes = np.asarray(gt_anno["bbox"], dtype=np.float64).reshape(-1, 4)[raw == "DontCare"]
-    det = np.asarray(dt_anno["name"], dtype=str).reshape(-1)
-    det_depth = np.asarray(dt_anno["location"], dtype=np.float64).reshape(-1, 3)[:, 2]
-    in_band = (near < det_depth) & (det_depth < far)
+    dc_bboxes = gt_bbox[raw == "DontCare"]
     det_own = (np.char.lower(det) if det.size else det) == cls
     ignored_dt = np.where(in_band, np.where(det_own, 0, -1), 1).astype(np.int64)
     return int(np.count_nonzero(ignored_gt == 0)), ignored_gt, ignored_dt, dc_bboxes
@@ -242,11 +282,11 @@ def _ptr(a):
 class _Split:
     """Concatenated per-image arrays of one (class, difficulty) in the layout csrc/kitti_stats.hip reads."""
 
-    def __init__(self, gt_annos, dt_annos, current_class, dataset, difficulty):
+    def __init__(self, gt_annos, dt_annos, current_class, dataset, difficulty, metric="new"):
         ig, idt, dcs, gts, dts = [], [], [], [], []
         self.num_valid_gt = 0
         for g, d in zip(gt_annos, dt_annos):
-            nv, ignored_gt, ignored_dt, dc = clean_data(g, d, current_class, dataset, difficulty)
+            nv, ignored_gt, ignored_dt, dc = clean_data(g, d, current_class, dataset, difficulty, metric)
             self.num_valid_gt += nv
             ig.append(ignored_gt)
             idt.append(ignored_dt)
@@ -263,9 +303,10 @@ class _Split:
 
 
 def eval_class(gt_annos, dt_annos, current_classes, dataset, difficultys, metric, min_overlaps, compute_aos=False,
-               device_id=0, overlaps=None):
+               device_id=0, overlaps=None, difficulty_metric="new"):
     """-> dict(recall, precision, orientation), each [num_class, num_difficulty, num_minoverlap, 41]
-    (eval2.py:460-569).  min_overlaps: [num_minoverlap, metric, num_class]."""
+    (eval2.py:460-569).  min_overlaps: [num_minoverlap, metric, num_class].  ``metric`` is the overlap kind (0 image box / 1 BEV /
+    2 3D) as in the reference; the difficulty rule ("new" | "old", the ``metric`` keyword everywhere else) is ``difficulty_metric``."""
     assert len(gt_annos) == len(dt_annos)
     n_img = len(gt_annos)
     if overlaps is None:
@@ -275,7 +316,7 @@ def eval_class(gt_annos, dt_annos, current_classes, dataset, difficultys, metric
     precision, recall, aos = np.zeros(shape), np.zeros(shape), np.zeros(shape)
     for m, current_class in enumerate(current_classes):
         for l, difficulty in enumerate(difficultys):
-            sp = _Split(gt_annos, dt_annos, current_class, dataset, difficulty)
+            sp = _Split(gt_annos, dt_annos, current_class, dataset, difficulty, difficulty_metric)
             for k, min_overlap in enumerate(min_overlaps[:, metric, m]):
                 scores = np.zeros((max(1, int(sp.gt_nums.sum())),), dtype=np.float64)
                 n_scores = ctypes.c_longlong(0)
@@ -309,15 +350,16 @@ def get_mAP(prec):
     return np.cumsum(prec[..., ::4], axis=-1)[..., -1] / 11 * 100
 
 
-def do_eval(gt_annos, dt_annos, current_classes, dataset, min_overlaps, compute_aos=False, device_id=0):
-    difficultys = [0, 1, 2, 3, 4, 5]
-    ret = eval_class(gt_annos, dt_annos, current_classes, dataset, difficultys, 0, min_overlaps, compute_aos, device_id)
+def do_eval(gt_annos, dt_annos, current_classes, dataset, min_overlaps, compute_aos=False, device_id=0, metric="new"):
+    difficultys = _difficulties(metric)
+    ret = eval_class(gt_annos, dt_annos, current_classes, dataset, difficultys, 0, min_overlaps, compute_aos, device_id,
+                     difficulty_metric=metric)
     mAP_bbox = get_mAP(ret["precision"])
     mAP_aos = get_mAP(ret["orientation"]) if compute_aos else None
     mAP_bev = get_mAP(eval_class(gt_annos, dt_annos, current_classes, dataset, difficultys, 1, min_overlaps,
-                                 device_id=device_id)["precision"])
+                                 device_id=device_id, difficulty_metric=metric)["precision"])
     mAP_3d = get_mAP(eval_class(gt_annos, dt_annos, current_classes, dataset, difficultys, 2, min_overlaps,
-                                device_id=device_id)["precision"])
+                                device_id=device_id, difficulty_metric=metric)["precision"])
     return mAP_bbox, mAP_bev, mAP_3d, mAP_aos
 
 
@@ -327,29 +369,38 @@ def _line(value):
     return s.getvalue()
 
 
-def get_official_eval_result(gt_annos, dt_annos, current_classes, dataset="kitti", dense_sample=False, device_id=0):
-    """-> (result text, dict) in the reference's format (eval2.py:608-716)."""
+def _class_ids(current_classes):
+    name_to_class = {v: n for n, v in CLASS_TO_NAME.items()}
+    if not isinstance(current_classes, (list, tuple)):
+        current_classes = [current_classes]
+    return [name_to_class[c] if isinstance(c, str) else c for c in current_classes]
+
+
+def _alpha_is_valid(dt_annos):
+    for anno in dt_annos:
+        if anno["alpha"].shape[0] != 0:
+            return bool(anno["alpha"][0] != -10)
+    return False
+
+
+def get_official_eval_result(gt_annos, dt_annos, current_classes, dataset="kitti", dense_sample=False, device_id=0, metric="new"):
+    """-> (result text, dict) in the reference's format (eval2.py:629-722; metric="old": eval_old.py:619-695, three numbers per
+    line and no dense sampling)."""
     overlap_0_7 = np.array([[0.7, 0.5, 0.5, 0.7, 0.5], [0.7, 0.5, 0.5, 0.7, 0.5], [0.7, 0.5, 0.5, 0.7, 0.5]])
     overlap_0_5 = np.array([[0.7, 0.5, 0.5, 0.7, 0.5], [0.5, 0.25, 0.25, 0.5, 0.25], [0.5, 0.25, 0.25, 0.5, 0.25]])
     extra = []
-    if dense_sample:
+    if dense_sample and metric == "new":
         for i in range(101):
             tmp = np.zeros((3, 5))
             tmp[:, 0] = i / 100.0
             extra.append(tmp)
     min_overlaps = np.stack([overlap_0_7, overlap_0_5] + extra, axis=0)
-    name_to_class = {v: n for n, v in CLASS_TO_NAME.items()}
-    if not isinstance(current_classes, (list, tuple)):
-        current_classes = [current_classes]
-    current_classes = [name_to_class[c] if isinstance(c, str) else c for c in current_classes]
+    current_classes = _class_ids(current_classes)
     min_overlaps = min_overlaps[:, :, current_classes]
-    compute_aos = False
-    for anno in dt_annos:
-        if anno["alpha"].shape[0] != 0:
-            if anno["alpha"][0] != -10:
-                compute_aos = True
-            break
-    mAPbbox, mAPbev, mAP3d, mAPaos = do_eval(gt_annos, dt_annos, current_classes, dataset, min_overlaps, compute_aos, device_id)
+    compute_aos = _alpha_is_valid(dt_annos)
+    mAPbbox, mAPbev, mAP3d, mAPaos = do_eval(gt_annos, dt_annos, current_classes, dataset, min_overlaps, compute_aos, device_id,
+                                             metric)
+    levels = range(len(_difficulties(metric)))
     result = ""
     res = {}
     for j, curcls in enumerate(current_classes):
@@ -359,9 +410,9 @@ def get_official_eval_result(gt_annos, dt_annos, current_classes, dataset="kitti
             res[curcls][head] = {"mAPbbox": mAPbbox[j, :, i], "mAPbev": mAPbev[j, :, i], "mAP3d": mAP3d[j, :, i]}
             result += _line(head + ":")
             for tag, arr in (("bbox AP:", mAPbbox), ("bev  AP:", mAPbev), ("3d   AP:", mAP3d)):
-                result += _line(tag + "".join("%.4f, " % arr[j, d, i] for d in range(6)))
-            if compute_aos:
-                result += _line("aos  AP:" + ", ".join("%.2f" % mAPaos[j, d, i] for d in range(6)))
+                result += _line(tag + "".join("%.4f, " % arr[j, d, i] for d in levels))
+            if compute_aos:                           # the old metric's line keeps its trailing separator (eval_old.py:681-683)
+                result += _line("aos  AP:" + ", ".join("%.2f" % mAPaos[j, d, i] for d in levels) + (", " if metric == "old" else ""))
     ret = {"result": res}
     for tag, arr in (("3d", mAP3d), ("bev", mAPbev), ("image", mAPbbox)):
         for d, name in enumerate(("easy", "moderate", "hard")):
@@ -369,10 +420,344 @@ def get_official_eval_result(gt_annos, dt_annos, current_classes, dataset="kitti
     return result, ret
 
 
-def evaluate(result_path, label_path, image_ids, current_class=0, dataset="kitti", score_thresh=-1, device_id=0):
-    """Result folder + label folder + id list -> (result text, dict) (evaluate.py:88-135, plain branch)."""
-    dt_annos = get_label_annos(result_path, list(image_ids))
+COCO_RANGE = {0: [0.5, 0.95, 10], 1: [0.25, 0.7, 10], 2: [0.25, 0.7, 10], 3: [0.5, 0.95, 10], 4: [0.25, 0.7, 10]}
+
+
+def do_coco_style_eval(gt_annos, dt_annos, current_classes, overlap_ranges, compute_aos, dataset="kitti", device_id=0, metric="new"):
+    """mAP averaged over ten overlap thresholds (eval2.py:611-626).  overlap_ranges: [lo / hi / count, overlap kind, num_class].
+    The reference's call of do_eval is one argument short since ``dataset`` joined its signature; this passes it."""
+    min_overlaps = np.zeros([10, *overlap_ranges.shape[1:]])
+    for i in range(overlap_ranges.shape[1]):
+        for j in range(overlap_ranges.shape[2]):
+            lo, hi, num = overlap_ranges[:, i, j]
+            min_overlaps[:, i, j] = np.linspace(lo, hi, int(num))
+    mAP_bbox, mAP_bev, mAP_3d, mAP_aos = do_eval(gt_annos, dt_annos, current_classes, dataset, min_overlaps, compute_aos, device_id,
+                                                 metric)
+    return mAP_bbox.mean(-1), mAP_bev.mean(-1), mAP_3d.mean(-1), None if mAP_aos is None else mAP_aos.mean(-1)
+
+
+def get_coco_eval_result(gt_annos, dt_annos, current_classes, dataset="kitti", device_id=0, metric="new"):
+    """-> result text (eval2.py:725-784): three numbers per line for either metric."""
+    current_classes = _class_ids(current_classes)
+    overlap_ranges = np.zeros([3, 3, len(current_classes)])
+    for i, curcls in enumerate(current_classes):
+        overlap_ranges[:, :, i] = np.array(COCO_RANGE[curcls])[:, np.newaxis]
+    compute_aos = _alpha_is_valid(dt_annos)
+    mAPs = do_coco_style_eval(gt_annos, dt_annos, current_classes, overlap_ranges, compute_aos, dataset, device_id, metric)
+    result = ""
+    for j, curcls in enumerate(current_classes):
+        lo, hi, num = COCO_RANGE[curcls]
+        result += _line("%s coco AP@%.2f:%.2f:%.2f:" % (CLASS_TO_NAME[curcls], lo, (hi - lo) / (num - 1), hi))
+        for tag, arr in zip(("bbox AP:", "bev  AP:", "3d   AP:", "aos  AP:"), mAPs):
+            if arr is not None:
+                result += _line(tag + ", ".join("%.2f" % arr[j, d] for d in range(3)))
+    return result
+
+
+# ---------------------------------------------------------------------------------------------------
+# best match and the output transformations (evaluate.py:17-81, 114-275)
+# ---------------------------------------------------------------------------------------------------
+def _segments(dt_annos, gt_annos):
+    assert len(dt_annos) == len(gt_annos)
+    n = np.array([len(a["name"]) for a in dt_annos], dtype=np.int64)
+    k = np.array([len(a["name"]) for a in gt_annos], dtype=np.int64)
+    return (np.concatenate([[0], np.cumsum(n)]).astype(np.int32), np.concatenate([[0], np.cumsum(k)]).astype(np.int32))
+
+
+def _cat(arrays, width, dtype=np.float64):
+    parts = [np.asarray(a, dtype=dtype).reshape((-1, width) if width else (-1,)) for a in arrays]
+    return np.ascontiguousarray(np.concatenate(parts, 0) if parts else np.zeros((0, width) if width else (0,), dtype))
+
+
+def _best_match_device(dt_annos, gt_annos, device_id=0, columns=True):
+    """One prcnn_bev_best_match launch over all images.  -> dict of DEVICE tensors row_val / row_idx (/ col_val / col_idx),
+    box_off / q_off, and the host offsets."""
+    import torch
+    box_off, q_off = _segments(dt_annos, gt_annos)
+    n, k = int(box_off[-1]), int(q_off[-1])
+    dev = torch.device("cuda", device_id)
+    boxes = torch.from_numpy(_cat([_bev_boxes(a) for a in dt_annos], 5, np.float32)).to(dev)
+    query = torch.from_numpy(_cat([_bev_boxes(a) for a in gt_annos], 5, np.float32)).to(dev)
+    m = {"box_off_host": box_off, "q_off_host": q_off, "box_off": torch.from_numpy(box_off).to(dev), "q_off": torch.from_numpy(q_off).to(dev),
+         "row_val": torch.empty((n,), dtype=torch.float32, device=dev), "row_idx": torch.empty((n,), dtype=torch.int32, device=dev),
+         "col_val": torch.empty((k,), dtype=torch.float32, device=dev) if columns else None,
+         "col_idx": torch.empty((k,), dtype=torch.int32, device=dev) if columns else None}
+    with torch.cuda.device(dev):
+        _lib.call("prcnn_bev_best_match", len(dt_annos), n, k, m["box_off"].data_ptr(), m["q_off"].data_ptr(), boxes.data_ptr(),
+                  query.data_ptr(), -1, m["row_val"].data_ptr(), m["row_idx"].data_ptr(), _lib.ptr(m["col_val"]), _lib.ptr(m["col_idx"]),
+                  _lib.current_stream(boxes))
+    return m
+
+
+def best_match(dt_annos, gt_annos, device="cuda", device_id=0):
+    """-> (dt_matches, gt_matches): per image (val f64, idx i64) -- for every detection the largest BEV overlap with a ground-truth box
+    of its image and that box's index (np.max / np.argmax: ties to the lowest index), and the same for every ground-truth box over the
+    detections (evaluate.py:135-207).  An image with an empty side gives val 0, idx -1.
+    device "cuda": the fused launch (no pair matrix); "cpu": numpy over calculate_iou(..., 1)."""
+    if device == "cuda":
+        m = _best_match_device(dt_annos, gt_annos, device_id)
+        host = {key: m[key].cpu().numpy() for key in ("row_val", "row_idx", "col_val", "col_idx")}
+        out = []
+        for off, val, idx in ((m["box_off_host"], host["row_val"], host["row_idx"]), (m["q_off_host"], host["col_val"], host["col_idx"])):
+            out.append([(val[off[i]:off[i + 1]].astype(np.float64), idx[off[i]:off[i + 1]].astype(np.int64)) for i in range(len(dt_annos))])
+        return out[0], out[1]
+    if device != "cpu":
+        raise ValueError("device %r is neither 'cuda' nor 'cpu'" % (device,))
+    dt_matches, gt_matches = [], []
+    for o in calculate_iou(dt_annos, gt_annos, 1, device_id):
+        for axis, other, into in ((1, 0, dt_matches), (0, 1, gt_matches)):
+            if o.shape[0] > 0 and o.shape[1] > 0:
+                into.append((np.max(o, axis=axis), np.argmax(o, axis=axis).astype(np.int64)))
+            else:
+                into.append((np.zeros(o.shape[other]), np.full(o.shape[other], -1, dtype=np.int64)))
+    return dt_matches, gt_matches
+
+
+def read_plane(fname):
+    with open(fname) as f:
+        return np.array([float(v) for v in f.readlines()[-1].split(" ")])
+
+
+def annos_to_ground(annos, planes_dir, ids):
+    """Drop every box onto its image's ground plane a x + b y + c z + d = 0: the last line of <planes_dir>/<id>.txt (evaluate.py:17-35)."""
+    for anno, i in zip(annos, ids):
+        plane = read_plane(os.path.join(planes_dir, "%06d.txt" % i))
+        anno["location"][:, 1] -= (-plane[3] - plane[0] * anno["location"][:, 0] - plane[2] * anno["location"][:, 2]) / plane[1]
+    return annos
+
+
+def rescale_pred(annos, ratio):
+    for anno in annos:
+        anno["dimensions"] *= ratio
+    return annos
+
+
+def _align(dt_annos, gt_annos, mode, device, device_id):
+    """align_size (mode 0) / align_front (mode 1), in place.  -> per image branch codes (-1 untouched; bits as prcnn_eval_align)."""
+    if device == "cuda":
+        import torch
+        m = _best_match_device(dt_annos, gt_annos, device_id, columns=False)
+        dev = m["row_val"].device
+        up = lambda annos, key, w: torch.from_numpy(_cat([a[key] for a in annos], w)).to(dev)
+        loc, dim = up(dt_annos, "location", 3), up(dt_annos, "dimensions", 3)
+        alpha, ry, gdim = up(dt_annos, "alpha", 0), up(dt_annos, "rotation_y", 0), up(gt_annos, "dimensions", 3)
+        branch = torch.empty((loc.shape[0],), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.call("prcnn_eval_align", len(dt_annos), loc.shape[0], m["box_off"].data_ptr(), m["q_off"].data_ptr(), loc.data_ptr(),
+                      dim.data_ptr(), alpha.data_ptr(), ry.data_ptr(), gdim.data_ptr(), m["row_val"].data_ptr(), m["row_idx"].data_ptr(),
+                      int(mode), branch.data_ptr(), _lib.current_stream(loc))
+        loc, dim, branch, off = loc.cpu().numpy(), dim.cpu().numpy(), branch.cpu().numpy().astype(np.int64), m["box_off_host"]
+        for i, anno in enumerate(dt_annos):
+            anno["location"][...] = loc[off[i]:off[i + 1]]
+            anno["dimensions"][...] = dim[off[i]:off[i + 1]]
+        return [branch[off[i]:off[i + 1]] for i in range(len(dt_annos))]
+    branches = []
+    for dt, gt, (val, idx) in zip(dt_annos, gt_annos, best_match(dt_annos, gt_annos, device, device_id)[0]):
+        code = np.full(len(val), -1, dtype=np.int64)
+        for j in range(len(val)):
+            if val[j] > ALIGN_MIN_OVERLAP:
+                code[j] = 0
+                if mode == 1:                          # evaluate.py:210-228
+                    dist = np.linalg.norm(dt["location"][j, :])
+                    alpha = dt["alpha"][j]
+                    alpha = np.arctan2(np.sin(alpha), np.cos(alpha))
+                    if np.abs(np.sin(alpha)) * dist > dt["dimensions"][j, 2] / 2.0:
+                        shift = (dt["dimensions"][j, 2] - gt["dimensions"][idx[j], 2]) / 2.0
+                        angle = -dt["rotation_y"][j] if 0 < alpha else -dt["rotation_y"][j] + np.pi
+                        code[j] |= 1 | (2 if 0 < alpha else 0)
+                        dt["location"][j, 0] += shift * np.cos(angle)
+                        dt["location"][j, 2] += shift * np.sin(angle)
+                    if np.abs(np.cos(alpha)) * dist > dt["dimensions"][j, 1] / 2.0:
+                        shift = (dt["dimensions"][j, 1] - gt["dimensions"][idx[j], 1]) / 2.0
+                        inner = -np.pi / 2.0 < alpha < np.pi / 2.0
+                        angle = -dt["rotation_y"][j] - np.pi / 2.0 if inner else -dt["rotation_y"][j] + np.pi / 2.0
+                        code[j] |= 4 | (8 if inner else 0)
+                        dt["location"][j, 0] += shift * np.cos(angle)
+                        dt["location"][j, 2] += shift * np.sin(angle)
+                dt["dimensions"][j, :] = gt["dimensions"][idx[j], :]
+        branches.append(code)
+    return branches
+
+
+def align_size(dt_annos, gt_annos, device="cuda", device_id=0):
+    """Every detection whose best BEV overlap exceeds 0.2 takes the size of that ground-truth box (evaluate.py:187-197)."""
+    _align(dt_annos, gt_annos, 0, device, device_id)
+    return dt_annos
+
+
+def align_front(dt_annos, gt_annos, device="cuda", device_id=0):
+    """... and is first moved so that its faces towards the camera stay where they were (evaluate.py:200-229)."""
+    _align(dt_annos, gt_annos, 1, device, device_id)
+    return dt_annos
+
+
+def get_scale_map(src, dst, form="regular"):
+    """Map (n,3) dimensions (l, h, w) from the source statistics to the destination's (evaluate.py:58-81).  src / dst: the
+    ``label_stats_<split>.json`` dicts of ``stat_norm stats`` (length / height / width -> mean, std)."""
+    keys = ("length", "height", "width")
+    if form == "regular":
+        f = lambda x, s, d: x - s["mean"] + d["mean"]
+    elif form == "gaussian":
+        f = lambda x, s, d: (x - s["mean"]) / s["std"] * d["std"] + d["mean"]
+    elif form == "log":
+        f = lambda x, s, d: x / s["mean"] * d["mean"]
+    else:
+        raise ValueError("scale_map %r is none of regular, gaussian, log" % (form,))
+    return lambda x: np.stack([f(x[:, c], src[key], dst[key]) for c, key in enumerate(keys)], axis=1)
+
+
+def _stats(s):
+    if isinstance(s, dict):
+        return s
+    with open(s) as f:
+        return json.load(f)
+
+
+def reverse_align(gt_annos, src_stats, dst_stats, scale_map="regular"):
+    """Statistical normalization applied to the ground-truth sizes (evaluate.py:232-249); statistics as dicts or file names."""
+    mapping = get_scale_map(_stats(src_stats), _stats(dst_stats), scale_map)
+    for anno in gt_annos:
+        if len(anno["name"]) > 0:
+            anno["dimensions"] = mapping(anno["dimensions"])
+    return gt_annos
+
+
+def to_kitti_format(anno, extra=None):
+    """Annotation -> the reference's 16-column %.2f text (kitti_common.py:293-304); ``extra``: a 17th column."""
+    rows = []
+    for i in range(len(anno["name"])):
+        row = "%s %.2f %d %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f" % (
+            anno["name"][i], anno["truncated"][i], anno["occluded"][i], anno["alpha"][i],
+            anno["bbox"][i, 0], anno["bbox"][i, 1], anno["bbox"][i, 2], anno["bbox"][i, 3],
+            anno["dimensions"][i, 1], anno["dimensions"][i, 2], anno["dimensions"][i, 0],
+            anno["location"][i, 0], anno["location"][i, 1], anno["location"][i, 2], anno["rotation_y"][i], anno["score"][i])
+        rows.append(row if extra is None else row + " %.2f" % extra[i])
+    return "\n".join(rows)
+
+
+def save_labels(annos, folder, ids, extras=None):
+    assert len(annos) == len(ids)
+    os.makedirs(folder, exist_ok=True)
+    for n, (anno, i) in enumerate(zip(annos, ids)):
+        with open(os.path.join(folder, "%06d.txt" % i), "w") as f:
+            f.write(to_kitti_format(anno, None if extras is None else extras[n]))
+
+
+def write_with_iou(dt_annos, gt_annos, parent, ids, device="cuda", device_id=0):
+    """<parent>/with_iou: the detections with their best BEV overlap as a 17th column; <parent>/with_iou_gt: the ground truth
+    with theirs (evaluate.py:130-185)."""
+    dt_matches, gt_matches = best_match(dt_annos, gt_annos, device, device_id)
+    save_labels(dt_annos, os.path.join(parent, "with_iou"), ids, [v for v, _ in dt_matches])
+    save_labels(gt_annos, os.path.join(parent, "with_iou_gt"), ids, [v for v, _ in gt_matches])
+
+
+def direct_save(result_path, text, result, toground=False, align_size=False, reverse_align=False, adapted=False):
+    """Result text and per-class dict beside the run folder: <run>_val20[_ground][_align_size][_reverse_align][_adapted].txt / .pkl
+    in the folder that holds <run>/<result folder> (evaluate.py:258-274).  -> the path without extension."""
+    run = os.path.dirname(result_path)
+    fname = os.path.basename(run) + "_val20"
+    for on, tag in ((toground, "_ground"), (align_size, "_align_size"), (reverse_align, "_reverse_align"), (adapted, "_adapted")):
+        if on:
+            fname += tag
+    base = os.path.join(os.path.dirname(run), fname)
+    with open(base + ".pkl", "wb") as f:
+        pickle.dump(result, f)
+    with open(base + ".txt", "w") as f:
+        f.write(text)
+    return base
+
+
+# evaluate() takes the reference's keyword names, which are these functions' names
+_TRANSFORMS = {"rescale_pred": rescale_pred, "align_size": align_size, "align_front": align_front, "reverse_align": reverse_align,
+               "direct_save": direct_save}
+
+
+def evaluate(result_path, label_path, image_ids, current_class=0, dataset="kitti", score_thresh=-1, device_id=0, metric="new",
+             coco=False, toground=False, rescale_pred=None, align_size=False, align_front=False, reverse_align=False,
+             dense_sample=False, direct_save=False, output_iou=False, adapted=False, planes_path=None, src_stats=None,
+             dst_stats=None, scale_map="regular", device="cuda"):
+    """Result folder + label folder + id list -> (result text, dict); the text alone with ``coco``; None with ``output_iou``
+    (evaluate.py:84-275, the switches in the reference's order of application).  The transformed labels go where the reference
+    puts them: grounded/, align_size/, align_front/, reverse_align/, with_iou/, with_iou_gt/ beside the result folder.
+    planes_path defaults to <label folder>/../planes; reverse_align reads its two statistics from src_stats / dst_stats.
+    ``device`` selects how best matches and alignment are computed ("cuda": csrc/eval_match.hip, "cpu": numpy)."""
+    g = _TRANSFORMS
+    image_ids = list(image_ids)
+    parent = os.path.dirname(result_path)
+    dt_annos = get_label_annos(result_path, image_ids)
     if score_thresh > 0:
         dt_annos = filter_annos_low_score(dt_annos, score_thresh)
-    gt_annos = get_label_annos(label_path, list(image_ids))
-    return get_official_eval_result(gt_annos, dt_annos, current_class, dataset, device_id=device_id)
+    if toground:
+        dt_annos = annos_to_ground(dt_annos, planes_path or os.path.join(os.path.dirname(label_path), "planes"), image_ids)
+        save_labels(dt_annos, os.path.join(parent, "grounded"), image_ids)
+    if rescale_pred is not None:
+        dt_annos = g["rescale_pred"](dt_annos, rescale_pred)
+    gt_annos = get_label_annos(label_path, image_ids)
+    if output_iou:
+        write_with_iou(dt_annos, gt_annos, parent, image_ids, device, device_id)
+    if align_size:
+        dt_annos = g["align_size"](dt_annos, gt_annos, device, device_id)
+        save_labels(dt_annos, os.path.join(parent, "align_size"), image_ids)
+    if align_front:
+        dt_annos = g["align_front"](dt_annos, gt_annos, device, device_id)
+        save_labels(dt_annos, os.path.join(parent, "align_front"), image_ids)
+    if reverse_align:
+        if src_stats is None or dst_stats is None:
+            raise ValueError("reverse_align needs src_stats and dst_stats (label_stats_<split>.json of `stat_norm stats`)")
+        gt_annos = g["reverse_align"](gt_annos, src_stats, dst_stats, scale_map)
+        save_labels(gt_annos, os.path.join(parent, "reverse_align"), image_ids)
+    if output_iou:
+        return None
+    if coco:
+        return get_coco_eval_result(gt_annos, dt_annos, current_class, dataset, device_id, metric)
+    text, ret = get_official_eval_result(gt_annos, dt_annos, current_class, dataset, dense_sample, device_id, metric)
+    if direct_save:
+        g["direct_save"](result_path, text, ret["result"], toground, align_size, reverse_align, adapted)
+    return text, ret
+
+
+def read_imageset_file(path):
+    with open(path) as f:
+        return [int(line) for line in f.readlines()]
+
+
+def main(argv=None):
+    import argparse
+    ap = argparse.ArgumentParser(prog="python -m 3d_adapt_auto_driving_amd.kitti_eval", description=__doc__.split("\n")[0])
+    ap.add_argument("--result_path", type=str, required=True, help="predictions to be evaluated")
+    ap.add_argument("--dataset_path", type=str, default=None, help="KITTI format dataset path")
+    ap.add_argument("--label_split_file", type=str, default=None, help="split file containing data ids to be evaluated")
+    ap.add_argument("--label_path", type=str, default=None, help="ground truth label files")
+    ap.add_argument("--metric", type=str, default="new", choices=["new", "old"], help="difficulty by [old: bbox height, new: distance]")
+    ap.add_argument("--current_class", type=int, default=0, choices=range(5), help="0: Car, 1: Pedestrian, 2: Cyclist, 3: Van, 4: Person_sitting")
+    ap.add_argument("--toground", action="store_true", help="move predictions to ground plane")
+    ap.add_argument("--rescale_pred", type=int, default=None, help="scale all prediction boxes with this ratio")
+    ap.add_argument("--align_size", action="store_true", help="set prediction box size same as ground truth")
+    ap.add_argument("--align_front", action="store_true", help="align bbox's face facing camera with ground truth")
+    ap.add_argument("--reverse_align", action="store_true", help="apply statistical normalization to ground truth (needs --src_stats, --dst_stats)")
+    ap.add_argument("--dataset", type=str, default="kitti", choices=sorted(FOCAL), help="focal length of the old metric's height caps")
+    ap.add_argument("--coco", action="store_true", help="COCO-style result (mean over ten overlap thresholds)")
+    ap.add_argument("--score_thresh", type=float, default=-1)
+    ap.add_argument("--dense_sample", action="store_true", help="also AP at overlap 0.00, 0.01, ..., 1.00 (new metric)")
+    ap.add_argument("--direct_save", action="store_true", help="write <run>_val20[...].txt / .pkl beside the run folder")
+    ap.add_argument("--output_iou", action="store_true", help="write with_iou/ and with_iou_gt/ and stop")
+    ap.add_argument("--adapted", action="store_true", help="tag for the --direct_save file name")
+    ap.add_argument("--src_stats", type=str, default=None, help="label_stats_<split>.json of the labels' dataset")
+    ap.add_argument("--dst_stats", type=str, default=None, help="label_stats_<split>.json of the model's dataset")
+    ap.add_argument("--scale_map", type=str, default="regular", choices=["regular", "gaussian", "log"])
+    ap.add_argument("--device", type=str, default="cuda", choices=["cuda", "cpu"], help="best match / alignment: fused HIP launch or numpy")
+    args = vars(ap.parse_args(argv))
+    dataset_path = args.pop("dataset_path")
+    split_file, label_path = args.pop("label_split_file"), args.pop("label_path")
+    if dataset_path is None and (split_file is None or label_path is None):
+        ap.error("give --dataset_path, or both --label_split_file and --label_path")
+    split_file = split_file or os.path.join(dataset_path, "val.txt")
+    label_path = label_path or os.path.join(dataset_path, "training", "label_2")
+    out = evaluate(args.pop("result_path"), label_path, read_imageset_file(split_file), **args)
+    if out is not None:
+        print(out if isinstance(out, str) else out[0])
+    return out
+
+
+if __name__ == "__main__":
+    main()

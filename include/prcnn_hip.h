@@ -568,6 +568,25 @@ int prcnn_rotate_iou_eval_segmented(int nseg, long long total, const long long *
                                     const int *q_off, const float *boxes, const float *query_boxes, float *iou,
                                     int criterion, void *stream);
 
+/* Fused best match over the segmented layout above (csrc/eval_match.hip; evaluate/evaluate.py:135-207 takes np.max / np.argmax of
+ * every image's BEV overlap block, along both axes).  n = box_off[nseg] boxes, k = q_off[nseg] queries, offsets DEVICE i32.
+ * -> row_val (n) f32 / row_idx (n) i32: for every box the maximum over its segment's queries of the pair value
+ * prcnn_rotate_iou_eval_segmented would have written (bit-equal) and the segment-local index where it is first reached;
+ * col_val (k) / col_idx (k): the same for every query over its segment's boxes, both may be NULL.  A segment whose other side is
+ * empty yields value 0 and index -1.  No (n x k) buffer exists anywhere. */
+int prcnn_bev_best_match(int nseg, int n, int k, const int *box_off, const int *q_off, const float *boxes,
+                         const float *query_boxes, int criterion, float *row_val, int *row_idx, float *col_val, int *col_idx,
+                         void *stream);
+
+/* align_size (mode 0) / align_front (mode 1) of evaluate/evaluate.py:187-230, one thread per detection, f64, DEVICE pointers.
+ * location (n,3) and dimensions (n,3; stored l, h, w) are rewritten in place for detections whose row_val, widened to f64, is
+ * > 0.2: dimensions take the matched ground-truth row of gt_dimensions (q_off[segment] + row_idx), align_front first shifts the
+ * location along the box axes by half the size differences.  branch (n) i32 or NULL: -1 untouched, else bit 0 first shift taken,
+ * bit 1 its 0 < alpha choice, bit 2 second shift taken, bit 3 its |alpha| < pi / 2 choice. */
+int prcnn_eval_align(int nseg, int n, const int *box_off, const int *q_off, double *location, double *dimensions,
+                     const double *alpha, const double *rotation_y, const double *gt_dimensions, const float *row_val,
+                     const int *row_idx, int mode, int *branch, void *stream);
+
 /* ---- lib/datasets/kitti_rcnn_dataset.py: the network-input stage on the device ---------- */
 
 /* get_lidar + get_valid_flag + the near/far sampler of get_rpn_sample (kitti_rcnn_dataset.py:249-324) with
