@@ -130,6 +130,10 @@ SIGNATURES = {
     "prcnn_stat_norm_occlusion": [_I, _I, _I, _I, _P, _P, _P, _P],
     "prcnn_rpn_labels_workspace": [_I, _I, _P],
     "prcnn_rpn_labels": [_I, _I, _I, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P],
+    "prcnn_gt_box_chunk": [],
+    "prcnn_gt_box_trig": [_I, _P, _P],
+    "prcnn_gt_extract_count": [_P, _P],
+    "prcnn_gt_extract_write": [_P, _P],
 }
 
 _lib = None

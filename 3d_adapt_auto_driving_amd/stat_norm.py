@@ -70,6 +70,19 @@ class Object3d:
             except ValueError:
                 self.track_id = label[15]
 
+    def get_obj_level(self):
+        """The KITTI difficulty of the label (lib/utils/object3d.py get_obj_level): sets ``level_str`` / ``level``, -> level."""
+        height = float(self.box2d[3]) - float(self.box2d[1]) + 1
+        if height >= 40 and self.trucation <= 0.15 and self.occlusion <= 0:
+            self.level_str, self.level = "Easy", 1
+        elif height >= 25 and self.trucation <= 0.3 and self.occlusion <= 1:
+            self.level_str, self.level = "Moderate", 2
+        elif height >= 25 and self.trucation <= 0.5 and self.occlusion <= 2:
+            self.level_str, self.level = "Hard", 3
+        else:
+            self.level_str, self.level = "UnKnown", 4
+        return self.level
+
     def to_kitti_format(self):
         vals = (self.cls_type, self.trucation, int(self.occlusion), self.alpha, self.box2d[0], self.box2d[1], self.box2d[2],
                 self.box2d[3], self.h, self.w, self.l, self.t[0], self.t[1], self.t[2], self.ry)

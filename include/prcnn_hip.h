@@ -676,6 +676,31 @@ int prcnn_rpn_labels_workspace(int b, int g, long long *bytes);
 int prcnn_rpn_labels(int b, int n, int g, const float *pts, const float *gt, const int *counts, const float *trig, const float *scores,
                      float thresh, int *cls, float *reg, int *stats, double *work, void *stream);
 
+/* GT-database point extraction (tools/generate_gt_database.py:59-87) for a batch of ragged scenes (csrc/gt_database.hip).
+ * pt_off / tile_off / box_off (n_scenes + 1) i32: points, 64-point tiles and boxes per scene, back to back; bt_off (n_scenes + 1) i64
+ * into bt_cnt (sum n_box * n_tile) i32; velo (sum n, 4) f32 raw points; calib (n_scenes, 12) f32 = np.dot(V2C.T, R0.T), (4, 3)
+ * row-major; boxes (sum g, 7) f32 [x, y_bottom, z, h, w, l, ry]; trig (sum g, 2) f32 from prcnn_gt_box_trig; counts (sum g) i32
+ * (zeroed by the caller) = points inside every box; out_off (sum g + 1) i64 = exclusive sums of counts; out (sum counts, 4) f32 =
+ * rect x, y, z | intensity, every object's rows in point-index order.  max_tiles / max_boxes: the largest scene's.
+ * The field layout is gt_database.py's _GtBatch. */
+typedef struct prcnn_gt_batch {
+    int n_scenes, max_tiles, max_boxes, reserved;
+    const int *pt_off, *tile_off, *box_off;
+    const long long *bt_off;
+    const float *velo, *calib, *boxes, *trig;
+    int *bt_cnt, *counts;
+    const long long *out_off;
+    float *out;
+} prcnn_gt_batch;
+/* boxes per LDS chunk of the kernels (the tests place their box counts around it) */
+int prcnn_gt_box_chunk(void);
+/* HOST pointers: trig (n, 2) f32 = (cos ry, sin ry) as prcnn_host_pts_in_boxes3d evaluates them */
+int prcnn_gt_box_trig(int n, const float *boxes3d, float *trig);
+/* passes 1 + 2: inside counts per (box, tile) -> ordered exclusive offsets in bt_cnt, totals in counts */
+int prcnn_gt_extract_count(const prcnn_gt_batch *batch, void *stream);
+/* pass 3: the objects' rows (out_off / out set by the caller from the totals) */
+int prcnn_gt_extract_write(const prcnn_gt_batch *batch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
