@@ -18,21 +18,21 @@ import warnings
 # name: (kind, default, read by, meaning)
 SWITCHES = {
     # ---- operational
-    "PRCNN_GRAPHS": ("operational", "1", "eval_rcnn.py", "0: eager enqueue (PipelinedRunner) instead of hipGraph replay (GraphedRunner)"),
-    "PRCNN_GRAPH_SLOTS": ("operational", "depth/group+1", "eval_rcnn.py", "group slots of the graphed runner (>= 2; 5.9 GB of HBM each at batch 8)"),
-    "PRCNN_GEO_GROUP": ("operational", "4", "eval_rcnn.py", "batches per geometry chain"),
-    "PRCNN_PAIR": ("operational", "2", "eval_rcnn.py", "batches of a geometry group that share the launches of the RPN / proposal / RCNN / final stages in the graphed runner (must divide the group; detections come back up to 2 x pair - 1 submits late)"),
-    "PRCNN_GEO_DEPTH": ("operational", "3*group", "eval_rcnn.py", "batches the geometry runs ahead"),
-    "PRCNN_SIDE_STREAMS": ("operational", "2", "eval_rcnn.py", "geometry side streams (with feature + proposal stream: the 4 hardware queues)"),
-    "PRCNN_LOADER_THREADS": ("operational", "1", "eval_rcnn.py", "threads of the numeric libraries (BLAS / OpenMP) in every loader and writer process; 0: leave them alone (round 6: a loader's small numpy products fanned out over the whole host's thread pool)"),
+    "PRCNN_GRAPHS": ("operational", "1", "runners.py", "0: eager enqueue (PipelinedRunner) instead of hipGraph replay (GraphedRunner)"),
+    "PRCNN_GRAPH_SLOTS": ("operational", "depth/group+1", "runners.py", "group slots of the graphed runner (>= 2; 5.9 GB of HBM each at batch 8)"),
+    "PRCNN_GEO_GROUP": ("operational", "4", "runners.py", "batches per geometry chain"),
+    "PRCNN_PAIR": ("operational", "2", "runners.py", "batches of a geometry group that share the launches of the RPN / proposal / RCNN / final stages in the graphed runner (must divide the group; detections come back up to 2 x pair - 1 submits late)"),
+    "PRCNN_GEO_DEPTH": ("operational", "3*group", "runners.py", "batches the geometry runs ahead"),
+    "PRCNN_SIDE_STREAMS": ("operational", "2", "runners.py", "geometry side streams (with feature + proposal stream: the 4 hardware queues)"),
+    "PRCNN_LOADER_THREADS": ("operational", "1", "host.py", "threads of the numeric libraries (BLAS / OpenMP) in every loader and writer process; 0: leave them alone (round 6: a loader's small numpy products fanned out over the whole host's thread pool)"),
     "PRCNN_RAW_SLOT_POINTS": ("operational", "200000", "eval_rcnn.py", "points per raw cloud a slot of the loaders' shared page-locked buffer holds with --device_input (slot = batch x points x 16 bytes; a larger cloud raises)"),
-    "PRCNN_LOADER_WORKERS": ("operational", "budget", "eval_rcnn.py", "loader processes of eval_scenes (default: host_budget)"),
-    "PRCNN_WRITER_PROCS": ("operational", "budget", "eval_rcnn.py", "KITTI result writer processes"),
+    "PRCNN_LOADER_WORKERS": ("operational", "budget", "host.py", "loader processes of eval_scenes (default: host_budget)"),
+    "PRCNN_WRITER_PROCS": ("operational", "budget", "host.py", "KITTI result writer processes"),
     "PRCNN_LOADER_CONTEXT": ("operational", "forkserver/fork", "eval_rcnn.py", "multiprocessing start method of loaders and writers"),
-    "PRCNN_NO_AFFINITY": ("operational", "unset", "eval_rcnn.py", "1: do not pin a rank to its share of the host cores"),
+    "PRCNN_NO_AFFINITY": ("operational", "unset", "host.py", "1: do not pin a rank to its share of the host cores"),
     "PRCNN_RESULT_LAG": ("operational", "3", "eval_rcnn.py", "batches between submitting a batch and reading its detections on the host"),
     "PRCNN_GRAPHS_FORCE": ("debug", "unset", "__init__.py", "1: replay graphs although DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 was not in place (profiles/graph_fault_probe.py)"),
-    "PRCNN_GRAPH_DEBUG": ("debug", "0", "eval_rcnn.py", "bit mask: device syncs + prints around the graph replays"),
+    "PRCNN_GRAPH_DEBUG": ("debug", "0", "runners.py", "bit mask: device syncs + prints around the graph replays"),
     # ---- numerics
     "PRCNN_SPLIT_BF16": ("numerics", "unset", "net/fast_infer.py", "1: EXPERIMENT -- the plain per-point layers (point_layer: FP modules' second layers, coarse products, RCNN heads) on the bf16 matrix cores with every operand split exactly into three bf16 pieces (csrc/split_bf16.hip): ~1e-7 relative to the f32 fma chain, not its bits; measured in profiles/r06_split_bf16.md, never the headline"),
     "PRCNN_NO_FP_LINEAR": ("numerics", "unset", "net/fast_infer.py", "FP layer 1 over the interpolated tensor (reference association) instead of interp(W f)"),

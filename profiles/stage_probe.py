@@ -27,7 +27,7 @@ def wrap(obj, name, tag):
     setattr(obj, name, w)
 wrap(eng, "rpn_stage", "rpn"); wrap(eng, "rcnn_stage", "rcnn"); wrap(eng, "propose", "proposals")
 wrap(eng, "rcnn_geometry", "rcnn_geo"); wrap(eng, "rcnn_features", "rcnn")
-wrap(eng, "geometry_begin", "geo_begin"); wrap(eng, "geometry_finish", "geo_finish"); wrap(eng, "geometry_group", "geo_group"); wrap(E, "postprocess", "final")
+wrap(eng, "geometry_begin", "geo_begin"); wrap(eng, "geometry_finish", "geo_finish"); wrap(eng, "geometry_group", "geo_group"); wrap(importlib.import_module(PKG + ".runners"), "postprocess", "final")
 def loop(n):
     for i in range(n):
         runner.submit(batches[i % NB], [batches[(i + d) % NB] for d in range(1, runner.depth + 1)])

@@ -258,7 +258,7 @@ def test_host_budget_is_idempotent_after_pinning(monkeypatch):
     monkeypatch.setattr(os, "sched_getaffinity", lambda pid: set(state["aff"]))
     monkeypatch.setattr(os, "sched_setaffinity", lambda pid, cores: state.__setitem__("aff", set(cores)))
     monkeypatch.setattr(os, "cpu_count", lambda: 64)
-    monkeypatch.setattr(E, "_NODE_AFFINITY", None)
+    monkeypatch.setattr(pkg("host"), "_NODE_AFFINITY", None)
     first = E.host_budget(world=4, local_rank=2)
     assert first["cores"] == list(range(32, 48))
     assert E.pin_to_budget(first) and state["aff"] == set(range(32, 48))
@@ -267,7 +267,7 @@ def test_host_budget_is_idempotent_after_pinning(monkeypatch):
         assert again["cores"] == first["cores"] and again["loaders"] == first["loaders"]
         E.pin_to_budget(again)
     # a rank its launcher already confined to a quarter of the node keeps the quarter whole
-    monkeypatch.setattr(E, "_NODE_AFFINITY", None)
+    monkeypatch.setattr(pkg("host"), "_NODE_AFFINITY", None)
     state["aff"] = set(range(16, 32))
     kept = E.host_budget(world=4, local_rank=3)
     assert kept["cores"] == list(range(16, 32))

@@ -560,13 +560,13 @@ def test_fused_final_stage_equals_batched_torch_path():
         cls[4, 10:] = -5.0                                            # scene 4: ten candidates
         ret = {"rois": torch.from_numpy(rois).to(DEV), "rcnn_reg": torch.from_numpy(reg).to(DEV).view(B * M, ch),
                "rcnn_cls": torch.from_numpy(cls).to(DEV).view(B * M, 1)}
-        E.FUSED_POSTPROCESS = True
+        pkg("runners").FUSED_POSTPROCESS = True
         f = E.postprocess(cfg, ret, B)
-        E.FUSED_POSTPROCESS = False
+        pkg("runners").FUSED_POSTPROCESS = False
         try:
             t = E.postprocess(cfg, ret, B)
         finally:
-            E.FUSED_POSTPROCESS = True
+            pkg("runners").FUSED_POSTPROCESS = True
         torch.cuda.synchronize()
         assert (f["pred_boxes3d"] - t["pred_boxes3d"]).abs().max().item() < 1e-5
         assert torch.equal(f["num"], t["num"]), (f["num"], t["num"])
@@ -595,13 +595,13 @@ def test_final_stage_with_every_pair_a_candidate():
     cls[3, 1:] = -6.0                                                              # scene 3: one box
     ret = {"rois": torch.from_numpy(rois).to(DEV), "rcnn_reg": torch.from_numpy(reg).to(DEV).view(B * M, ch),
            "rcnn_cls": torch.from_numpy(cls).to(DEV).view(B * M, 1)}
-    E.FUSED_POSTPROCESS = True
+    pkg("runners").FUSED_POSTPROCESS = True
     f = E.postprocess(cfg, ret, B)
-    E.FUSED_POSTPROCESS = False
+    pkg("runners").FUSED_POSTPROCESS = False
     try:
         t = E.postprocess(cfg, ret, B)
     finally:
-        E.FUSED_POSTPROCESS = True
+        pkg("runners").FUSED_POSTPROCESS = True
     torch.cuda.synchronize()
     assert torch.equal(f["num"], t["num"]), (f["num"], t["num"])
     assert int(f["num"][3]) == 1 and int(f["num"][0]) >= 1 and int(f["num"][1]) <= M // 2

@@ -93,6 +93,42 @@ def test_paired_members_when_the_caller_changes_its_mind():
             assert torch.equal(g[k], w[k]), "submit %d (batch %d): %s" % (n, order[n], k)
 
 
+def test_one_batch_chains_give_the_grouped_chains_detections(monkeypatch):
+    """The eager runner with PRCNN_GEO_GROUP=1 (every batch a geometry chain of its own) against the default group of 4, over six
+    batches -- one full group and a partly filled one: a cloud's geometry does not depend on which chain computed it, so every
+    detection tensor comes out bit for bit, batch by batch."""
+    C = importlib.import_module(PKG + ".config"); E = importlib.import_module(PKG + ".eval_rcnn"); S = importlib.import_module(PKG + ".synth")
+    dev = torch.device("cuda", 0)
+    cfg = C.default_eval_cfg()
+    model = E.build_model(cfg, dev, seed=0)
+    batches = [torch.from_numpy(S.scenes(4, 16384, seed0=100 + 4 * s)).to(dev) for s in range(6)]
+
+    def run(group):
+        if group is None:
+            monkeypatch.delenv("PRCNN_GEO_GROUP", raising=False)
+        else:
+            monkeypatch.setenv("PRCNN_GEO_GROUP", str(group))
+        runner = E.PipelinedRunner(model, cfg, dev)           # (reads the variable in __init__)
+        dets = [runner.submit(b, batches[i + 1:i + 1 + runner.depth]) for i, b in enumerate(batches)]
+        dets = [d for d in dets if d is not None]
+        first = runner.flush()
+        dets += ([first] if first is not None else []) + runner.drain()
+        outs = []
+        for det in dets:
+            with torch.cuda.stream(det["stream"]):
+                outs.append({k: det[k].clone() for k in KEYS})
+        torch.cuda.synchronize()
+        return runner.group, outs
+    g1, single = run(1)
+    g4, grouped = run(None)
+    assert (g1, g4) == (1, 4)
+    assert len(single) == len(grouped) == len(batches)
+    for i, (a, b) in enumerate(zip(single, grouped)):
+        for k in KEYS:
+            assert torch.equal(a[k], b[k]), "batch %d: %s differs between chains of one batch and chains of four" % (i, k)
+    assert sum(int(b["num"].sum()) for b in grouped) > 0
+
+
 def test_scratch_of_a_captured_graph_stays_where_it_is():
     """the C library's per-stream scratch: a larger request on a stream whose graphs point to the old buffer gets a new buffer (the graph
     still replays correctly afterwards), and a request that would have to allocate DURING a capture fails loudly"""

@@ -465,7 +465,7 @@ def test_graph_replay_is_refused_when_the_runtime_switch_came_too_late(monkeypat
     with pytest.raises(RuntimeError, match="DEBUG_CLR_GRAPH_PACKET_CAPTURE"):
         E.GraphedRunner(None, None, "cpu")
     made = []
-    monkeypatch.setattr(E, "PipelinedRunner", lambda *a: made.append(a) or "eager")
+    monkeypatch.setattr(pkg("runners"), "PipelinedRunner", lambda *a: made.append(a) or "eager")
     cfg = pkg("config").default_eval_cfg()
     with warnings.catch_warnings(record=True) as w:
         warnings.simplefilter("always")
