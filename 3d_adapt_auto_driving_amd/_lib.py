@@ -42,6 +42,10 @@ SIGNATURES = {
     "prcnn_set_ball_query_mode": [_I],
     "prcnn_ball_query": [_I, _I, _I, _F, _I, _P, _P, _P, _P],
     "prcnn_fps_new_xyz": [_I, _I, _I, _P, _P, _P, _P],
+    "prcnn_fps_new_xyz_nested": [_I, _I, _I, _P, _P, _P, _P],
+    "prcnn_fps_nested_supported": [_I, _I],
+    "prcnn_fps_prefix_check": [_I, _I, _I, _P, _P, _P, _P, _P],
+    "prcnn_fps_new_xyz_flagged": [_I, _I, _I, _P, _P, _P, _P, _P],
     "prcnn_ball_query_limit": [_I, _I, _I, _F, _I, _P, _P, _P, _P, _P],
     "prcnn_group_points": [_I, _I, _I, _I, _I, _P, _P, _P, _P],
     "prcnn_group_points_grad": [_I, _I, _I, _I, _I, _P, _P, _P, _P],

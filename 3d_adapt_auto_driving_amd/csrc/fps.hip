@@ -177,14 +177,16 @@ struct KeyCodec {
 template <int WAVES, int PPT, bool ORDERED>
 __global__ __launch_bounds__(64 * WAVES) void fps_reg_kernel(
     int n, int m, KeyCodec kc, const float *__restrict__ xyz, float *__restrict__ temp,
-    int *__restrict__ idx, float *__restrict__ new_xyz = nullptr)
+    int *__restrict__ idx, float *__restrict__ new_xyz = nullptr, const int *__restrict__ rejected = nullptr)
 {
     // temp == NULL: the running minima start at the reference caller's fill value (1e10, pointnet2_utils.py:26) and are not
     // handed back; new_xyz != NULL: the selected points' coordinates are written as well (prcnn_fps_new_xyz: the caller's
-    // fill + index cast + gather launches folded into this one)
+    // fill + index cast + gather launches folded into this one); rejected != NULL (prcnn_fps_new_xyz_nested): a cloud whose
+    // entry is 0 passed the prefix check, which wrote its outputs -- nothing to do (one workgroup is one cloud: uniform)
     constexpr int T = 64 * WAVES;
     __shared__ unsigned long long s_best[3];
     const int b = blockIdx.x;
+    if (rejected && rejected[b] == 0) return;
     const float *__restrict__ cloud = xyz + (long)b * n * 3;
     float *__restrict__ mind = temp ? temp + (long)b * n : nullptr;
     int *__restrict__ sel = idx + (long)b * m;
@@ -317,12 +319,14 @@ __device__ __forceinline__ unsigned part1by1(unsigned v)   // spread the low 16 
 
 // perm[b][s] = original index of the s-th point in Morton order of a 64 x 64 grid over the cloud's
 // (x, z) bounding box.  Any permutation is valid for correctness; this one makes tiles compact.
-__global__ __launch_bounds__(1024) void fps_order_kernel(int n, const float *__restrict__ xyz, int *__restrict__ perm)
+__global__ __launch_bounds__(1024) void fps_order_kernel(int n, const float *__restrict__ xyz, int *__restrict__ perm,
+                                                         const int *__restrict__ rejected = nullptr)
 {
     __shared__ int cnt[4096];
     __shared__ float red[4][16];
     __shared__ int wsum[16];
     const int b = blockIdx.x, t = threadIdx.x;
+    if (rejected && rejected[b] == 0) return;                         // (fps_reg_kernel: the cloud's sampling is skipped, nobody reads its order)
     const float *__restrict__ cloud = xyz + (long)b * n * 3;
     float x0 = INFINITY, x1 = -INFINITY, z0 = INFINITY, z1 = -INFINITY;
     for (int k = t; k < n; k += 1024) {
@@ -417,16 +421,18 @@ __device__ __forceinline__ void fs_pick3(const float (&px)[PPT], const float (&p
 template <int PPT>
 __global__ __launch_bounds__(1024) void fps_spec_kernel(
     int n, int m, KeyCodec kc, const float *__restrict__ xyz, const int *__restrict__ perm,
-    float *__restrict__ temp, int *__restrict__ idx, float *__restrict__ new_xyz)
+    float *__restrict__ temp, int *__restrict__ idx, float *__restrict__ new_xyz, const int *__restrict__ rejected = nullptr)
 {
     // temp == NULL: the running minima start at the reference caller's fill value (1e10, pointnet2_utils.py:26) and are not handed back;
-    // new_xyz != NULL: the coordinates of the picks are written as well (prcnn_fps_new_xyz: the caller's gather launch folded in)
+    // new_xyz != NULL: the coordinates of the picks are written as well (prcnn_fps_new_xyz: the caller's gather launch folded in);
+    // rejected: as in fps_reg_kernel
     constexpr int SB = PPT == 16 ? 4 : (PPT == 8 ? 3 : 2);          // slot bits below the tie key
     __shared__ unsigned long long s_vk[32];                          // packed (value, key) of the published entries
     __shared__ float s_xyz[32][3];
     __shared__ float s_bound[16];
     __shared__ int s_rank[32], s_blk[32];                            // per entry: entries that precede it / one of them blocks it
     const int b = blockIdx.x;
+    if (rejected && rejected[b] == 0) return;
     const float *__restrict__ cloud = xyz + (long)b * n * 3;
     const int *__restrict__ order = perm + (long)b * n;
     float *__restrict__ mind = temp ? temp + (long)b * n : nullptr;
@@ -1013,12 +1019,13 @@ static int host_opt_n_threads(int work_size)
 }
 
 template <int WAVES, int PPT>
-static void launch_reg(int b, int n, int m, KeyCodec kc, const float *xyz, float *temp, int *idx, hipStream_t st, float *new_xyz = nullptr)
+static void launch_reg(int b, int n, int m, KeyCodec kc, const float *xyz, float *temp, int *idx, hipStream_t st, float *new_xyz = nullptr,
+                       const int *rejected = nullptr)
 {
     if ((1 << kc.log2bs) == 64 * WAVES)
-        hipLaunchKernelGGL((fps_reg_kernel<WAVES, PPT, true>), dim3(b), dim3(64 * WAVES), 0, st, n, m, kc, xyz, temp, idx, new_xyz);
+        hipLaunchKernelGGL((fps_reg_kernel<WAVES, PPT, true>), dim3(b), dim3(64 * WAVES), 0, st, n, m, kc, xyz, temp, idx, new_xyz, rejected);
     else
-        hipLaunchKernelGGL((fps_reg_kernel<WAVES, PPT, false>), dim3(b), dim3(64 * WAVES), 0, st, n, m, kc, xyz, temp, idx, new_xyz);
+        hipLaunchKernelGGL((fps_reg_kernel<WAVES, PPT, false>), dim3(b), dim3(64 * WAVES), 0, st, n, m, kc, xyz, temp, idx, new_xyz, rejected);
 }
 
 }  // namespace prcnn
@@ -1082,23 +1089,33 @@ static int fps2_capacity(size_t pad)
     return cap;
 }
 
-static int fps_any(int b, int n, int m, const float *xyz, float *temp, int *idx, float *new_xyz, void *stream)
+// The tie-key layout of a cloud of n points: the reference's block size opt_n_threads(n) and the bits of k div bs above it
+static int fps_codec(int n, KeyCodec *kc)
+{
+    const int bs = host_opt_n_threads(n);
+    kc->hipcc = g_fps_hipcc;
+    kc->log2bs = 0;
+    while ((1 << kc->log2bs) < bs) ++kc->log2bs;
+    const int nq = (n + bs - 1) / bs;  // values of k div bs: 0 .. nq-1
+    kc->sh = 0;
+    while ((1 << kc->sh) < nq) ++kc->sh;
+    PRCNN_REQUIRE(kc->sh + kc->log2bs <= 31, "fps: n=%d too large for the 32-bit tie key", n);
+    return PRCNN_OK;
+}
+
+// rejected != NULL (prcnn_fps_new_xyz_nested, n <= 16384): per cloud, 0 = the prefix check accepted it and wrote its outputs, the
+// sampling kernels leave it alone.  Every other caller passes NULL: same launches, same code path as before the check existed.
+static int fps_any(int b, int n, int m, const float *xyz, float *temp, int *idx, float *new_xyz, void *stream, const int *rejected = nullptr)
 {
     PRCNN_REQUIRE(b >= 0 && n >= 0 && m >= 0, "fps: bad sizes b=%d n=%d m=%d", b, n, m);
     if (b == 0 || m == 0) return PRCNN_OK;
     PRCNN_REQUIRE(n > 0, "fps: empty cloud with m=%d", m);
     PRCNN_REQUIRE(xyz && (temp || new_xyz) && idx, "fps: null pointer");
     hipStream_t st = (hipStream_t)stream;
+    PRCNN_REQUIRE(!rejected || n <= 16384, "fps: the skip flags serve n <= 16384 (n=%d)", n);   // never the two-workgroup kernel and its spin
 
-    const int bs = host_opt_n_threads(n);
     KeyCodec kc;
-    kc.hipcc = g_fps_hipcc;
-    kc.log2bs = 0;
-    while ((1 << kc.log2bs) < bs) ++kc.log2bs;
-    const int nq = (n + bs - 1) / bs;  // values of k div bs: 0 .. nq-1
-    kc.sh = 0;
-    while ((1 << kc.sh) < nq) ++kc.sh;
-    PRCNN_REQUIRE(kc.sh + kc.log2bs <= 31, "fps: n=%d too large for the 32-bit tie key", n);
+    if (const int rc = fps_codec(n, &kc)) return rc;
 
     // large clouds: Morton ordering + pruned scan (exact).  It needs (n ints) of scratch per scene and pays
     // off when the sample count is large enough for the pruning radius to shrink.
@@ -1118,8 +1135,8 @@ static int fps_any(int b, int n, int m, const float *xyz, float *temp, int *idx,
             if (!temp) { set_error("fps_new_xyz: cannot allocate the distance scratch"); return PRCNN_ELAUNCH; }
             hipLaunchKernelGGL(fps_fill_kernel, dim3((unsigned)(((long)b * n + 255) / 256)), dim3(256), 0, st, (long)b * n, 1e10f, temp);
         }
-        const int rc = fps_any(b, n, m, xyz, temp, idx, nullptr, stream);
-        if (rc != PRCNN_OK) return rc;
+        const int rc = fps_any(b, n, m, xyz, temp, idx, nullptr, stream, rejected);
+        if (rc != PRCNN_OK) return rc;                                // (the gather serves an accepted cloud too: its idx is 0 .. m-1)
         hipLaunchKernelGGL(fps_gather_xyz_kernel, dim3((unsigned)((long)((m + 255) / 256) * b)), dim3(256), 0, st, n, m, xyz, idx, new_xyz);
         return check_launch("fps_new_xyz(gather)");
     }
@@ -1149,7 +1166,7 @@ static int fps_any(int b, int n, int m, const float *xyz, float *temp, int *idx,
     if (n > 2048 && n <= 16384 && m >= 256) {
         int *perm = (int *)scratch_for(st, (size_t)b * n * sizeof(int), 1);
         if (!perm) { set_error("fps: cannot allocate ordering scratch"); return PRCNN_ELAUNCH; }
-        hipLaunchKernelGGL(fps_order_kernel, dim3(b), dim3(1024), 0, st, n, xyz, perm);
+        hipLaunchKernelGGL(fps_order_kernel, dim3(b), dim3(1024), 0, st, n, xyz, perm, rejected);
         // Unused dynamic LDS as a placement hint: with more than half of a CU's LDS requested, two of these
         // latency-bound 1024-thread workgroups (the chains of two batches run on two streams) never share a CU.
         // (+1.2 % end to end; only when the batch is small enough that one workgroup per CU costs no concurrency)
@@ -1163,19 +1180,19 @@ static int fps_any(int b, int n, int m, const float *xyz, float *temp, int *idx,
                 const int rc = ensure_dynamic_lds(k, pad, "furthest_point_sampling(speculative)");
                 if (rc != PRCNN_OK) return rc;
             }
-        if (n <= 4096) hipLaunchKernelGGL((fps_spec_kernel<4>), dim3(b), dim3(1024), pad, st, n, m, kc, xyz, perm, temp, idx, new_xyz);
-        else if (n <= 8192) hipLaunchKernelGGL((fps_spec_kernel<8>), dim3(b), dim3(1024), pad, st, n, m, kc, xyz, perm, temp, idx, new_xyz);
-        else hipLaunchKernelGGL((fps_spec_kernel<16>), dim3(b), dim3(1024), pad, st, n, m, kc, xyz, perm, temp, idx, new_xyz);
+        if (n <= 4096) hipLaunchKernelGGL((fps_spec_kernel<4>), dim3(b), dim3(1024), pad, st, n, m, kc, xyz, perm, temp, idx, new_xyz, rejected);
+        else if (n <= 8192) hipLaunchKernelGGL((fps_spec_kernel<8>), dim3(b), dim3(1024), pad, st, n, m, kc, xyz, perm, temp, idx, new_xyz, rejected);
+        else hipLaunchKernelGGL((fps_spec_kernel<16>), dim3(b), dim3(1024), pad, st, n, m, kc, xyz, perm, temp, idx, new_xyz, rejected);
         return check_launch("furthest_point_sampling(speculative)");
     }
-    if (n <= 128) launch_reg<1, 2>(b, n, m, kc, xyz, temp, idx, st);
-    else if (n <= 256) launch_reg<1, 4>(b, n, m, kc, xyz, temp, idx, st);
-    else if (n <= 512) launch_reg<1, 8>(b, n, m, kc, xyz, temp, idx, st);
-    else if (n <= 1024 && b >= 128) launch_reg<1, 16>(b, n, m, kc, xyz, temp, idx, st);
-    else if (n <= 1024) launch_reg<4, 4>(b, n, m, kc, xyz, temp, idx, st);
-    else if (n <= 4096) launch_reg<16, 4>(b, n, m, kc, xyz, temp, idx, st);
-    else if (n <= 8192) launch_reg<16, 8>(b, n, m, kc, xyz, temp, idx, st);
-    else if (n <= 16384) launch_reg<16, 16>(b, n, m, kc, xyz, temp, idx, st);
+    if (n <= 128) launch_reg<1, 2>(b, n, m, kc, xyz, temp, idx, st, nullptr, rejected);
+    else if (n <= 256) launch_reg<1, 4>(b, n, m, kc, xyz, temp, idx, st, nullptr, rejected);
+    else if (n <= 512) launch_reg<1, 8>(b, n, m, kc, xyz, temp, idx, st, nullptr, rejected);
+    else if (n <= 1024 && b >= 128) launch_reg<1, 16>(b, n, m, kc, xyz, temp, idx, st, nullptr, rejected);
+    else if (n <= 1024) launch_reg<4, 4>(b, n, m, kc, xyz, temp, idx, st, nullptr, rejected);
+    else if (n <= 4096) launch_reg<16, 4>(b, n, m, kc, xyz, temp, idx, st, nullptr, rejected);
+    else if (n <= 8192) launch_reg<16, 8>(b, n, m, kc, xyz, temp, idx, st, nullptr, rejected);
+    else if (n <= 16384) launch_reg<16, 16>(b, n, m, kc, xyz, temp, idx, st, nullptr, rejected);
     else hipLaunchKernelGGL(fps_generic_kernel, dim3(b), dim3(1024), 0, st, n, m, kc, xyz, temp, idx);
     return check_launch("furthest_point_sampling");
 }
@@ -1190,29 +1207,184 @@ extern "C" int prcnn_furthest_point_sampling(int b, int n, int m, const float *x
 // FPS of many small clouds (n <= 1024: one wave per cloud, everything in registers) with the selected coordinates written
 // alongside the indices: what furthest_point_sample + gather_operation (pointnet2_modules.py:40-46) produce, without the
 // caller's 1e10 fill of the distance scratch, the index cast and the gather launch.  idx (b,m), new_xyz (b,m,3).
+static int fps_new_xyz_any(int b, int n, int m, const float *xyz, int *idx, float *new_xyz, void *stream, const int *rejected)
+{
+    if (n > 1024) return fps_any(b, n, m, xyz, nullptr, idx, new_xyz, stream, rejected);      // round 4: the speculative kernel writes them too
+    hipStream_t st = (hipStream_t)stream;
+    KeyCodec kc;
+    if (const int rc = fps_codec(n, &kc)) return rc;
+    if (n <= 128) launch_reg<1, 2>(b, n, m, kc, xyz, nullptr, idx, st, new_xyz, rejected);
+    else if (n <= 256) launch_reg<1, 4>(b, n, m, kc, xyz, nullptr, idx, st, new_xyz, rejected);
+    else if (n <= 512) launch_reg<1, 8>(b, n, m, kc, xyz, nullptr, idx, st, new_xyz, rejected);
+    else if (b >= 128) launch_reg<1, 16>(b, n, m, kc, xyz, nullptr, idx, st, new_xyz, rejected);
+    else launch_reg<4, 4>(b, n, m, kc, xyz, nullptr, idx, st, new_xyz, rejected);   // few clouds: four waves each (as prcnn_furthest_point_sampling)
+    return check_launch("fps_new_xyz");
+}
+
 extern "C" int prcnn_fps_new_xyz(int b, int n, int m, const float *xyz, int *idx, float *new_xyz, void *stream)
 {
     PRCNN_REQUIRE(b >= 0 && n > 0 && m >= 0, "fps_new_xyz: b=%d n=%d m=%d", b, n, m);
     if (b == 0 || m == 0) return PRCNN_OK;
     PRCNN_REQUIRE(xyz && idx && new_xyz, "fps_new_xyz: null pointer");
-    if (n > 1024) return fps_any(b, n, m, xyz, nullptr, idx, new_xyz, stream);      // round 4: the speculative kernel writes them too
-    hipStream_t st = (hipStream_t)stream;
-    const int bs = host_opt_n_threads(n);
-    KeyCodec kc;
-    kc.hipcc = g_fps_hipcc;
-    kc.log2bs = 0;
-    while ((1 << kc.log2bs) < bs) ++kc.log2bs;
-    const int nq = (n + bs - 1) / bs;
-    kc.sh = 0;
-    while ((1 << kc.sh) < nq) ++kc.sh;
-    if (n <= 128) launch_reg<1, 2>(b, n, m, kc, xyz, nullptr, idx, st, new_xyz);
-    else if (n <= 256) launch_reg<1, 4>(b, n, m, kc, xyz, nullptr, idx, st, new_xyz);
-    else if (n <= 512) launch_reg<1, 8>(b, n, m, kc, xyz, nullptr, idx, st, new_xyz);
-    else if (b >= 128) launch_reg<1, 16>(b, n, m, kc, xyz, nullptr, idx, st, new_xyz);
-    else launch_reg<4, 4>(b, n, m, kc, xyz, nullptr, idx, st, new_xyz);             // few clouds: four waves each (as prcnn_furthest_point_sampling)
-    return check_launch("fps_new_xyz");
+    return fps_new_xyz_any(b, n, m, xyz, idx, new_xyz, stream, nullptr);
 }
 
+namespace prcnn {
+// ---- nested sampling: is the answer the prefix?  (prcnn_fps_new_xyz_nested) ------------------------------------------------
+// The RPN backbone samples 16384 -> 4096 -> 1024 -> 256 -> 64, every level from the previous level's new_xyz: the previous picks in
+// pick order.  FPS is a greedy arg-max, so it is prefix-consistent: pick s of the outer run is the arg-max of the running minima over
+// the whole outer cloud, it lies in the inner cloud P[0..n) (the first n picks), so it is the arg-max over P as well -- computed from
+// the same coordinates, the same fps_dist and the same pivots in the same order.  By induction the inner run picks 0, 1, ..., m-1.
+// The one way this fails is an exact tie at a maximum: the tie key depends on n and on a point's position, so the inner run may break
+// a tie differently (an integer lattice does).  Whether a cloud's answer IS the prefix has no dependent chain and is checked in
+// parallel, n * m distance evaluations.  With T_s[j] = min(1e10, min_{i < s} fps_dist(P[j], P[i])) and D[s] = T_s[s] the sampling
+// kernels pick s at step s, for every s in 1 .. m-1, if and only if
+//     D[s] > 0                                                       (beats the picked points and their copies, T = 0, and the -1 start)
+//     for every j > s:  D[s] > T_s[j],  or  D[s] == T_s[j] and encode(s) < encode(j)     (the kernels' total order: better())
+// -- every condition a positive comparison, and every coordinate finite, so a NaN or an infinity rejects.  An accepted cloud's
+// outputs are idx = 0 .. m-1 and new_xyz = P[0..m): fps_prefix_pivots_kernel writes them for EVERY cloud, the sampling kernels skip
+// the accepted clouds and overwrite the rejected ones.  Two launches:
+//   fps_prefix_pivots_kernel   D[s] into scratch: a workgroup per 64 pivots, its four waves split the i < s range, pivots from LDS
+//   fps_prefix_check_kernel    a thread per point j walks s = 1 .. min(j, m) - 1 with its running minimum against D[s]; pivots and
+//                              D staged in LDS 256 at a time; a workgroup leaves as soon as the cloud is known to be rejected
+// ---------------------------------------------------------------------------------------------------------------------------------
+constexpr int FPX_T = 256;                                            // threads of both kernels = pivots staged per pass
+
+template <bool HIPCC>
+__global__ __launch_bounds__(FPX_T) void fps_prefix_pivots_kernel(int n, int m, const float *__restrict__ xyz, float *__restrict__ dpiv,
+                                                                  int *__restrict__ rejected, int *__restrict__ idx, float *__restrict__ new_xyz)
+{
+    __shared__ float s_p[FPX_T][3];
+    __shared__ float s_part[4][64];
+    const int b = blockIdx.y, t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const float *__restrict__ cloud = xyz + (long)b * n * 3;
+    if (blockIdx.x == 0 && t == 0) rejected[b] = 0;                   // the flag's reset, on-stream in front of the check
+    const int s = blockIdx.x * 64 + lane;                             // this lane's pivot (the four waves hold the same 64)
+    const int sc = min(s, m - 1);
+    const float x = cloud[3 * sc], y = cloud[3 * sc + 1], z = cloud[3 * sc + 2];
+    const int iend = min(blockIdx.x * 64 + 63, m - 1);                // i < s <= iend
+    float d = 1e10f;                                                  // the reference caller's fill value (pointnet2_utils.py:26)
+    for (int i0 = 0; i0 < iend; i0 += FPX_T) {
+        __syncthreads();
+        if (i0 + t < iend) { s_p[t][0] = cloud[3 * (i0 + t)]; s_p[t][1] = cloud[3 * (i0 + t) + 1]; s_p[t][2] = cloud[3 * (i0 + t) + 2]; }
+        __syncthreads();
+        const int k1 = min(64, iend - i0 - 64 * w);
+#pragma unroll 4
+        for (int k = 0; k < k1; ++k) {
+            const int q = 64 * w + k;
+            const float e = fps_dist<HIPCC>(x, y, z, s_p[q][0], s_p[q][1], s_p[q][2]);
+            d = (i0 + q < s) ? fminf(e, d) : d;                       // min(d, temp[k]) of sampling_gpu.cu:134
+        }
+    }
+    s_part[w][lane] = d;
+    __syncthreads();
+    if (w == 0 && s < m) {
+        dpiv[(long)b * m + s] = fminf(fminf(s_part[0][lane], s_part[1][lane]), fminf(s_part[2][lane], s_part[3][lane]));
+        if (idx) idx[(long)b * m + s] = s;
+        if (new_xyz) { float *o = new_xyz + ((long)b * m + s) * 3; o[0] = x; o[1] = y; o[2] = z; }
+    }
+}
+
+template <bool HIPCC>
+__global__ __launch_bounds__(FPX_T) void fps_prefix_check_kernel(int n, int m, KeyCodec kc, const float *__restrict__ xyz,
+                                                                 const float *__restrict__ dpiv, int *__restrict__ rejected)
+{
+    __shared__ float4 s_p[FPX_T];                                     // (P[i], D[i + 1]): step s = i + 1 compares D[s] with the minimum over i < s
+    const int b = blockIdx.y, t = threadIdx.x;
+    const float *__restrict__ cloud = xyz + (long)b * n * 3;
+    const float *__restrict__ D = dpiv + (long)b * m;
+    const int j = blockIdx.x * FPX_T + t, jc = min(j, n - 1);         // (a thread beyond the cloud repeats point n-1: same verdict)
+    const float x = cloud[3 * jc], y = cloud[3 * jc + 1], z = cloud[3 * jc + 2];
+    const uint32_t kj = kc.encode(jc);
+    bool ok = fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY;
+    if (jc >= 1 && jc < m) ok &= D[jc] > 0.f;
+    const int jmax = min(n, (int)(blockIdx.x + 1) * FPX_T) - 1;       // the block's last point: steps s <= min(m, jmax) - 1
+    const int iend = min(m, jmax) - 1;                                // pivots i = s - 1 < iend
+    float r = 1e10f;
+    for (int i0 = 0; ; i0 += FPX_T) {
+        // uniform exit: somebody (this workgroup or another one of the cloud) has rejected -- or the walk is over
+        const int seen = __hip_atomic_load(rejected + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (__syncthreads_or(!ok || seen != 0) || i0 >= iend) break;
+        if (i0 + t < iend) {
+            const int i = i0 + t;
+            s_p[t] = make_float4(cloud[3 * i], cloud[3 * i + 1], cloud[3 * i + 2], D[i + 1]);
+        }
+        __syncthreads();
+        const int k1 = min(FPX_T, iend - i0);
+#pragma unroll 4
+        for (int k = 0; k < k1; ++k) {
+            const float4 p = s_p[k];
+            const int s = i0 + k + 1;
+            r = fminf(fps_dist<HIPCC>(x, y, z, p.x, p.y, p.z), r);
+            bool win = p.w > r;
+            if (p.w == r) win = kc.encode(s) < kj;                    // an exact tie (rare): the kernels' key order decides
+            ok = ok && (win || s >= jc);
+        }
+    }
+    if (!ok) rejected[b] = 1;
+}
+}  // namespace prcnn
+
+// the shapes the check serves (everything else goes to prcnn_fps_new_xyz as it is): a pick to decide, the sampling kernels that take the flag
+extern "C" int prcnn_fps_nested_supported(int n, int m) { return m >= 2 && m <= n && n <= 16384; }
+
+static int fps_prefix_any(int b, int n, int m, const KeyCodec &kc, const float *xyz, int *idx, float *new_xyz, float *dpiv, int *rejected,
+                          hipStream_t st)
+{
+    const dim3 g1((unsigned)((m + 63) / 64), (unsigned)b), g2((unsigned)((n + FPX_T - 1) / FPX_T), (unsigned)b);
+    if (kc.hipcc) {
+        hipLaunchKernelGGL(fps_prefix_pivots_kernel<true>, g1, dim3(FPX_T), 0, st, n, m, xyz, dpiv, rejected, idx, new_xyz);
+        hipLaunchKernelGGL(fps_prefix_check_kernel<true>, g2, dim3(FPX_T), 0, st, n, m, kc, xyz, dpiv, rejected);
+    } else {
+        hipLaunchKernelGGL(fps_prefix_pivots_kernel<false>, g1, dim3(FPX_T), 0, st, n, m, xyz, dpiv, rejected, idx, new_xyz);
+        hipLaunchKernelGGL(fps_prefix_check_kernel<false>, g2, dim3(FPX_T), 0, st, n, m, kc, xyz, dpiv, rejected);
+    }
+    return check_launch("fps_prefix_check");
+}
+
+// The check alone (tests, profiles/fps_nested_probe.py: the acceptance rate): rejected (b) <- 0 where sampling m of the cloud's n points
+// returns 0 .. m-1, 1 where it may not; idx / new_xyz (NULL: not wanted) <- the prefix, for every cloud.
+extern "C" int prcnn_fps_prefix_check(int b, int n, int m, const float *xyz, int *idx, float *new_xyz, int *rejected, void *stream)
+{
+    PRCNN_REQUIRE(b >= 0 && b <= 65535 && prcnn_fps_nested_supported(n, m), "fps_prefix_check: b=%d n=%d m=%d", b, n, m);
+    if (b == 0) return PRCNN_OK;
+    PRCNN_REQUIRE(xyz && rejected, "fps_prefix_check: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    KeyCodec kc;
+    if (const int rc = fps_codec(n, &kc)) return rc;
+    float *dpiv = (float *)scratch_for(st, (size_t)b * m * sizeof(float), 15);
+    if (!dpiv) { set_error("fps_prefix_check: cannot allocate the pivot scratch"); return PRCNN_ELAUNCH; }
+    return fps_prefix_any(b, n, m, kc, xyz, idx, new_xyz, dpiv, rejected, st);
+}
+
+// The sampling launches of prcnn_fps_new_xyz_nested WITHOUT its check, under a verdict the caller made up (tests: a cloud whose entry
+// is 0 must come back untouched, whatever it holds; one whose entry is not 0 sampled as by prcnn_fps_new_xyz).  rejected (b) on the device.
+extern "C" int prcnn_fps_new_xyz_flagged(int b, int n, int m, const float *xyz, int *idx, float *new_xyz, const int *rejected, void *stream)
+{
+    PRCNN_REQUIRE(b >= 0 && prcnn_fps_nested_supported(n, m), "fps_new_xyz_flagged: b=%d n=%d m=%d", b, n, m);
+    if (b == 0) return PRCNN_OK;
+    PRCNN_REQUIRE(xyz && idx && new_xyz && rejected, "fps_new_xyz_flagged: null pointer");
+    return fps_new_xyz_any(b, n, m, xyz, idx, new_xyz, stream, rejected);
+}
+
+// prcnn_fps_new_xyz for a caller that EXPECTS the prefix (xyz is an earlier sampling's new_xyz): same outputs for any input -- the
+// check decides per cloud, the hint only says that running it is worth its n * m evaluations.  No allocation or host synchronisation
+// once the stream's scratch exists: capturable like the plain entry.
+extern "C" int prcnn_fps_new_xyz_nested(int b, int n, int m, const float *xyz, int *idx, float *new_xyz, void *stream)
+{
+    PRCNN_REQUIRE(b >= 0 && n > 0 && m >= 0, "fps_new_xyz_nested: b=%d n=%d m=%d", b, n, m);
+    if (b == 0 || m == 0) return PRCNN_OK;
+    PRCNN_REQUIRE(xyz && idx && new_xyz, "fps_new_xyz_nested: null pointer");
+    if (!prcnn_fps_nested_supported(n, m) || b > 65535) return fps_new_xyz_any(b, n, m, xyz, idx, new_xyz, stream, nullptr);
+    hipStream_t st = (hipStream_t)stream;
+    KeyCodec kc;
+    if (const int rc = fps_codec(n, &kc)) return rc;
+    float *dpiv = (float *)scratch_for(st, ((size_t)b * m + (size_t)b) * sizeof(float), 15);     // D (b, m), then the flags (b)
+    if (!dpiv) { set_error("fps_new_xyz_nested: cannot allocate the check's scratch"); return PRCNN_ELAUNCH; }
+    int *rejected = (int *)(dpiv + (size_t)b * m);
+    if (const int rc = fps_prefix_any(b, n, m, kc, xyz, idx, new_xyz, dpiv, rejected, st)) return rc;
+    return fps_new_xyz_any(b, n, m, xyz, idx, new_xyz, stream, rejected);
+}
 // ---- spatial groups of a cloud for the consumers that sweep it per box (csrc/roipool.hip) -------------------------------------
 // The cloud in the Morton order of fps_order_kernel, 64 points per group: pxyz (b, n) float4 = (x, y, z, original index as bits),
 // aabb (b, n / 64, 2) float4 = per-group (min x, min y, min z, -) and (max x, max y, max z, -).  A box then tests 256 group boxes

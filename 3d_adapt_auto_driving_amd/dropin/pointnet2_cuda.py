@@ -60,15 +60,56 @@ def point_aux_wrapper(scores, xyz, thresh, seg, depth, depth_norm):
               depth_norm.data_ptr(), _lib.current_stream(xyz))
 
 
+class PrefixExpected(int):
+    """A sample count that carries the caller's hint "xyz is an earlier sampling's new_xyz: expect the picks 0 .. m-1".
+    fps_new_xyz_wrapper(xyz, PrefixExpected(m)) is fps_new_xyz_nested_wrapper(xyz, m).  The hint rides on the count so that the
+    nested levels stay calls of fps_new_xyz_wrapper with its two arguments: a proxy around this module that counts the sampling
+    calls and checks each against a CPU stand-in (tests/test_gpu_shadow.py) sees and checks them like any other."""
+    __slots__ = ()
+
+
 def fps_new_xyz_wrapper(xyz, m):
     """xyz (b,n,3) -> (idx (b,m) i32, new_xyz (b,m,3)): furthest_point_sampling_wrapper + the gather of the selected
-    coordinates in one launch (csrc/fps.hip); shapes: fps_new_xyz_supported."""
+    coordinates in one launch (csrc/fps.hip); shapes: fps_new_xyz_supported.  m a PrefixExpected: through the prefix check."""
     _chk(torch.float32, xyz)
     b, n, _ = xyz.shape
+    entry = "prcnn_fps_new_xyz_nested" if isinstance(m, PrefixExpected) else "prcnn_fps_new_xyz"
+    m = int(m)
     idx = torch.empty((b, m), dtype=torch.int32, device=xyz.device)
     new_xyz = torch.empty((b, m, 3), dtype=torch.float32, device=xyz.device)
-    _lib.call("prcnn_fps_new_xyz", b, n, m, xyz.data_ptr(), idx.data_ptr(), new_xyz.data_ptr(), _lib.current_stream(xyz))
+    _lib.call(entry, b, n, m, xyz.data_ptr(), idx.data_ptr(), new_xyz.data_ptr(), _lib.current_stream(xyz))
     return idx, new_xyz
+
+
+def fps_new_xyz_nested_supported(n, m):
+    """does prcnn_fps_new_xyz_nested run its check at this shape (2 <= m <= n <= 16384)?  Other shapes take the plain entry inside."""
+    return bool(_lib.call("prcnn_fps_nested_supported", n, m))
+
+
+def fps_new_xyz_nested_wrapper(xyz, m):
+    """fps_new_xyz_wrapper for an xyz that is an earlier sampling's new_xyz (the picks in pick order): the same outputs for ANY
+    input; where a cloud's answer is the prefix 0 .. m-1 -- checked per cloud on the GPU, exact ties at a maximum are the only
+    way it is not -- the dependent pick loop is skipped (csrc/fps.hip: fps_prefix_check_kernel)."""
+    return fps_new_xyz_wrapper(xyz, PrefixExpected(m))
+
+
+def fps_new_xyz_flagged_wrapper(xyz, m, rejected, idx, new_xyz):
+    """the sampling launches of the nested entry under a caller-made verdict (test hook): clouds with rejected == 0 keep what idx /
+    new_xyz hold, the others are sampled as by fps_new_xyz_wrapper"""
+    _chk(torch.float32, xyz, new_xyz); _chk(torch.int32, rejected, idx)
+    b, n, _ = xyz.shape
+    _lib.call("prcnn_fps_new_xyz_flagged", b, n, int(m), xyz.data_ptr(), idx.data_ptr(), new_xyz.data_ptr(), rejected.data_ptr(),
+              _lib.current_stream(xyz))
+
+
+def fps_prefix_check_wrapper(xyz, m):
+    """xyz (b,n,3) -> rejected (b,) i32: 0 where sampling m points of the cloud returns 0 .. m-1 (the check of the nested entry
+    alone: tests, profiles/fps_nested_probe.py)"""
+    _chk(torch.float32, xyz)
+    b, n, _ = xyz.shape
+    rejected = torch.empty((b,), dtype=torch.int32, device=xyz.device)
+    _lib.call("prcnn_fps_prefix_check", b, n, int(m), xyz.data_ptr(), None, None, rejected.data_ptr(), _lib.current_stream(xyz))
+    return rejected
 
 
 def ball_query_limit_wrapper(b, n, m, radius, nsample, new_xyz, xyz, limit, idx):

@@ -39,6 +39,10 @@ USE_PACKED = os.environ.get("PRCNN_NO_PACK") is None
 # RoI pooling fills a box holding fewer than 512 points by repeating them (roipool3d_kernel.cu:152-159): the per-point
 # RCNN entrance chain and SA1 run over the DISTINCT pooled points only (bit-identical results).  PRCNN_NO_POOL_DEDUP=1: A/B.
 USE_POOL_DEDUP = os.environ.get("PRCNN_NO_POOL_DEDUP") is None
+# SA levels 1.. sample the previous level's picks in pick order: the answer is the prefix 0 .. m-1 unless an exact tie interferes, which
+# the library checks per cloud instead of running the dependent pick loop (csrc/fps.hip, prcnn_fps_new_xyz_nested; same results).
+# PRCNN_NESTED_FPS = the largest cloud (points) that is sampled that way; 0: the plain sampling call at every level.
+NESTED_FPS_MAX_N = int(os.environ.get("PRCNN_NESTED_FPS", "4096"))
 USE_POINT_LAYER = os.environ.get("PRCNN_LIB_GEMM") is None     # per-point layers (FP modules, heads) on the own MFMA layer kernel
 # every per-point width zero-padded to a multiple of 128 (SA level outputs, FP inputs, narrow head outputs), so that NO layer
 # of the engine is left to a GEMM library: fixed summation order everywhere, reproduced bit for bit by the oracle
@@ -463,7 +467,16 @@ class FastPointRCNN:
         cur = state["l_xyz"][-1]
         ext = pu.pointnet2
         if has_entry(ext, "fps_new_xyz_wrapper") and has_entry(ext, "fps_new_xyz_supported") and ext.fps_new_xyz_supported(cur.shape[1], npoint):
-            sel, new_xyz = ext.fps_new_xyz_wrapper(cur, npoint)        # sampling + the centres' coordinates, one launch (round 4: every level)
+            # sampling + the centres' coordinates, one launch (round 4: every level); level k >= 1 samples level k-1's centres, which
+            # are in pick order: prcnn_fps_new_xyz_nested (same outputs, the pick loop only for the clouds that fail the prefix check).
+            # NOTE the form of the call: ext.PrefixExpected(npoint) IS an int, and fps_new_xyz_wrapper(cur, PrefixExpected(m)) is
+            # exactly fps_new_xyz_nested_wrapper(cur, m) (dropin/pointnet2_cuda.py) -- the hint rides on the count so that every level's
+            # sampling stays ONE kind of call for the proxies that count and shadow-check them (tests/test_gpu_shadow.py: four
+            # fps_new_xyz_wrapper calls per step, each compared with the CPU stand-in).  int(m) drops the hint: never convert it on
+            # the way (tests/test_gpu_fps_nested.py::test_engine_takes_the_nested_entry counts the C entries the engine reaches).
+            nested = (k >= 1 and cur.shape[1] <= NESTED_FPS_MAX_N and has_entry(ext, "fps_new_xyz_nested_wrapper")
+                      and ext.fps_new_xyz_nested_supported(cur.shape[1], npoint))
+            sel, new_xyz = ext.fps_new_xyz_wrapper(cur, ext.PrefixExpected(npoint) if nested else npoint)
         else:
             sel = pu.furthest_point_sample(cur, npoint)
             new_xyz = torch.gather(cur, 1, sel.long().unsqueeze(-1).expand(-1, -1, 3)).contiguous()

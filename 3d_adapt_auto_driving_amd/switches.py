@@ -31,6 +31,7 @@ SWITCHES = {
     "PRCNN_LOADER_CONTEXT": ("operational", "forkserver/fork", "eval_rcnn.py", "multiprocessing start method of loaders and writers"),
     "PRCNN_NO_AFFINITY": ("operational", "unset", "host.py", "1: do not pin a rank to its share of the host cores"),
     "PRCNN_RESULT_LAG": ("operational", "3", "eval_rcnn.py", "batches between submitting a batch and reading its detections on the host"),
+    "PRCNN_NESTED_FPS": ("operational", "4096", "net/fast_infer.py", "largest cloud (points) among SA levels 1.. of the RPN backbone that is sampled through prcnn_fps_new_xyz_nested (per-cloud prefix check, the pick loop only for the clouds that fail it) instead of prcnn_fps_new_xyz; 0: none, 1024: the two small levels only.  Same results bit for bit at every value (`tests/test_gpu_fps_nested.py`); it is listed here and not as an A/B switch because its value is a size: a deployment whose clouds hold exact ties (lattices, quantised coordinates: every cloud rejected, the check pure overhead) sets 0"),
     "PRCNN_GRAPHS_FORCE": ("debug", "unset", "__init__.py", "1: replay graphs although DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 was not in place (profiles/graph_fault_probe.py)"),
     "PRCNN_GRAPH_DEBUG": ("debug", "0", "runners.py", "bit mask: device syncs + prints around the graph replays"),
     # ---- numerics
@@ -87,6 +88,7 @@ def table():
     held = {"ab": "`tests/test_gpu_switches.py::test_each_ab_switch_gives_the_same_detections` (bit for bit)",
             "numerics": "`tests/test_gpu_switches.py::test_numerics_switches_stay_inside_the_box_tolerance` (boxes within 1e-4)"}
     special = {"PRCNN_ALLOW_LIB_GEMM": "set together with the GEMM-library switches in the numerics test",
+               "PRCNN_NESTED_FPS": "`tests/test_gpu_fps_nested.py::test_engine_detections_do_not_depend_on_the_nested_route` (bit for bit)",
                "PRCNN_FPS2_CAPACITY": "`tests/test_gpu_ops.py::test_fps_two_workgroups_respects_the_co_resident_capacity`",
                "PRCNN_BENCH_SHARE_GPU": "`tests/test_gpu_configs.py::test_bench_two_ranks_on_one_gpu_...`, `::test_bench_eight_ranks_on_one_gpu`",
                "PRCNN_GRAPHS": "`tests/test_gpu_graphs.py` (replay == eager enqueue, bit for bit); every child of the switch tests runs with 0"}

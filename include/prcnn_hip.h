@@ -102,6 +102,24 @@ int prcnn_set_fps_arithmetic(int mode);
  * tie rule as prcnn_furthest_point_sampling. */
 int prcnn_fps_new_xyz(int b, int n, int m, const float *xyz, int *idx, float *new_xyz, void *stream);
 
+/* prcnn_fps_new_xyz for a caller that expects the answer to be the prefix 0 .. m-1: xyz is the new_xyz of an earlier sampling of a
+ * larger cloud (its picks in pick order), as at every level but the first of a set-abstraction pyramid.  Furthest point sampling is a
+ * greedy arg-max, hence prefix-consistent up to exact ties at a maximum; the library checks that per cloud in parallel (n * m distance
+ * evaluations, no dependent chain), writes the prefix for the clouds that pass and runs the sampling kernels for the others in the
+ * same launches.  SAME outputs as prcnn_fps_new_xyz for ANY input -- the hint only says the check is worth running.  Shapes outside
+ * prcnn_fps_nested_supported (1: 2 <= m <= n <= 16384) go to prcnn_fps_new_xyz unchanged. */
+int prcnn_fps_new_xyz_nested(int b, int n, int m, const float *xyz, int *idx, float *new_xyz, void *stream);
+int prcnn_fps_nested_supported(int n, int m);
+/* The check alone: rejected (b) <- 0 where sampling m of the cloud's n points returns 0 .. m-1 (decided with the arithmetic of
+ * prcnn_set_fps_arithmetic and the tie order of prcnn_furthest_point_sampling), 1 where it may not; idx (b,m) / new_xyz (b,m,3), each
+ * NULL or written with the prefix for every cloud.  b <= 65535, shapes: prcnn_fps_nested_supported. */
+int prcnn_fps_prefix_check(int b, int n, int m, const float *xyz, int *idx, float *new_xyz, int *rejected, void *stream);
+/* The sampling launches of prcnn_fps_new_xyz_nested alone, under a caller-made verdict (a test hook): clouds with rejected[c] == 0 are
+ * left untouched in idx / new_xyz, the others are sampled as by prcnn_fps_new_xyz.  Shapes: prcnn_fps_nested_supported.  Where the
+ * coordinates are gathered behind the sampling (n > 1024 outside the speculative kernel's range) a skipped cloud's idx must hold valid
+ * indices: its new_xyz is gathered from them. */
+int prcnn_fps_new_xyz_flagged(int b, int n, int m, const float *xyz, int *idx, float *new_xyz, const int *rejected, void *stream);
+
 /* three_nn_wrapper_fast  src/interpolate.cpp:14-23 -> src/interpolate_gpu.cu:9-52.
  * unknown (b,n,3), known (b,m,3) -> dist2 (b,n,3) SQUARED distances, idx (b,n,3). */
 int prcnn_three_nn(int b, int n, int m, const float *unknown, const float *known,
