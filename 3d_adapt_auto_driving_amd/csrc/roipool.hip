@@ -88,7 +88,7 @@ __device__ __forceinline__ int select_points(int pts_num, int sampled, const flo
     return min(total, sampled);
 }
 
-// The same selection through the spatial groups of prcnn_point_groups (csrc/fps.hip): 256 group boxes are tested against the
+// The same selection through the spatial groups of prcnn_point_groups (csrc/point_groups.hip): 256 group boxes are tested against the
 // box's footprint (conservatively: circumscribed square in x / z, the y slab, 1 mm of slack for the f32 rounding of either
 // side), the points of the groups that remain go through the SAME pt_in_box3d arithmetic, and the hits are sorted by original
 // index -- what the index-order sweep produces.  Returns -1 when more than `cap` points are inside (a scene-sized box): the

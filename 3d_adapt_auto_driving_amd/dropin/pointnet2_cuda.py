@@ -89,7 +89,7 @@ def fps_new_xyz_nested_supported(n, m):
 def fps_new_xyz_nested_wrapper(xyz, m):
     """fps_new_xyz_wrapper for an xyz that is an earlier sampling's new_xyz (the picks in pick order): the same outputs for ANY
     input; where a cloud's answer is the prefix 0 .. m-1 -- checked per cloud on the GPU, exact ties at a maximum are the only
-    way it is not -- the dependent pick loop is skipped (csrc/fps.hip: fps_prefix_check_kernel)."""
+    way it is not -- the dependent pick loop is skipped (csrc/fps_prefix.hip: fps_prefix_check_kernel)."""
     return fps_new_xyz_wrapper(xyz, PrefixExpected(m))
 
 

@@ -40,7 +40,7 @@ USE_PACKED = os.environ.get("PRCNN_NO_PACK") is None
 # RCNN entrance chain and SA1 run over the DISTINCT pooled points only (bit-identical results).  PRCNN_NO_POOL_DEDUP=1: A/B.
 USE_POOL_DEDUP = os.environ.get("PRCNN_NO_POOL_DEDUP") is None
 # SA levels 1.. sample the previous level's picks in pick order: the answer is the prefix 0 .. m-1 unless an exact tie interferes, which
-# the library checks per cloud instead of running the dependent pick loop (csrc/fps.hip, prcnn_fps_new_xyz_nested; same results).
+# the library checks per cloud instead of running the dependent pick loop (csrc/fps_prefix.hip, prcnn_fps_new_xyz_nested; same results).
 # PRCNN_NESTED_FPS = the largest cloud (points) that is sampled that way; 0: the plain sampling call at every level.
 NESTED_FPS_MAX_N = int(os.environ.get("PRCNN_NESTED_FPS", "4096"))
 USE_POINT_LAYER = os.environ.get("PRCNN_LIB_GEMM") is None     # per-point layers (FP modules, heads) on the own MFMA layer kernel
@@ -577,7 +577,7 @@ class FastPointRCNN:
         return out
 
     def _point_groups(self, xyz):
-        """Spatial groups of the input clouds for the RCNN's RoI pooling (csrc/fps.hip prcnn_point_groups): xyz only, so they
+        """Spatial groups of the input clouds for the RCNN's RoI pooling (csrc/point_groups.hip prcnn_point_groups): xyz only, so they
         ride with the geometry chain on its side stream."""
         rp = roipool3d_utils.roipool3d_cuda
         if not (self.cfg.RCNN.ENABLED and has_entry(rp, "point_groups") and xyz.shape[1] % 64 == 0 and xyz.shape[1] <= 65536):
@@ -1072,7 +1072,7 @@ class FastPointRCNN:
         # either (prcnn_ball_pack_rep; round 3: 7.5x fewer SA2 rows on LiDAR-shaped scenes, bit-identical results).
         centre_dedup = bool(pooled_cnt is not None and point_mlp and has_entry(ext, "dup_rep_wrapper"))
         rep = None
-        # The two sampled levels' geometry for every RoI cloud in ONE launch (a wave per RoI: csrc/fps.hip rcnn_roi_geometry_kernel)
+        # The two sampled levels' geometry for every RoI cloud in ONE launch (a wave per RoI: csrc/roi_geometry.hip rcnn_roi_geometry_kernel)
         # instead of FPS, ball query, representative map -- twice -- as six latency-bound launches; and both levels' row lists written by
         # the wave that holds the hit lists (no pack launches for these levels)
         fused_geo = None

@@ -235,7 +235,7 @@ int prcnn_ball_pack_rep(int b, int n, int m, int nsample, const int *idx, const 
  * same source as sampled point j. */
 int prcnn_dup_rep(int b, int n, int m, const int *sel, const int *limit, const int *prev, int *rep, void *stream);
 
-/* The whole geometry chain of the RCNN's RoI clouds in ONE launch, a wave per RoI (csrc/fps.hip, round 3): xyz (b,512,3) pooled
+/* The whole geometry chain of the RCNN's RoI clouds in ONE launch, a wave per RoI (csrc/roi_geometry.hip, round 3): xyz (b,512,3) pooled
  * coordinates whose points k >= limit[cloud] are copies of point k % limit[cloud] ->
  *   new_xyz1 (b,128,3), idx1 (b,128,ns1), rep1 (b,128)  = prcnn_fps_new_xyz(128), prcnn_ball_query_limit(r1, ns1), prcnn_dup_rep(limit)
  *   new_xyz2 (b,32,3),  idx2 (b,32,ns2),  rep2 (b,32)   = the same one level up over the 128 centres: prcnn_fps_new_xyz(32),
@@ -245,7 +245,7 @@ int prcnn_dup_rep(int b, int n, int m, const int *sel, const int *limit, const i
 int prcnn_rcnn_roi_geometry(int b, int n, int m1, float r1, int ns1, int m2, float r2, int ns2, const float *xyz,
                             const int *limit, float *new_xyz1, int *idx1, int *rep1, float *new_xyz2, int *idx2, int *rep2,
                             void *stream);
-/* ... and the distinct-row lists of both levels out of the same launch (round 5; csrc/fps.hip roi_pack_out): what
+/* ... and the distinct-row lists of both levels out of the same launch (round 5; csrc/roi_geometry.hip roi_pack_out): what
  *   prcnn_ball_pack_ex(b, b, 512, 128, ns1, idx1, limit, NULL, rep1, xyz, new_xyz1, rowinfo1, rowdxyz1, tilecloud1, hdr1, ...) and
  *   prcnn_ball_pack_ex(b, b, 128, 32, ns2, idx2, NULL, rep1, rep2, new_xyz1, new_xyz2, rowinfo2, rowdxyz2, tilecloud2, hdr2, ...)
  * write -- every cloud's rows in the same order, cut into the same tiles; the order of the clouds' tiles inside a list is whatever

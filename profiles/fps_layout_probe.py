@@ -1,4 +1,4 @@
-"""fps_spec_kernel under an experiment switch (PRCNN_FPS_LAYOUT, PRCNN_FPS_* of csrc/fps.hip): time of the product's launches -- 32 clouds,
+"""fps_spec_kernel under an experiment switch (PRCNN_FPS_LAYOUT, PRCNN_FPS_* of csrc/fps_spec.hip): time of the product's launches -- 32 clouds,
 16384 -> 4096 and 4096 -> 1024 (the level-1 centres of the same clouds) -- on uniform and LiDAR-shaped scenes, HIP events, median of 7;
 the picks are written to gpurun_out/r06/fps_picks_<tag>.npz so that two runs can be compared bit for bit (the switch is read once per
 process).   usage: python profiles/fps_layout_probe.py <tag> [compare_tag]"""

@@ -1,4 +1,4 @@
-"""How many picks does one exchange of the speculative FPS kernel decide?  A numpy model of csrc/fps.hip fps_spec_kernel's rounds (16 waves,
+"""How many picks does one exchange of the speculative FPS kernel decide?  A numpy model of csrc/fps_spec.hip fps_spec_kernel's rounds (16 waves,
 each publishing its best point, the best point of its other lanes and a bound; entries accepted in order while they beat the global bound
 and are not changed by the entries before them): rounds, picks per round and why rounds end, for the blocked Morton layout the kernel uses,
 for tiles interleaved across the waves, and for more published entries per wave.  CPU only.

@@ -1,4 +1,4 @@
-"""Where does a round of the speculative FPS kernel go?  s_memtime stamps at the phase boundaries of csrc/fps.hip fps_spec_kernel,
+"""Where does a round of the speculative FPS kernel go?  s_memtime stamps at the phase boundaries of csrc/fps_spec.hip fps_spec_kernel,
 accumulated per wave of workgroup 0 over the whole run (a text-instrumented COPY of the source, linked with the product's other objects
 into profiles/_exp/libprcnn_hip_fps_stamps.so; the product library is not touched).
 
@@ -18,8 +18,8 @@ NPH = 8
 
 
 def instrument():
-    s = open(os.path.join(CSRC, "fps.hip")).read()
-    s = s.replace('#include "common.hpp"', '#include "%s/common.hpp"' % CSRC).replace('#include "../../include/prcnn_hip.h"', '#include "%s/include/prcnn_hip.h"' % ROOT)
+    s = open(os.path.join(CSRC, "fps_spec.hip")).read()
+    s = s.replace('#include "fps_common.hpp"', '#include "%s/fps_common.hpp"' % CSRC)      # (its own includes are relative to it)
     a = s.index("template <int PPT>\n__global__ __launch_bounds__(1024) void fps_spec_kernel(")
     b = s.index("// The speculative kernel for 16384 < n <= 32768")
     k = s[a:b]
@@ -51,7 +51,7 @@ def build():
     open(src, "w").write(instrument())
     obj = os.path.join(EXP, "fps_stamps.o")
     subprocess.check_call(["/opt/rocm/bin/hipcc"] + FLAGS + ["-c", src, "-o", obj])
-    objs = [os.path.join(CSRC, "build", f) for f in sorted(os.listdir(os.path.join(CSRC, "build"))) if f.endswith(".o") and f != "fps.o"]
+    objs = [os.path.join(CSRC, "build", f) for f in sorted(os.listdir(os.path.join(CSRC, "build"))) if f.endswith(".o") and f != "fps_spec.o"]
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB, obj] + objs)
     print("built", LIB)
 

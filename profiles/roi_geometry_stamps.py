@@ -1,5 +1,5 @@
 """Where does a RoI cloud's chain in rcnn_roi_geometry_kernel go?  s_memtime stamps at the phase boundaries of a text-instrumented COPY of
-csrc/fps.hip (linked with the product's other objects into profiles/_exp/libprcnn_hip_rg_stamps.so; the product library is not touched),
+csrc/roi_geometry.hip (linked with the product's other objects into profiles/_exp/libprcnn_hip_rg_stamps.so; the product library is not touched),
 on the RoI clouds of a real step: the inputs of prcnn_rcnn_roi_geometry are recorded from one engine pass over 16 synthetic scenes.
 
   python profiles/roi_geometry_stamps.py build                 (build container: hipcc)
@@ -20,8 +20,8 @@ MAXB = 4096
 
 
 def instrument():
-    s = open(os.path.join(CSRC, "fps.hip")).read()
-    s = s.replace('#include "common.hpp"', '#include "%s/common.hpp"' % CSRC).replace('#include "../../include/prcnn_hip.h"', '#include "%s/include/prcnn_hip.h"' % ROOT)
+    s = open(os.path.join(CSRC, "roi_geometry.hip")).read()
+    s = s.replace('#include "fps_common.hpp"', '#include "%s/fps_common.hpp"' % CSRC)      # (its own includes are relative to it)
     a = s.index("__global__ __launch_bounds__(64) void rcnn_roi_geometry_kernel(")
     b = s.index("/* RoI clouds xyz (b,512,3) whose points k >= limit[cloud]")
     k = s[a:b]
@@ -58,7 +58,7 @@ def build():
     open(src, "w").write(instrument())
     obj = os.path.join(EXP, "rg_stamps.o")
     subprocess.check_call(["/opt/rocm/bin/hipcc"] + FLAGS + ["-c", src, "-o", obj])
-    objs = [os.path.join(CSRC, "build", f) for f in sorted(os.listdir(os.path.join(CSRC, "build"))) if f.endswith(".o") and f != "fps.o"]
+    objs = [os.path.join(CSRC, "build", f) for f in sorted(os.listdir(os.path.join(CSRC, "build"))) if f.endswith(".o") and f != "roi_geometry.o"]
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB, obj] + objs)
     print("built", LIB)
 

@@ -1,4 +1,4 @@
-"""The acceptance predicate of the nested sampling entry (prcnn_fps_new_xyz_nested, csrc/fps.hip: fps_prefix_check_kernel), restated
+"""The acceptance predicate of the nested sampling entry (prcnn_fps_new_xyz_nested, csrc/fps_prefix.hip: fps_prefix_check_kernel), restated
 in numpy and held against the CPU oracle: a cloud the predicate ACCEPTS must be sampled by oracle.furthest_point_sample to the prefix
 0 .. m-1, with the running minima the predicate computed.  The predicate never looks at the oracle's answer; it is the definition the
 GPU kernels implement (tests/test_gpu_fps_nested.py compares them with it):

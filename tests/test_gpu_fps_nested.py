@@ -1,4 +1,4 @@
-"""-m gpu: prcnn_fps_new_xyz_nested (csrc/fps.hip) gives prcnn_fps_new_xyz's outputs bit for bit on ANY input -- clouds in pick order
+"""-m gpu: prcnn_fps_new_xyz_nested (csrc/fps_prefix.hip) gives prcnn_fps_new_xyz's outputs bit for bit on ANY input -- clouds in pick order
 (accepted by the prefix check: the sampling kernels skip them), raw clouds, lattices, duplicates, NaN / inf (rejected: sampled as
 before) and batches that mix the two, in both arithmetic modes and at the smallest size of every kernel route; the check's per-cloud
 verdict equals the numpy predicate of tests/test_fps_prefix_predicate.py; and the engine's detections do not depend on the route."""
