@@ -138,6 +138,9 @@ SIGNATURES = {
     "prcnn_gt_box_trig": [_I, _P, _P],
     "prcnn_gt_extract_count": [_P, _P],
     "prcnn_gt_extract_write": [_P, _P],
+    "prcnn_aug_max_candidates": [],
+    "prcnn_aug_place": [_P, _P],
+    "prcnn_aug_write": [_P, _P],
 }
 
 _lib = None

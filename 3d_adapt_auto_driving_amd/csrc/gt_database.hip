@@ -18,14 +18,14 @@
 //           formed in f32, which is exact (the reference forms them in double) for every size that is not subnormal.  cos / sin
 //           come from the host (prcnn_gt_box_trig: the libm calls of the host path).
 #include "common.hpp"
+#include "gt_common.hpp"
+#include "point_chains.hpp"
 #include <math.h>
 #include <algorithm>
 
 namespace prcnn {
 
 constexpr int GT_THREADS = 256;                  // 4 waves = 4 tiles per workgroup
-constexpr int GT_CHUNK = 64;                     // boxes per LDS chunk (gt_database.py BOX_CHUNK mirrors it)
-constexpr int GT_REC = 8;                        // floats per staged box: cx, cy, cz, h/2, l/2, w/2, cos, sin
 
 struct GtTile {
     int s, tile, ntile, n, idx, lane;
@@ -57,8 +57,7 @@ __device__ __forceinline__ float4 gt_load_rect(const prcnn_gt_batch &b, const Gt
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
             if (c.n == 1) {                      // a (1, 4) . (4, 3) product is a gemv call: two pairs, then their sum
-                const float lo = __fmaf_rn(p.x, m[j], __fmul_rn(p.y, m[3 + j]));
-                v[j] = __fadd_rn(lo, __fmaf_rn(p.z, m[6 + j], m[9 + j]));
+                v[j] = gemv_row(p.x, p.y, p.z, m[j], m[3 + j], m[6 + j], m[9 + j]);
                 continue;
             }
             float a = __fmul_rn(p.x, m[j]);
@@ -77,22 +76,9 @@ __device__ __forceinline__ void gt_stage_boxes(const prcnn_gt_batch &b, int g0, 
     __syncthreads();
     for (int k = threadIdx.x; k < nb; k += GT_THREADS) {
         const float *bx = b.boxes + 7L * (g0 + k);
-        const float hh = __fmul_rn(bx[3], 0.5f);
-        float *o = lds + k * GT_REC;
-        o[0] = bx[0]; o[1] = __fsub_rn(bx[1], hh); o[2] = bx[2];
-        o[3] = hh; o[4] = __fmul_rn(bx[5], 0.5f); o[5] = __fmul_rn(bx[4], 0.5f);
-        o[6] = b.trig[2L * (g0 + k)]; o[7] = b.trig[2L * (g0 + k) + 1];
+        gt_box_record(bx, bx[3], b.trig[2L * (g0 + k)], b.trig[2L * (g0 + k) + 1], lds + k * GT_REC);
     }
     __syncthreads();
-}
-
-__device__ __forceinline__ bool gt_inside(const float *o, const float4 r)
-{
-    const float dx = __fsub_rn(r.x, o[0]), dy = __fsub_rn(r.y, o[1]), dz = __fsub_rn(r.z, o[2]);
-    const bool reject = fabsf(dx) > 10.0f || fabsf(dy) > o[3] || fabsf(dz) > 10.0f;
-    const float xr = __fadd_rn(__fmul_rn(dx, o[6]), __fmul_rn(dz, -o[7]));
-    const float zr = __fadd_rn(__fmul_rn(dx, o[7]), __fmul_rn(dz, o[6]));
-    return !reject && xr >= -o[4] && xr <= o[4] && zr >= -o[5] && zr <= o[5];
 }
 
 // ---- pass 1: counts per (box, tile)

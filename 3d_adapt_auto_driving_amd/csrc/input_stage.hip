@@ -21,6 +21,7 @@
 // in the seed, uniformity).  The transform and the filter ARE bitwise the reference's (round 4): flags and rectified
 // coordinates equal what the reference's own numpy code produced on the fixture scenes (tests/golden g11).
 #include "common.hpp"
+#include "point_chains.hpp"
 #include <math.h>
 #include <algorithm>
 
@@ -29,45 +30,11 @@ namespace prcnn {
 constexpr int IS_THREADS = 1024;
 constexpr int IS_MAX_OUT = 16384;
 
-struct SceneCalib {          // row-major, as calibration.py holds them
-    float v2c[12];           // 3x4
-    float r0[9];             // 3x3
-    float p2[12];            // 3x4
-    float img_h, img_w;
-};
-
 __device__ __forceinline__ unsigned fmix32(unsigned h)
 {
     h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
     return h;                // a bijection on 32-bit words
 }
-
-// lidar -> rectified frame -> image, validity, near / far class of ONE raw point, in the arithmetic the reference's numpy code
-// performs (pinned by tests/golden g11, reference-executed): ``np.dot`` of float32 operands is a chain of fused multiply-adds
-// over the inner index, first term a plain product -- for the tiny (4,3) = V2C^T . R0^T product of Calibration.lidar_to_rect
-// (calibration.py:51-59) as well as for the (n,4) . (4,3) products; rect_to_img divides by the rect depth (0 -> 1e-9,
-// calibration.py:66-68) and subtracts P2[2][3] for the depth; get_valid_flag (kitti_rcnn_dataset.py:201-222) compares in f32.
-struct LidarToRect {
-    float m[4][3];           // np.dot(V2C.T, R0.T)
-    __device__ void set(const SceneCalib &cb)
-    {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                float acc = __fmul_rn(cb.v2c[i], cb.r0[3 * j]);                       // V2C^T[i][0] * R0^T[0][j]
-                acc = __fmaf_rn(cb.v2c[4 + i], cb.r0[3 * j + 1], acc);
-                m[i][j] = __fmaf_rn(cb.v2c[8 + i], cb.r0[3 * j + 2], acc);
-            }
-    }
-    __device__ __forceinline__ float row(int j, float px, float py, float pz) const
-    {
-        float acc = __fmul_rn(px, m[0][j]);
-        acc = __fmaf_rn(py, m[1][j], acc);
-        acc = __fmaf_rn(pz, m[2][j], acc);
-        return __fadd_rn(acc, m[3][j]);                                               // fma(1, m, acc)
-    }
-};
 
 // -> class: 0 = invalid, 1 = near (z < far_depth), 2 = far; x, y, z = rectified coordinates
 __device__ __forceinline__ int classify_point(const SceneCalib &cb, const LidarToRect &l2r, int lidar_frame, int image_filter,
@@ -77,15 +44,7 @@ __device__ __forceinline__ int classify_point(const SceneCalib &cb, const LidarT
     x = px; y = py; z = pz;
     if (lidar_frame) { x = l2r.row(0, px, py, pz); y = l2r.row(1, px, py, pz); z = l2r.row(2, px, py, pz); }
     bool ok = true;
-    if (image_filter) {
-        float hu = __fmul_rn(x, cb.p2[0]); hu = __fmaf_rn(y, cb.p2[1], hu); hu = __fmaf_rn(z, cb.p2[2], hu); hu = __fadd_rn(hu, cb.p2[3]);
-        float hv = __fmul_rn(x, cb.p2[4]); hv = __fmaf_rn(y, cb.p2[5], hv); hv = __fmaf_rn(z, cb.p2[6], hv); hv = __fadd_rn(hv, cb.p2[7]);
-        float hw = __fmul_rn(x, cb.p2[8]); hw = __fmaf_rn(y, cb.p2[9], hw); hw = __fmaf_rn(z, cb.p2[10], hw); hw = __fadd_rn(hw, cb.p2[11]);
-        const float zz = (z == 0.f) ? 1e-9f : z;
-        const float u = __fdiv_rn(hu, zz), v = __fdiv_rn(hv, zz);
-        const float depth = __fsub_rn(hw, cb.p2[11]);
-        ok = u >= 0.f && u < cb.img_w && v >= 0.f && v < cb.img_h && depth >= 0.f;
-    }
+    if (image_filter) ok = in_image(cb, x, y, z);
     if (scope)
         ok = ok && x >= scope[0] && x <= scope[1] && y >= scope[2] && y <= scope[3] && z >= scope[4] && z <= scope[5];
     return !ok ? 0 : (z < far_depth ? 1 : 2);

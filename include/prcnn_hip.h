@@ -719,6 +719,43 @@ int prcnn_gt_extract_count(const prcnn_gt_batch *batch, void *stream);
 /* pass 3: the objects' rows (out_off / out set by the caller from the totals) */
 int prcnn_gt_extract_write(const prcnn_gt_batch *batch, void *stream);
 
+/* Augmented-scene generation (tools/generate_aug_scene.py:150-249) for a batch of ragged scenes and of jobs = (epoch, scene) pairs
+ * over them (csrc/aug_scene.hip).  Device pointers.  Scenes: pt_off / tile_off / box_off (n_scenes + 1) i32 as in prcnn_gt_batch; velo
+ * (sum n, 4) f32 raw points; calib (n_scenes, 35) f32 = V2C | R0 | P2 | image height, width (prcnn_valid_flags' layout); scope 6 f64
+ * x0, x1, y0, y1, z0, z1 (PC_AREA_SCOPE); boxes (sum g, 7) f32 = the scenes' non-DontCare label boxes; rect (sum n, 4) f32 and valid
+ * (sum n) u8: the filter's results (rect x, y, z | intensity; valid flag).  Jobs: job_scene (n_jobs) i32; jt_off (n_jobs + 1) i64 into
+ * tile_cnt (sum of the jobs' scenes' tiles) i32; cand_n (n_jobs) i32 <= 16 candidates in try order with cand_db (n_jobs, 16) i32 =
+ * database entry, cand_box (n_jobs, 16, 7) f32 = its box on the road plane, cand_trig (n_jobs, 16, 2) f32 from prcnn_gt_box_trig,
+ * cand_move (n_jobs, 16) f64 = move_height; sizes (n_jobs, 18) i32 = [kept points, accepted, the accepted slots in acceptance order
+ * (-1 behind them)].  Database: db_pts (sum m, 4) f32 rect x, y, z | intensity, db_off (n_db + 1) i64.  Output: out_off (n_jobs + 1) i64
+ * rows per job, obj_off (n_jobs, 17) i64 = first row of every accepted object (and the end of the last), out (rows, 4) f32 = the kept
+ * points in point order, then the accepted objects' points.  max_tiles: the largest scene's.  The field layout is aug_scene.py's
+ * _AugBatch. */
+typedef struct prcnn_aug_batch {
+    int n_scenes, n_jobs, max_tiles, n_db;
+    const int *pt_off, *tile_off, *box_off;
+    const float *velo, *calib;
+    const double *scope;
+    const float *boxes;
+    float *rect;
+    unsigned char *valid;
+    const int *job_scene;
+    const long long *jt_off;
+    const int *cand_n, *cand_db;
+    const float *cand_box, *cand_trig;
+    const double *cand_move;
+    int *sizes, *tile_cnt;
+    const float *db_pts;
+    const long long *db_off, *out_off, *obj_off;
+    float *out;
+} prcnn_aug_batch;
+/* candidates per job (16) */
+int prcnn_aug_max_candidates(void);
+/* filter, placement, kept counts: fills rect, valid, tile_cnt (ordered exclusive offsets) and sizes */
+int prcnn_aug_place(const prcnn_aug_batch *batch, void *stream);
+/* the rows (out_off / obj_off / out set by the caller from sizes) */
+int prcnn_aug_write(const prcnn_aug_batch *batch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
