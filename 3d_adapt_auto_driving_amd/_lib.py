@@ -141,6 +141,8 @@ SIGNATURES = {
     "prcnn_aug_max_candidates": [],
     "prcnn_aug_place": [_P, _P],
     "prcnn_aug_write": [_P, _P],
+    "prcnn_train_place": [_P, _P],
+    "prcnn_train_emit": [_P, _P],
 }
 
 _lib = None

@@ -756,6 +756,48 @@ int prcnn_aug_place(const prcnn_aug_batch *batch, void *stream);
 /* the rows (out_off / obj_off / out set by the caller from sizes) */
 int prcnn_aug_write(const prcnn_aug_batch *batch, void *stream);
 
+/* RPN training input stage (lib/datasets/kitti_rcnn_dataset.py:249-382 get_rpn_sample in TRAIN mode, GT-aug :428-531 and
+ * data_augmentation :533-591 included) for a batch of ragged scenes (csrc/train_input.hip).  Device pointers.  Scenes: pt_off /
+ * tile_off / box_off (n_scenes + 1) i32 as in prcnn_aug_batch; velo (sum n, 4) f32 raw points, or rect x, y, z | intensity where
+ * is_rect (n_scenes) u8 is set; calib (n_scenes, 35) f32 and scope 6 f64 as in prcnn_aug_batch, the scope applied when reduce_by_range;
+ * box_rec (sum g, 11) f64 = the overlap records of the scenes' non-DontCare boxes (w, l + 0.5): the four BEV corners x, z of the f32
+ * corner array, min_h, max_h, the f32 volume term; cand_n (n_scenes) i32, cand_rec (n_scenes, 16, 11) f64 the candidates' records,
+ * cand_box (n_scenes, 16, 7) f32 placed boxes, cand_trig (n_scenes, 16, 2) f32, cand_move (n_scenes, 16) f64 = move_height.
+ * Work: rect (sum n, 4) f32, valid and flag (sum n) u8 (flag: bit 0 kept, bit 1 near), tile_cnt (2 * tiles) i32 interleaved kept /
+ * near ordered exclusive offsets, lists (3, sum n) i32 = the kept / near / far points' indices in point order.  sizes (n_scenes, 19)
+ * i32 = [kept points, near kept points, accepted, the accepted slots in acceptance order (-1 behind them)]: the block the host reads.
+ * Emit: db_pts (n_db_rows, 4) f32 resident rect x, y, z | intensity; codes (n_scenes, npoints) i64 = kind << 56 | slot << 48 | value
+ * with kind 0 / 1 / 2 a rank in the kept / near / far list and kind 3 a database row whose object sits in candidate slot `slot`; aug
+ * (n_scenes, 6) f64 = rotmat.T as m00, m10, m01, m11, the f32 scale, flags (1 rotation, 2 scaling, 4 flip); pts_rect (n_scenes,
+ * npoints, 3), pts_input (n_scenes, npoints, input_channels = 3 | 4), pts_features (n_scenes, npoints, 1) f32.  max_tiles: the largest tile count among the scenes
+ * [scene_begin, scene_end) of a place call (it sizes the grid).  The field layout is train_input.py's _TrainBatch. */
+typedef struct prcnn_train_batch {
+    int n_scenes, max_tiles, npoints, input_channels, reduce_by_range, scene_begin, scene_end, reserved;
+    long long n_db_rows;
+    const int *pt_off, *tile_off, *box_off;
+    const float *velo, *calib;
+    const double *scope;
+    const unsigned char *is_rect;
+    const double *box_rec;
+    const int *cand_n;
+    const double *cand_rec;
+    const float *cand_box, *cand_trig;
+    const double *cand_move;
+    float *rect;
+    unsigned char *valid, *flag;
+    int *tile_cnt, *lists, *sizes;
+    const float *db_pts;
+    const long long *codes;
+    const double *aug;
+    float *pts_rect, *pts_input, *pts_features;
+} prcnn_train_batch;
+/* filter, placement under the online overlap rule, flags, ordered scans, index lists of the scenes [scene_begin, scene_end): fills
+ * their part of rect .. lists and sizes.  (The sampler's draws of scene i come before the GT-aug draws of scene i + 1 in the loader's
+ * stream and their number depends on scene i's counts, so a caller that owns that stream places scene by scene.) */
+int prcnn_train_place(const prcnn_train_batch *batch, void *stream);
+/* the B x npoints output rows (codes / aug / outputs set by the caller after it has read sizes) */
+int prcnn_train_emit(const prcnn_train_batch *batch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

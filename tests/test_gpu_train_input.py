@@ -1,0 +1,216 @@
+"""The RPN training input stage on the device (csrc/train_input.hip through train_input.RpnTrainInput): against the reference's own
+loader (tests/golden g20) and against the try-by-try numpy path, bit for bit per key, on tests/train_tree.py's tree and on small
+seeded trees at the shapes where the kernels can go wrong."""
+import importlib
+import os
+import sys
+
+import numpy as np
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+import train_tree  # noqa: E402
+
+PKG = "3d_adapt_auto_driving_amd"
+pytestmark = pytest.mark.gpu
+G20 = os.path.join(HERE, "golden", "g20_train_input_ref.npz")
+GROUPS = ([0, 1, 2], [3, 4, 5, 6])
+
+
+def make_db(root):
+    G = importlib.import_module(PKG + ".gt_database")
+    G.generate_gt_database(root, class_name="Car", save_dir=os.path.join(root, "db"), device="cpu", log=lambda *a: None)
+    return G.database_file_name(os.path.join(root, "db"), "train", "Car")
+
+
+@pytest.fixture(scope="module")
+def tree_db(tmp_path_factory):
+    root = str(tmp_path_factory.mktemp("train_tree"))
+    train_tree.write_train_tree(root)
+    return root, make_db(root)
+
+
+def make_cfg(hard_ratio=0.6, intensity=True, prob=0.75, fixed=False, rand_num=True, extra=15, aug_data=True):
+    cfg = importlib.import_module(PKG + ".config").make_cfg()
+    cfg["GT_AUG_ENABLED"], cfg["GT_AUG_RAND_NUM"], cfg["GT_AUG_APPLY_PROB"], cfg["GT_AUG_HARD_RATIO"] = True, rand_num, prob, hard_ratio
+    cfg["GT_EXTRA_NUM"], cfg["AUG_DATA"] = extra, aug_data
+    cfg.RPN["USE_INTENSITY"], cfg.RPN["FIXED"] = intensity, fixed
+    return cfg
+
+
+def source(tree_db, cfg, device, seed, npoints=train_tree.NPOINTS, faraway=train_tree.NPOINTS_FARAWAY, with_replace=False,
+           split=train_tree.SPLIT):
+    T = importlib.import_module(PKG + ".train_input")
+    return T.RpnTrainInput(tree_db[0], cfg, tree_db[1], split=split, npoints=npoints, npoints_faraway=faraway,
+                           with_replace=with_replace, seed=seed, device=device)
+
+
+def host(v):
+    return v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)
+
+
+def same(got, want):
+    assert list(got) == list(want)
+    for key in want:
+        if key == "aug_method":
+            assert got[key] == want[key]
+            continue
+        g, w = host(got[key]), host(want[key])
+        assert g.dtype == w.dtype and g.shape == w.shape, key
+        assert g.tobytes() == w.tobytes(), key
+
+
+def same_state(a, b):
+    sa, sb = a.generator_state(), b.generator_state()
+    assert sa[0] == sb[0] and np.array_equal(sa[1], sb[1]) and sa[2:] == sb[2:]
+    assert all(np.array_equal(x, y) for x, y in zip(a.db_pos, b.db_pos))
+    assert a.last_kept == b.last_kept
+
+
+@pytest.mark.parametrize("rec", ["a", "b"])
+def test_device_equals_the_reference(tree_db, rec):
+    """the device path against the reference's own loader (g20), per key, and the generator's final state"""
+    z = np.load(G20, allow_pickle=False)
+    cfg = make_cfg(float(z[rec + "_hard_ratio"]), rand_num=bool(z[rec + "_rand_num"]))
+    dev = source(tree_db, cfg, "cuda", int(z["seed"]))
+    for gi, group in enumerate(GROUPS):
+        got = dev.batch(group)
+        for key, v in got.items():
+            w = z["%s_%d_%s" % (rec, gi, key)]
+            if key == "aug_method":
+                assert repr(v) == str(w)
+            elif key in ("sample_id", "random_select", "gt_boxes3d"):
+                assert np.array_equal(host(v), w) and host(v).dtype == w.dtype, key
+            else:
+                import torch
+                assert torch.is_tensor(v) and v.is_cuda and torch.equal(v.cpu(), torch.from_numpy(w)), key
+    st = dev.generator_state()
+    assert np.array_equal(st[1], z[rec + "_state_key"]) and [float(v) for v in st[2:]] == z[rec + "_state_rest"].tolist()
+    assert np.stack(dev.db_pos).tobytes() == z[rec + "_pos"].tobytes()
+
+
+@pytest.mark.parametrize("hard_ratio, intensity, npoints, faraway, with_replace, groups, seed", [
+    (0.6, True, 1024, 128, False, ([0, 1, 2, 3, 4], [5, 6]), 2020),          # B = 5
+    (0.0, False, 256, 32, False, ([6], [3], [1]), 7),                        # B = 1, npoints 256, the aug-scene id, no intensity
+    (0.6, True, 1024, 128, True, ([2, 0, 5],), 11),                          # with_replace; scene 2 has more than 64 label boxes
+])
+def test_device_equals_cpu(tree_db, hard_ratio, intensity, npoints, faraway, with_replace, groups, seed):
+    cfg = make_cfg(hard_ratio, intensity)
+    dev = source(tree_db, cfg, "cuda", seed, npoints, faraway, with_replace)
+    cpu = source(tree_db, cfg, "cpu", seed, npoints, faraway, with_replace)
+    for group in groups:
+        same(dev.batch(group), cpu.batch(group))
+        same_state(dev, cpu)
+    assert any(d[2] for d in cpu.decisions) and any(not d[2] for d in cpu.decisions)
+
+
+def test_second_batch_equals_a_fresh_object_with_the_same_state(tree_db):
+    import copy
+    cfg = make_cfg()
+    used = source(tree_db, cfg, "cuda", 31)
+    used.batch([0, 2, 4])
+    fresh = source(tree_db, cfg, "cuda", 0)
+    fresh.rng.set_state(used.generator_state())
+    fresh.db_pos = copy.deepcopy(used.db_pos)                                  # the drift is part of the state
+    same(used.batch([5, 1, 3, 6]), fresh.batch([5, 1, 3, 6]))
+    same_state(used, fresh)
+
+
+def test_device_fixed_and_no_gt_aug(tree_db):
+    cfg = make_cfg(fixed=True)
+    cfg["GT_AUG_ENABLED"] = False
+    dev, cpu = source(tree_db, cfg, "cuda", 3), source(tree_db, cfg, "cpu", 3)
+    got, want = dev.batch([0, 3, 6]), cpu.batch([0, 3, 6])
+    assert "rpn_cls_label" not in got
+    same(got, want)
+
+
+# ------------------------------------------------------------------------------------------------------------------- the sweep
+SWEEP = ((1, 1), (63, 64), (64, 65), (65, 1), (2000, 1))                         # (raw points, non-DontCare labels) per scene
+DB_NODES = ((4, 1), (6, 2), (5, 4), (7, 1), (3, 3), (6, 5))
+
+
+@pytest.fixture(scope="module")
+def sweep_db(tmp_path_factory):
+    """Two scenes that make the database (cars on DB_NODES, half of them with more than 100 points), then split ``sweep``: clouds
+    of 1, 63, 64, 65 and 2000 points inside the image with 1, 64, 65, 1, 1 label boxes, and ``packed``: a scene on a flat plane whose
+    points all lie inside the (free) database nodes' removal boxes.  Every object stands on train_tree's grid: no pair can come near 0 < IoU < 1e-3."""
+    root = str(tmp_path_factory.mktemp("sweep_tree"))
+    rng = np.random.default_rng(77)
+    cars = [train_tree.car_on_node(rng, i, j) for i, j in DB_NODES]
+    for sid, part in ((0, cars[:3]), (1, cars[3:])):
+        lines = [train_tree._line("Car", hwl, p, ry, 0.4) for hwl, p, ry in part]
+        clusters = [(hwl, p, ry, 300 if k % 2 else 30) for k, (hwl, p, ry) in enumerate(part)]
+        lidar, cal, plane, _ = train_tree.make_scene(np.random.default_rng(100 + sid), lines, clusters, 200)
+        train_tree.write_scene(root, sid, lidar, cal, lines, plane)
+    ids = []
+    for k, (n, g) in enumerate(SWEEP):
+        sid = 10 + k
+        hwl, p, ry = train_tree.car_on_node(rng, 5, 1)                            # the scene's own car: a node the database lacks
+        lines = [train_tree._line("Car", hwl, p, ry, -0.7)]
+        lines += [train_tree._line("Tram", (3.5, 2.6, 15.0), (60.0, 1.9, 90.0 + 20.0 * q), 0.02, 0.0) for q in range(g - 1)]
+        lidar, cal, plane, _ = train_tree.make_scene(np.random.default_rng(200 + k), lines, [], n)
+        train_tree.write_scene(root, sid, lidar, cal, lines, plane)
+        ids.append(sid)
+    # every raw point well inside a database node's removal box (h + 2 above a bottom that a flat plane puts at y = 1.65; the points
+    # lie within 0.3 m of the label centre in x and z and at y in 0.1 .. 0.82): the pasted objects remove them all
+    hwl, p, ry = train_tree.car_on_node(rng, 5, 6)
+    lines = [train_tree._line("Car", hwl, p, ry, 0.2)]
+    _, cal, _, _ = train_tree.make_scene(np.random.default_rng(300), lines, [], 4)
+    plane = np.array([0.0, -1.0, 0.0, 1.65])
+    srng = np.random.default_rng(301)
+    rect = np.concatenate([np.array([pp[0], pp[1] - 1.2, pp[2]]) + srng.uniform(-0.3, 0.3, (20, 3)) for _, pp, _ in cars])
+    Rv, tv = cal["Tr_velo_to_cam"][:, :3], cal["Tr_velo_to_cam"][:, 3]
+    velo = np.concatenate([(rect @ cal["R0_rect"] - tv) @ Rv, srng.random((len(rect), 1))], 1).astype(np.float32)
+    train_tree.write_scene(root, 20, velo, cal, lines, plane)
+    train_tree.write_split(root, "train", (0, 1))
+    train_tree.write_split(root, "sweep", ids)
+    train_tree.write_split(root, "packed", (20,))
+    return root, make_db(root)
+
+
+def no_discards(cpu):
+    """the share of decisions inside 0 < IoU < 1e-3 is zero (the trees' grid keeps every pair out of it)"""
+    band = [d for d in cpu.decisions if 0.0 < d[3] < 1e-3]
+    assert len(band) == 0 and len(cpu.decisions) > 0
+
+
+@pytest.mark.parametrize("prob, rand_num, extra, n_cand, intensity, groups", [
+    (1.0, False, 15, 16, True, ([0, 1, 2, 3, 4],)),                              # B = 5, 16 candidates in every scene
+    (1.0, False, 0, 1, False, ([0], [1], [2], [3], [4])),                        # B = 1, one candidate
+    (0.0, False, 15, 0, True, ([0], [2, 3], [4])),                               # no candidate
+])
+def test_sweep_device_equals_cpu(sweep_db, prob, rand_num, extra, n_cand, intensity, groups):
+    cfg = make_cfg(0.6, intensity, prob=prob, rand_num=rand_num, extra=extra)
+    dev = source(sweep_db, cfg, "cuda", 41, 256, 32, split="sweep")
+    cpu = source(sweep_db, cfg, "cpu", 41, 256, 32, split="sweep")
+    assert len(dev) == len(SWEEP)
+    for group in groups:
+        before = len(cpu.decisions)
+        want = cpu.batch(group)
+        assert len(cpu.decisions) - before == n_cand * len(group)
+        same(dev.batch(group), want)
+        same_state(dev, cpu)
+    if n_cand:
+        no_discards(cpu)
+
+
+@pytest.mark.parametrize("npoints, faraway", [(256, 32), (2048, 256)])         # fewer / more output rows than database points
+def test_every_scene_point_removed_by_the_pasted_boxes(sweep_db, npoints, faraway):
+    """the raw points lie inside the database nodes' removal boxes and every node gets pasted: no scene point is kept (empty kept, near
+    and far lists on the device) and every output row comes from the resident database"""
+    cfg = make_cfg(0.0, True, prob=1.0, rand_num=False, extra=15, aug_data=False)
+    dev = source(sweep_db, cfg, "cuda", 1, npoints, faraway, split="packed")
+    cpu = source(sweep_db, cfg, "cpu", 1, npoints, faraway, split="packed")
+    want = cpu.batch([0])
+    same(dev.batch([0]), want)
+    same_state(dev, cpu)
+    no_discards(cpu)
+    n_valid = len(cpu.valid_points(cpu.load_scene(20))[0])
+    assert n_valid >= 20 * (len(DB_NODES) - 1)                                   # node (7, 1) is outside the image; the rest pass the filter ...
+    assert cpu.last_kept == [(20, 0)] and dev.last_kept == [(20, 0)]             # ... and none is left after the removal
+    accepted = {d[1] for d in cpu.decisions if d[2]}
+    assert len(accepted) == len(DB_NODES)                                        # every node was pasted
+    db_xz = {(float(x), float(z)) for k in accepted for x, _, z in cpu.db[k]["points"]}
+    assert all((float(x), float(z)) in db_xz for x, _, z in want["pts_rect"][0])
