@@ -53,11 +53,13 @@ import threading
 import numpy as np
 
 from . import kitti_io, kitti_utils
-from .gt_database import MAX_IO_WORKERS, TILE, box_trig, class_tuple, load_gt_database, sample_id_list
-from .stat_norm import Object3d, png_size
+from .gt_database import box_trig, class_tuple, load_gt_database, sample_id_list
+from .kitti_io import Object3d, png_size
+from .scene_batch import (MAX_IO_WORKERS, TILE, as_calib, boxes_of_labels, check_device, check_pc_range, class_whitelist, cum,  # noqa: F401
+                          database_rows, enlarged, no_label_error, offsets_to_device, pack_scenes, place_on_plane, to_device, valid_points)
 
 TRY_TIMES = 50
-MAX_CAND = 16                            # csrc/aug_scene.hip AUG_MAX_CAND (the loop admits at most 15)
+MAX_CAND = 16                            # csrc/placement.hpp PLACE_MAX_CAND (the loop admits at most 15)
 SEED = 1024
 PC_AREA_SCOPE = {True: np.array([[-40, 40], [-1, 3], [0, 70.4]]), False: np.array([[-30, 30], [-1, 3], [0, 50]])}
 
@@ -65,11 +67,6 @@ PC_AREA_SCOPE = {True: np.array([[-40, 40], [-1, 3], [0, 70.4]]), False: np.arra
 def area_scope(class_name):
     """PC_AREA_SCOPE of the tool: x, y, z ranges in the rect frame, with the tool's dtypes (float64 for Car, int64 otherwise)."""
     return PC_AREA_SCOPE[class_name == "Car"]
-
-
-def check_pc_range(xyz, scope):
-    (x0, x1), (y0, y1), (z0, z1) = scope
-    return bool((x0 <= xyz[0] <= x1) and (y0 <= xyz[1] <= y1) and (z0 <= xyz[2] <= z1))
 
 
 def road_plane(path):
@@ -80,16 +77,6 @@ def road_plane(path):
     if plane[1] > 0:
         plane = -plane
     return plane / np.linalg.norm(plane[0:3])
-
-
-def place_on_plane(entry, plane):
-    """A database entry put on the road plane -> (box (7,) f32, move_height f64)."""
-    a, b, c, d = plane
-    box = entry["gt_box3d"].copy()
-    cur_height = (-d - a * box[0] - c * box[2]) / b
-    move = np.float64(box[1]) - cur_height
-    box[1] = np.float32(np.float64(box[1]) - move)
-    return box, np.float64(move)
 
 
 def shifted_points(points, move):
@@ -162,38 +149,22 @@ def _swapped_backend(iou3d_utils):
         iou3d_utils.iou3d_cuda = saved
 
 
-def valid_points(pts_lidar, calib, img_shape, scope):
-    """generate_aug_scene.py:241-249 -> (pts_rect (n, 3) f32, intensity (n,) f32) of the valid points."""
-    pts_rect = calib.lidar_to_rect(pts_lidar[:, 0:3])
-    pts_img, depth = calib.rect_to_img(pts_rect)
-    flag = np.logical_and(np.logical_and(pts_img[:, 0] >= 0, pts_img[:, 0] < img_shape[1]),
-                          np.logical_and(pts_img[:, 1] >= 0, pts_img[:, 1] < img_shape[0]))
-    flag = np.logical_and(flag, depth >= 0)
-    x, y, z = (pts_rect[:, k].astype(np.float64) for k in range(3))
-    (x0, x1), (y0, y1), (z0, z1) = np.asarray(scope, dtype=np.float64)
-    flag = flag & (x >= x0) & (x <= x1) & (y >= y0) & (y <= y1) & (z >= z0) & (z <= z1)
-    return pts_rect[flag][:, 0:3], pts_lidar[flag][:, 3]
-
-
 class _CpuScene:
     """The state of one aug_one_scene call (generate_aug_scene.py:161-234)."""
 
     def __init__(self, sample_id, pts_rect, intensity, all_boxes, plane):
         self.sample_id, self.pts_rect, self.intensity, self.plane = sample_id, pts_rect, intensity, plane
-        self.cur = all_boxes.copy()
-        self.cur[:, 4] += 0.5
-        self.cur[:, 5] += 0.5
+        self.cur = enlarged(all_boxes)
         self.flag = np.ones(pts_rect.shape[0], dtype=np.int32)
         self.accepted, self.tested = [], []             # (db index, box, move) ; db indices
 
     def try_candidate(self, idx, entry):
         import torch
         from . import iou3d_utils, roipool3d_utils
-        box, move = place_on_plane(entry, self.plane)
+        box, move = place_on_plane(entry["gt_box3d"], self.plane)
         self.tested.append(int(idx))
         if self.cur.shape[0] == 0:
-            raise ValueError("aug_scene: sample %06d has no label besides DontCare: the overlap test has nothing to compare with "
-                             "(the reference raises here)" % self.sample_id)
+            raise no_label_error("aug_scene", self.sample_id)
         iou3d = iou3d_utils.boxes_iou3d_gpu(torch.from_numpy(box.reshape(1, 7)), torch.from_numpy(self.cur)).numpy()
         if not (iou3d.max() < np.float32(1e-8)):
             return False
@@ -201,10 +172,7 @@ class _CpuScene:
         big[3] += 2
         mask = roipool3d_utils.pts_in_boxes3d_cpu(torch.from_numpy(self.pts_rect), torch.from_numpy(big.reshape(1, 7)))[0].numpy()
         self.flag[mask == 1] = 0
-        big = box.copy()
-        big[4] += 0.5
-        big[5] += 0.5
-        self.cur = np.concatenate((self.cur, big.reshape(1, 7)), axis=0)
+        self.cur = np.concatenate((self.cur, enlarged(box).reshape(1, 7)), axis=0)
         self.accepted.append((int(idx), box, move))
         return True
 
@@ -237,8 +205,7 @@ def aug_one_scene_cpu(rng, sample_id, pts_rect, intensity, all_boxes, plane, db,
 
 def _norm_scene(scene):
     pts, calib, img_shape, boxes, plane = scene
-    calib = calib if isinstance(calib, kitti_io.Calibration) else kitti_io.Calibration(calib)
-    return (np.ascontiguousarray(np.asarray(pts, dtype=np.float32).reshape(-1, 4)), calib, tuple(int(v) for v in img_shape[:2]),
+    return (np.ascontiguousarray(np.asarray(pts, dtype=np.float32).reshape(-1, 4)), as_calib(calib), tuple(int(v) for v in img_shape[:2]),
             np.ascontiguousarray(np.asarray(boxes, dtype=np.float32).reshape(-1, 7)), np.asarray(plane, dtype=np.float64).reshape(4))
 
 
@@ -251,8 +218,7 @@ def _check_jobs(scenes, jobs, db, ids):
         if any(not 0 <= i < len(db) for i in cand):
             raise ValueError("aug_scene: candidate outside the database")
         if len(cand) and scenes[s][3].shape[0] == 0:
-            raise ValueError("aug_scene: sample %06d has no label besides DontCare: the overlap test has nothing to compare with "
-                             "(the reference raises here)" % (ids[s] if ids is not None else s))
+            raise no_label_error("aug_scene", ids[s] if ids is not None else s)
 
 
 def _place_cpu(scenes, jobs, db, scope, ids):
@@ -281,10 +247,6 @@ class _AugBatch(C.Structure):
                 ("db_pts", C.c_void_p), ("db_off", C.c_void_p), ("out_off", C.c_void_p), ("obj_off", C.c_void_p), ("out", C.c_void_p)]
 
 
-def _cum(a):
-    return np.concatenate([[0], np.cumsum(a)]).astype(np.int64)
-
-
 class AugPlacer:
     """The device path: the database's points (x, y, z, intensity rows + offsets) and (cos ry, sin ry) are uploaded once and stay."""
 
@@ -294,13 +256,10 @@ class AugPlacer:
         if _lib.call("prcnn_aug_max_candidates") != MAX_CAND:
             raise _lib.PrcnnError("aug_scene: MAX_CAND differs from the library's")
         self.device, self.db = device, db
-        self.db_n = np.array([len(e["points"]) for e in db], dtype=np.int64)
-        self.db_off = _cum(self.db_n)
-        rows = [np.concatenate((e["points"].reshape(-1, 3), e["intensity"].reshape(-1, 1)), 1) for e in db]
-        pts = np.concatenate(rows, 0).astype(np.float32) if rows else np.zeros((0, 4), np.float32)
+        pts, self.db_n, self.db_off = database_rows(db)
         self.db_boxes = np.stack([e["gt_box3d"] for e in db]).astype(np.float32) if db else np.zeros((0, 7), np.float32)
         self.db_trig = box_trig(self.db_boxes)
-        self.t_pts = torch.from_numpy(np.ascontiguousarray(pts if len(pts) else np.zeros((1, 4), np.float32))).to(device)
+        self.t_pts = torch.from_numpy(pts if len(pts) else np.zeros((1, 4), np.float32)).to(device)
         self.t_off = torch.from_numpy(self.db_off).to(device)
 
     def __call__(self, scenes, jobs, scope, ids=None):
@@ -313,17 +272,13 @@ class AugPlacer:
         if J == 0:
             return []
         device = self.device
-        n = np.array([len(p) for p, _, _, _, _ in scenes], dtype=np.int64)
-        nt = (n + TILE - 1) // TILE
-        nb = np.array([len(b) for _, _, _, b, _ in scenes], dtype=np.int64)
-        pt_off, tile_off, box_off = _cum(n), _cum(nt), _cum(nb)
+        pk = pack_scenes([p for p, _, _, _, _ in scenes], [len(b) for _, _, _, b, _ in scenes], [c for _, c, _, _, _ in scenes],
+                         [shape for _, _, shape, _, _ in scenes])
         job_scene = np.array([s for s, _ in jobs], dtype=np.int32)
-        jt_off = _cum(nt[job_scene])
-        if pt_off[-1] >= 2 ** 31 or jt_off[-1] >= 2 ** 31:
+        jt_off = cum(pk.nt[job_scene])
+        if pk.pt_off[-1] >= 2 ** 31 or jt_off[-1] >= 2 ** 31:
             raise ValueError("aug_scene batch too large: split it")
-        velo = np.concatenate([p for p, _, _, _, _ in scenes]) if pt_off[-1] else np.zeros((1, 4), np.float32)
-        boxes = np.concatenate([b for _, _, _, b, _ in scenes]) if box_off[-1] else np.zeros((1, 7), np.float32)
-        calib = np.stack([kitti_io.DeviceInputStage.pack_calib(c, shape) for _, c, shape, _, _ in scenes]).astype(np.float32)
+        boxes = np.concatenate([b for _, _, _, b, _ in scenes]) if pk.box_off[-1] else np.zeros((1, 7), np.float32)
         cand_n = np.array([len(c) for _, c in jobs], dtype=np.int32)
         cand_db = np.zeros((J, MAX_CAND), dtype=np.int32)
         cand_box = np.zeros((J, MAX_CAND, 7), dtype=np.float32)
@@ -331,17 +286,16 @@ class AugPlacer:
         cand_move = np.zeros((J, MAX_CAND), dtype=np.float64)
         for j, (s, cand) in enumerate(jobs):
             for k, i in enumerate(cand):
-                cand_box[j, k], cand_move[j, k] = place_on_plane(self.db[i], scenes[s][4])
+                cand_box[j, k], cand_move[j, k] = place_on_plane(self.db[i]["gt_box3d"], scenes[s][4])
                 cand_db[j, k], cand_trig[j, k] = i, self.db_trig[i]
-        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
-        t_in = [dev(a) for a in (pt_off.astype(np.int32), tile_off.astype(np.int32), box_off.astype(np.int32), velo, calib,
-                                 np.asarray(scope, dtype=np.float64).reshape(6), boxes)]
-        t_rect = torch.empty((max(1, int(pt_off[-1])), 4), dtype=torch.float32, device=device)
-        t_valid = torch.empty((max(1, int(pt_off[-1])),), dtype=torch.uint8, device=device)
+        dev = to_device(device)
+        t_in = offsets_to_device(pk, dev) + [dev(a) for a in (pk.velo, pk.calib, np.asarray(scope, dtype=np.float64).reshape(6), boxes)]
+        t_rect = torch.empty((max(1, int(pk.pt_off[-1])), 4), dtype=torch.float32, device=device)
+        t_valid = torch.empty((max(1, int(pk.pt_off[-1])),), dtype=torch.uint8, device=device)
         t_job = [dev(a) for a in (job_scene, jt_off, cand_n, cand_db, cand_box, cand_trig, cand_move)]
         t_sizes = torch.zeros((J, MAX_CAND + 2), dtype=torch.int32, device=device)
         t_cnt = torch.empty((max(1, int(jt_off[-1])),), dtype=torch.int32, device=device)
-        b = _AugBatch(S, J, int(nt.max()) if S else 0, len(self.db), *[t.data_ptr() for t in t_in], t_rect.data_ptr(), t_valid.data_ptr(),
+        b = _AugBatch(S, J, pk.max_tiles, len(self.db), *[t.data_ptr() for t in t_in], t_rect.data_ptr(), t_valid.data_ptr(),
                       *[t.data_ptr() for t in t_job], t_sizes.data_ptr(), t_cnt.data_ptr(), self.t_pts.data_ptr(), self.t_off.data_ptr(),
                       None, None, None)
         stream = C.c_void_p(_lib.current_stream(t_rect))
@@ -354,7 +308,7 @@ class AugPlacer:
             slots = [int(k) for k in sizes[j, 2:2 + sizes[j, 1]]]
             accepted.append(slots)
             rows = [self.db_n[cand[k]] for k in slots]
-            obj_off[j, :len(slots) + 1] = out_off[j] + sizes[j, 0] + _cum(rows)
+            obj_off[j, :len(slots) + 1] = out_off[j] + sizes[j, 0] + cum(rows)
             obj_off[j, len(slots) + 1:] = obj_off[j, len(slots)]
             out_off[j + 1] = obj_off[j, len(slots)]
         total = int(out_off[-1])
@@ -380,20 +334,14 @@ def place_candidates(scenes, jobs, db, class_name="Car", device="cuda", ids=None
         jobs = [(int(s), [int(i) for i in cand]) for s, cand in jobs]
         _check_jobs(scenes, jobs, db, ids)
         return _place_cpu(scenes, jobs, db, scope, ids)
-    if not str(device).startswith("cuda"):
-        raise ValueError("device must be 'cpu' or 'cuda[:i]'")
+    check_device(device)
     placer = placer if placer is not None else AugPlacer(db, device)
     return placer(scenes, jobs, scope, ids)
 
 
 # ------------------------------------------------------------------------------------------------------------------------ tool
 def filtrate_objects(obj_list, classes, include_similar):
-    white = list(classes)
-    if include_similar:
-        if "Car" in classes:
-            white.append("Van")
-        if "Pedestrian" in classes or "Cyclist" in classes:
-            white.append("Person_sitting")
+    white = class_whitelist(classes, include_similar, sitting_with=("Pedestrian", "Cyclist"))
     return [o for o in obj_list if o.cls_type in white]
 
 
@@ -454,11 +402,7 @@ def generate_aug_scene(root, gt_database, save_dir, split="train", class_name="C
         def load_labels(sample_id):
             with open(os.path.join(base, "label_2", "%06d.txt" % sample_id)) as f:
                 objs = [Object3d(line) for line in f.readlines()]
-            every = [o for o in objs if o.cls_type != "DontCare"]
-            boxes = np.zeros((len(every), 7), dtype=np.float32)
-            for k, o in enumerate(every):
-                boxes[k, 0:3], boxes[k, 3], boxes[k, 4], boxes[k, 5], boxes[k, 6] = o.t, o.h, o.w, o.l, o.ry
-            return boxes, filtrate_objects(objs, classes, include_similar)
+            return boxes_of_labels([o for o in objs if o.cls_type != "DontCare"]), filtrate_objects(objs, classes, include_similar)
 
         def load(sample_id, labels=None):
             pts = np.fromfile(os.path.join(base, "velodyne", "%06d.bin" % sample_id), dtype=np.float32).reshape(-1, 4)
@@ -501,8 +445,7 @@ def generate_aug_scene(root, gt_database, save_dir, split="train", class_name="C
                         st = aug_one_scene_cpu(rng, sample_id, pts_rect, intensity, boxes, plane, db, scope)
                         written[(epoch, k)] = write(epoch, sample_id, calib, shape, objs, st.rows(db), [(i, box) for i, box, _ in st.accepted])
             else:
-                if not str(device).startswith("cuda"):
-                    raise ValueError("device must be 'cpu' or 'cuda[:i]'")
+                check_device(device)
                 # the stream first: it needs the labels only.  Then the geometry, batch by batch, every epoch of a scene in one call
                 labels = list(pool.map(load_labels, ids))
                 cands = {}

@@ -1,14 +1,14 @@
 // aug_scene.hip -- the geometric part of augmented-scene generation (tools/generate_aug_scene.py:150-234 aug_one_scene and the
 // filter of :241-249) for a batch of ragged scenes and of jobs = (epoch, scene) pairs over them.  The random stream of the tool does
-// not depend on any geometric result, so the host has replayed it: every job comes with the ordered list of at most AUG_MAX_CAND
+// not depend on any geometric result, so the host has replayed it: every job comes with the ordered list of at most PLACE_MAX_CAND
 // database objects that reach the overlap test, already put on the scene's road plane (aug_scene.py).
 //
-// Points of all scenes sit back to back (pt_off), cut into 64-point tiles (tile_off), as in gt_database.hip; the scenes' non-DontCare
+// Points of all scenes sit back to back (pt_off), cut into 64-point tiles (tile_off; scene_tiles.hpp); the scenes' non-DontCare
 // label boxes sit back to back too (box_off).  The database's points stay resident (db_pts / db_off).
 //   filter   once per scene: velo -> rect -> image, valid flag (in the image, depth >= 0, inside PC_AREA_SCOPE) -> rect, valid;
 //   place    one wave per job: every candidate against every label box of the scene (w + 0.5, l + 0.5; LDS chunks of GT_CHUNK) and
 //            against every earlier candidate (w + 0.5, l + 0.5), all pairs in parallel; then the greedy accept in try order from the
-//            ballots' conflict words.  The candidate x box matrix is never stored;
+//            ballots' conflict words (placement.hpp).  The candidate x box matrix is never stored;
 //   count    per (job, tile): points that are valid and inside NO accepted box enlarged by h + 2 (one flag per point however many
 //            enlargements hold it) -> tile_cnt;  scan: ordered exclusive scan per job, the total -> sizes;
 //   write    (after the host has turned the sizes into row offsets) the kept points in point order, then every accepted object's
@@ -23,66 +23,27 @@
 //   y shift        new_gt_points[:, 1] -= move_height with move_height a float64 scalar: f32(f64(y) - move_height) per point.
 #include "common.hpp"
 #include "gt_common.hpp"
+#include "placement.hpp"
 #include "point_chains.hpp"
 #include "rbox_iou.hpp"
+#include "scene_tiles.hpp"
 #include <math.h>
-#include <algorithm>
 
 namespace prcnn {
 
 constexpr int AUG_THREADS = 256;                 // 4 waves = 4 tiles per workgroup
-constexpr int AUG_MAX_CAND = 16;                 // candidates per job (the tool's loop admits at most 15)
-constexpr int AUG_SIZES = AUG_MAX_CAND + 2;      // ints per job in sizes: kept points, accepted, the accepted slots in order
+constexpr int AUG_SIZES = PLACE_MAX_CAND + 2;    // ints per job in sizes: kept points, accepted, the accepted slots in order
 constexpr int AUG_REC = 9;                       // floats per staged overlap box: x1, z1, x2, z2, cos, sin, y - h, y, volume
-
-struct AugTile {
-    int s, tile, ntile, n, idx, lane;
-    long p0;
-    bool live, valid;
-};
-
-__device__ __forceinline__ void aug_tile(const prcnn_aug_batch &b, int s, AugTile &c)
-{
-    c.s = s;
-    c.tile = blockIdx.x * (AUG_THREADS / WAVE) + threadIdx.x / WAVE;
-    c.ntile = b.tile_off[s + 1] - b.tile_off[s];
-    c.p0 = b.pt_off[s];
-    c.n = b.pt_off[s + 1] - b.pt_off[s];
-    c.lane = threadIdx.x & (WAVE - 1);
-    c.idx = c.tile * WAVE + c.lane;
-    c.live = c.tile < c.ntile;
-    c.valid = c.live && c.idx < c.n;
-}
 
 // ---- filter: once per scene
 __global__ __launch_bounds__(AUG_THREADS) void aug_filter_kernel(prcnn_aug_batch b)
 {
-    AugTile c;
-    aug_tile(b, blockIdx.y, c);
+    SceneTile c;
+    scene_tile<AUG_THREADS>(b, blockIdx.y, c);
     if (!c.valid) return;
-    const SceneCalib cb = ((const SceneCalib *)b.calib)[c.s];
-    LidarToRect l2r;
-    l2r.set(cb);
     const float4 p = *(const float4 *)(b.velo + 4 * (c.p0 + c.idx));
     float x, y, z;
-    bool ok;
-    if (c.n == 1) {
-        x = gemv_row(p.x, p.y, p.z, l2r.m[0][0], l2r.m[1][0], l2r.m[2][0], l2r.m[3][0]);
-        y = gemv_row(p.x, p.y, p.z, l2r.m[0][1], l2r.m[1][1], l2r.m[2][1], l2r.m[3][1]);
-        z = gemv_row(p.x, p.y, p.z, l2r.m[0][2], l2r.m[1][2], l2r.m[2][2], l2r.m[3][2]);
-        const float hu = gemv_row_t(x, y, z, cb.p2[0], cb.p2[1], cb.p2[2], cb.p2[3]);
-        const float hv = gemv_row_t(x, y, z, cb.p2[4], cb.p2[5], cb.p2[6], cb.p2[7]);
-        const float hw = gemv_row_t(x, y, z, cb.p2[8], cb.p2[9], cb.p2[10], cb.p2[11]);
-        const float zz = (z == 0.f) ? 1e-9f : z;
-        const float u = __fdiv_rn(hu, zz), v = __fdiv_rn(hv, zz);
-        ok = u >= 0.f && u < cb.img_w && v >= 0.f && v < cb.img_h && __fsub_rn(hw, cb.p2[11]) >= 0.f;
-    } else {
-        x = l2r.row(0, p.x, p.y, p.z); y = l2r.row(1, p.x, p.y, p.z); z = l2r.row(2, p.x, p.y, p.z);
-        ok = in_image(cb, x, y, z);
-    }
-    const double *sc = b.scope;
-    ok = ok && (double)x >= sc[0] && (double)x <= sc[1] && (double)y >= sc[2] && (double)y <= sc[3] && (double)z >= sc[4] &&
-         (double)z <= sc[5];
+    const bool ok = rect_valid_point(p, ((const SceneCalib *)b.calib)[c.s], c.n == 1, false, b.scope, x, y, z);
     *(float4 *)(b.rect + 4 * (c.p0 + c.idx)) = make_float4(x, y, z, p.w);
     b.valid[c.p0 + c.idx] = ok ? 1 : 0;
 }
@@ -120,82 +81,32 @@ __device__ __forceinline__ float aug_iou3d(const float *a, const float *b)
     return __fdiv_rn(o3, den);
 }
 
+// a candidate is placed when every overlap value is < 1e-8 (a NaN rejects, as np.max would)
+__device__ __forceinline__ bool aug_conflict(const float *a, const float *b) { return !(aug_iou3d(a, b) < 1e-8f); }
+
 __global__ __launch_bounds__(WAVE) void aug_place_kernel(prcnn_aug_batch b)
 {
     __shared__ float sorig[GT_CHUNK * AUG_REC];
-    __shared__ float scand[AUG_MAX_CAND * AUG_REC], sgrown[AUG_MAX_CAND * AUG_REC];
+    __shared__ float scand[PLACE_MAX_CAND * AUG_REC], sgrown[PLACE_MAX_CAND * AUG_REC];
     __shared__ unsigned srej;
     const int j = blockIdx.x, lane = threadIdx.x;
     const int s = b.job_scene[j];
     if (s < 0 || s >= b.n_scenes) return;            // (uniform in the workgroup) a job must name a scene of the batch
-    const int nc = min(max(b.cand_n[j], 0), AUG_MAX_CAND);
-    int *sizes = b.sizes + (long)AUG_SIZES * j;
-    if (lane == 0) srej = 0u;
+    const int nc = min(max(b.cand_n[j], 0), PLACE_MAX_CAND);
     if (lane < nc) {
-        const float *bx = b.cand_box + 7L * ((long)AUG_MAX_CAND * j + lane);
+        const float *bx = b.cand_box + 7L * ((long)PLACE_MAX_CAND * j + lane);
         aug_overlap_record(bx, 0.f, scand + lane * AUG_REC);
         aug_overlap_record(bx, 0.5f, sgrown + lane * AUG_REC);
     }
-    // every candidate against the scene's label boxes
-    const int bb = b.box_off[s], nb = b.box_off[s + 1] - bb;
-    for (int k0 = 0; k0 < nb; k0 += GT_CHUNK) {
-        const int kn = min(GT_CHUNK, nb - k0);
-        __syncthreads();
+    // every candidate against the scene's label boxes (w + 0.5, l + 0.5), then against every earlier candidate, grown alike
+    const int bb = b.box_off[s];
+    const unsigned rej = place_reject_by_labels<float, AUG_REC, aug_conflict>(scand, nc, sorig, b.box_off[s + 1] - bb, &srej, [&](int k0, int kn) {
         for (int k = lane; k < kn; k += WAVE) aug_overlap_record(b.boxes + 7L * (bb + k0 + k), 0.5f, sorig + k * AUG_REC);
-        __syncthreads();
-        for (int p = lane; p < nc * kn; p += WAVE) {
-            const int c = p / kn, k = p - c * kn;
-            if (!(aug_iou3d(scand + c * AUG_REC, sorig + k * AUG_REC) < 1e-8f)) atomicOr(&srej, 1u << c);   // LDS; an OR has no order
-        }
-    }
-    __syncthreads();
-    const unsigned rej = srej;
-    // every candidate i against every earlier one jj, grown: row i of an iteration's ballot is its 16-bit conflict word
-    unsigned conf[AUG_MAX_CAND];
-#pragma unroll
-    for (int it = 0; it < AUG_MAX_CAND * AUG_MAX_CAND / WAVE; ++it) {
-        const int p = it * WAVE + lane, i = p / AUG_MAX_CAND, jj = p % AUG_MAX_CAND;
-        bool bad = false;
-        if (i < nc && jj < i && !((rej >> i) & 1u) && !((rej >> jj) & 1u))
-            bad = !(aug_iou3d(scand + i * AUG_REC, sgrown + jj * AUG_REC) < 1e-8f);
-        const unsigned long long m = __ballot(bad);
-#pragma unroll
-        for (int q = 0; q < WAVE / AUG_MAX_CAND; ++q)
-            conf[it * (WAVE / AUG_MAX_CAND) + q] = (unsigned)(m >> (AUG_MAX_CAND * q)) & 0xffffu;
-    }
-    // the greedy accept in try order (uniform in the wave)
-    unsigned acc = 0u;
-    int n_acc = 0;
-#pragma unroll
-    for (int i = 0; i < AUG_MAX_CAND; ++i) {
-        if (i < nc && !((rej >> i) & 1u) && !(conf[i] & acc)) {
-            acc |= 1u << i;
-            if (lane == 0) sizes[2 + n_acc] = i;
-            ++n_acc;
-        }
-    }
-    if (lane == 0) {
-        sizes[1] = n_acc;
-        for (int k = n_acc; k < AUG_MAX_CAND; ++k) sizes[2 + k] = -1;
-    }
+    });
+    place_accept_greedy<float, AUG_REC, aug_conflict>(scand, sgrown, nc, rej, b.sizes + (long)AUG_SIZES * j + 2);
 }
 
-// the job's accepted boxes, h + 2 -> inside records (all threads of the workgroup; a barrier behind)
-__device__ __forceinline__ int aug_stage_accepted(const prcnn_aug_batch &b, int j, float *lds)
-{
-    const int *sizes = b.sizes + (long)AUG_SIZES * j;
-    const int na = min(max(sizes[1], 0), AUG_MAX_CAND);
-    if ((int)threadIdx.x < na) {
-        const int slot = min(max(sizes[2 + threadIdx.x], 0), AUG_MAX_CAND - 1);
-        const long q = (long)AUG_MAX_CAND * j + slot;
-        const float *bx = b.cand_box + 7L * q;
-        gt_box_record(bx, __fadd_rn(bx[3], 2.0f), b.cand_trig[2 * q], b.cand_trig[2 * q + 1], lds + threadIdx.x * GT_REC);
-    }
-    __syncthreads();
-    return na;
-}
-
-__device__ __forceinline__ bool aug_kept(const prcnn_aug_batch &b, const AugTile &c, const float *lds, int na, float4 &r)
+__device__ __forceinline__ bool aug_kept(const prcnn_aug_batch &b, const SceneTile &c, const float *lds, int na, float4 &r)
 {
     r = make_float4(0.f, 0.f, 0.f, 0.f);
     if (!c.valid) return false;
@@ -208,12 +119,12 @@ __device__ __forceinline__ bool aug_kept(const prcnn_aug_batch &b, const AugTile
 // ---- count: kept points per (job, tile)
 __global__ __launch_bounds__(AUG_THREADS) void aug_count_kernel(prcnn_aug_batch b)
 {
-    __shared__ float sbox[AUG_MAX_CAND * GT_REC];
+    __shared__ float sbox[PLACE_MAX_CAND * GT_REC];
     const int j = blockIdx.y;
     if (b.job_scene[j] < 0 || b.job_scene[j] >= b.n_scenes) return;
-    AugTile c;
-    aug_tile(b, b.job_scene[j], c);
-    const int na = aug_stage_accepted(b, j, sbox);
+    SceneTile c;
+    scene_tile<AUG_THREADS>(b, b.job_scene[j], c);
+    const int na = stage_accepted(b.sizes + (long)AUG_SIZES * j + 2, (long)PLACE_MAX_CAND * j, b.cand_box, b.cand_trig, sbox);
     if (!c.live) return;
     float4 r;
     const unsigned long long m = __ballot(aug_kept(b, c, sbox, na, r));
@@ -226,36 +137,19 @@ __global__ __launch_bounds__(AUG_THREADS) void aug_scan_kernel(prcnn_aug_batch b
     __shared__ int wsum[AUG_THREADS / WAVE];
     const int j = blockIdx.x, s = b.job_scene[j];
     if (s < 0 || s >= b.n_scenes) return;
-    const int nt = b.tile_off[s + 1] - b.tile_off[s];
-    int *a = b.tile_cnt + b.jt_off[j];
-    const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
-    int carry = 0;
-    for (int i0 = 0; i0 < nt; i0 += AUG_THREADS) {
-        const int i = i0 + threadIdx.x;
-        const int v = i < nt ? a[i] : 0;
-        int inc = v;
-        for (int d = 1; d < WAVE; d <<= 1) { const int o = __shfl_up(inc, d, 64); if (lane >= d) inc += o; }
-        __syncthreads();
-        if (lane == WAVE - 1) wsum[w] = inc;
-        __syncthreads();
-        int before = carry, tot = 0;
-#pragma unroll
-        for (int q = 0; q < AUG_THREADS / WAVE; ++q) { if (q < w) before += wsum[q]; tot += wsum[q]; }
-        if (i < nt) a[i] = before + inc - v;
-        carry += tot;
-    }
-    if (threadIdx.x == 0) b.sizes[(long)AUG_SIZES * j] = carry;
+    const int tot = tile_exclusive_scan<AUG_THREADS>(b.tile_cnt + b.jt_off[j], b.tile_off[s + 1] - b.tile_off[s], 1, wsum);
+    if (threadIdx.x == 0) b.sizes[(long)AUG_SIZES * j] = tot;
 }
 
 // ---- write: the kept points' rows
 __global__ __launch_bounds__(AUG_THREADS) void aug_write_kernel(prcnn_aug_batch b)
 {
-    __shared__ float sbox[AUG_MAX_CAND * GT_REC];
+    __shared__ float sbox[PLACE_MAX_CAND * GT_REC];
     const int j = blockIdx.y;
     if (b.job_scene[j] < 0 || b.job_scene[j] >= b.n_scenes) return;
-    AugTile c;
-    aug_tile(b, b.job_scene[j], c);
-    const int na = aug_stage_accepted(b, j, sbox);
+    SceneTile c;
+    scene_tile<AUG_THREADS>(b, b.job_scene[j], c);
+    const int na = stage_accepted(b.sizes + (long)AUG_SIZES * j + 2, (long)PLACE_MAX_CAND * j, b.cand_box, b.cand_trig, sbox);
     if (!c.live) return;
     float4 r;
     const bool keep = aug_kept(b, c, sbox, na, r);
@@ -273,15 +167,15 @@ __global__ __launch_bounds__(AUG_THREADS) void aug_objects_kernel(prcnn_aug_batc
 {
     const int j = blockIdx.z, k = blockIdx.y;
     const int *sizes = b.sizes + (long)AUG_SIZES * j;
-    if (k >= min(max(sizes[1], 0), AUG_MAX_CAND)) return;
+    if (k >= min(max(sizes[1], 0), PLACE_MAX_CAND)) return;
     const int slot = sizes[2 + k];
-    if (slot < 0 || slot >= AUG_MAX_CAND) return;
-    const long q = (long)AUG_MAX_CAND * j + slot;
+    if (slot < 0 || slot >= PLACE_MAX_CAND) return;
+    const long q = (long)PLACE_MAX_CAND * j + slot;
     const int e = b.cand_db[q];
     if (e < 0 || e >= b.n_db) return;
     const long long src = b.db_off[e], n = b.db_off[e + 1] - src;
-    const long long base = b.obj_off[(long)(AUG_MAX_CAND + 1) * j + k];
-    const long long end = min(b.obj_off[(long)(AUG_MAX_CAND + 1) * j + k + 1], b.out_off[j + 1]);
+    const long long base = b.obj_off[(long)(PLACE_MAX_CAND + 1) * j + k];
+    const long long end = min(b.obj_off[(long)(PLACE_MAX_CAND + 1) * j + k + 1], b.out_off[j + 1]);
     const double move = b.cand_move[q];
     for (long long i = (long long)blockIdx.x * AUG_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * AUG_THREADS) {
         float4 p = *(const float4 *)(b.db_pts + 4 * (src + i));
@@ -308,13 +202,7 @@ static int aug_check(const prcnn_aug_batch *b, const char *what)
     return PRCNN_OK;
 }
 
-static dim3 aug_grid(const prcnn_aug_batch *b, int ny)
-{
-    const int per = AUG_THREADS / WAVE;
-    return dim3((unsigned)std::max(1, (b->max_tiles + per - 1) / per), (unsigned)ny);
-}
-
-extern "C" int prcnn_aug_max_candidates(void) { return AUG_MAX_CAND; }
+extern "C" int prcnn_aug_max_candidates(void) { return PLACE_MAX_CAND; }
 
 extern "C" int prcnn_aug_place(const prcnn_aug_batch *b, void *stream)
 {
@@ -323,9 +211,9 @@ extern "C" int prcnn_aug_place(const prcnn_aug_batch *b, void *stream)
     if (b->n_scenes == 0 || b->n_jobs == 0) return PRCNN_OK;
     PRCNN_REQUIRE(sizeof(SceneCalib) == 35 * sizeof(float), "aug_place: calib layout");
     hipStream_t st = (hipStream_t)stream;
-    if (b->max_tiles > 0) hipLaunchKernelGGL(aug_filter_kernel, aug_grid(b, b->n_scenes), dim3(AUG_THREADS), 0, st, *b);
+    if (b->max_tiles > 0) hipLaunchKernelGGL(aug_filter_kernel, tile_grid(b->max_tiles, b->n_scenes, AUG_THREADS), dim3(AUG_THREADS), 0, st, *b);
     hipLaunchKernelGGL(aug_place_kernel, dim3(b->n_jobs), dim3(WAVE), 0, st, *b);
-    if (b->max_tiles > 0) hipLaunchKernelGGL(aug_count_kernel, aug_grid(b, b->n_jobs), dim3(AUG_THREADS), 0, st, *b);
+    if (b->max_tiles > 0) hipLaunchKernelGGL(aug_count_kernel, tile_grid(b->max_tiles, b->n_jobs, AUG_THREADS), dim3(AUG_THREADS), 0, st, *b);
     hipLaunchKernelGGL(aug_scan_kernel, dim3(b->n_jobs), dim3(AUG_THREADS), 0, st, *b);
     return check_launch("aug_place");
 }
@@ -338,7 +226,7 @@ extern "C" int prcnn_aug_write(const prcnn_aug_batch *b, void *stream)
     PRCNN_REQUIRE(b->out_off && b->obj_off && b->out, "aug_write: null pointer");
     PRCNN_REQUIRE(b->n_db == 0 || b->db_pts, "aug_write: null pointer");
     hipStream_t st = (hipStream_t)stream;
-    if (b->max_tiles > 0) hipLaunchKernelGGL(aug_write_kernel, aug_grid(b, b->n_jobs), dim3(AUG_THREADS), 0, st, *b);
-    if (b->n_db > 0) hipLaunchKernelGGL(aug_objects_kernel, dim3(4, AUG_MAX_CAND, b->n_jobs), dim3(AUG_THREADS), 0, st, *b);
+    if (b->max_tiles > 0) hipLaunchKernelGGL(aug_write_kernel, tile_grid(b->max_tiles, b->n_jobs, AUG_THREADS), dim3(AUG_THREADS), 0, st, *b);
+    if (b->n_db > 0) hipLaunchKernelGGL(aug_objects_kernel, dim3(4, PLACE_MAX_CAND, b->n_jobs), dim3(AUG_THREADS), 0, st, *b);
     return check_launch("aug_write");
 }

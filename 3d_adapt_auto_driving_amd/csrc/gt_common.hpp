@@ -1,6 +1,6 @@
-// gt_common.hpp -- the point-in-box test of the GT-database and augmented-scene kernels (csrc/gt_database.hip, csrc/aug_scene.hip):
-// roipool3d.cpp:82-95 as csrc/roipool_host.hip restates it, over a staged box record.  Moved out of gt_database.hip unchanged (the
-// arithmetic is described there; pinned by tests/golden g18).
+// gt_common.hpp -- the point-in-box test of the GT-database, augmented-scene and training-input kernels (csrc/gt_database.hip,
+// csrc/aug_scene.hip, csrc/train_input.hip, csrc/placement.hpp): roipool3d.cpp:82-95 as csrc/roipool_host.hip restates it, over a
+// staged box record.  Moved out of gt_database.hip unchanged (the arithmetic is described there; pinned by tests/golden g18).
 #pragma once
 #include "common.hpp"
 #include <math.h>

@@ -20,34 +20,15 @@
 #include "common.hpp"
 #include "gt_common.hpp"
 #include "point_chains.hpp"
+#include "scene_tiles.hpp"
 #include <math.h>
-#include <algorithm>
 
 namespace prcnn {
 
 constexpr int GT_THREADS = 256;                  // 4 waves = 4 tiles per workgroup
 
-struct GtTile {
-    int s, tile, ntile, n, idx, lane;
-    long p0;
-    bool live, valid;
-};
-
-__device__ __forceinline__ void gt_tile(const prcnn_gt_batch &b, GtTile &c)
-{
-    c.s = blockIdx.y;
-    c.tile = blockIdx.x * (GT_THREADS / WAVE) + threadIdx.x / WAVE;
-    c.ntile = b.tile_off[c.s + 1] - b.tile_off[c.s];
-    c.p0 = b.pt_off[c.s];
-    c.n = b.pt_off[c.s + 1] - b.pt_off[c.s];
-    c.lane = threadIdx.x & (WAVE - 1);
-    c.idx = c.tile * WAVE + c.lane;
-    c.live = c.tile < c.ntile;
-    c.valid = c.live && c.idx < c.n;
-}
-
 // one coalesced 16-byte load per lane; rect = [p 1] . M with M (4, 3) row-major
-__device__ __forceinline__ float4 gt_load_rect(const prcnn_gt_batch &b, const GtTile &c)
+__device__ __forceinline__ float4 gt_load_rect(const prcnn_gt_batch &b, const SceneTile &c)
 {
     float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
     if (c.valid) {
@@ -85,8 +66,8 @@ __device__ __forceinline__ void gt_stage_boxes(const prcnn_gt_batch &b, int g0, 
 __global__ __launch_bounds__(GT_THREADS) void gt_count_kernel(prcnn_gt_batch b)
 {
     __shared__ float sbox[GT_CHUNK * GT_REC];
-    GtTile c;
-    gt_tile(b, c);
+    SceneTile c;
+    scene_tile<GT_THREADS>(b, blockIdx.y, c);
     const float4 r = gt_load_rect(b, c);
     const int bb = b.box_off[c.s], nb = b.box_off[c.s + 1] - bb;
     int *cnt = b.bt_cnt + b.bt_off[c.s] + c.tile;
@@ -109,24 +90,8 @@ __global__ __launch_bounds__(GT_THREADS) void gt_scan_kernel(prcnn_gt_batch b)
     const int bb = b.box_off[s], nb = b.box_off[s + 1] - bb;
     if (k >= nb) return;
     const int nt = b.tile_off[s + 1] - b.tile_off[s];
-    int *a = b.bt_cnt + b.bt_off[s] + (long)k * nt;
-    const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
-    int carry = 0;
-    for (int i0 = 0; i0 < nt; i0 += GT_THREADS) {
-        const int i = i0 + threadIdx.x;
-        const int v = i < nt ? a[i] : 0;
-        int inc = v;
-        for (int d = 1; d < WAVE; d <<= 1) { const int o = __shfl_up(inc, d, 64); if (lane >= d) inc += o; }
-        __syncthreads();
-        if (lane == WAVE - 1) wsum[w] = inc;
-        __syncthreads();
-        int before = carry, tot = 0;
-#pragma unroll
-        for (int q = 0; q < GT_THREADS / WAVE; ++q) { if (q < w) before += wsum[q]; tot += wsum[q]; }
-        if (i < nt) a[i] = before + inc - v;
-        carry += tot;
-    }
-    if (threadIdx.x == 0) b.counts[bb + k] = carry;
+    const int tot = tile_exclusive_scan<GT_THREADS>(b.bt_cnt + b.bt_off[s] + (long)k * nt, nt, 1, wsum);
+    if (threadIdx.x == 0) b.counts[bb + k] = tot;
 }
 
 // ---- pass 3: the objects' rows
@@ -134,8 +99,8 @@ __global__ __launch_bounds__(GT_THREADS) void gt_write_kernel(prcnn_gt_batch b)
 {
     __shared__ float sbox[GT_CHUNK * GT_REC];
     __shared__ long long sbase[GT_CHUNK + 1];
-    GtTile c;
-    gt_tile(b, c);
+    SceneTile c;
+    scene_tile<GT_THREADS>(b, blockIdx.y, c);
     const float4 r = gt_load_rect(b, c);
     const unsigned long long below = (1ull << c.lane) - 1ull;
     const int bb = b.box_off[c.s], nb = b.box_off[c.s + 1] - bb;
@@ -175,12 +140,6 @@ static int gt_check(const prcnn_gt_batch *b, const char *what)
     return PRCNN_OK;
 }
 
-static dim3 gt_grid(const prcnn_gt_batch *b)
-{
-    const int per = GT_THREADS / WAVE;
-    return dim3((unsigned)std::max(1, (b->max_tiles + per - 1) / per), (unsigned)b->n_scenes);
-}
-
 extern "C" int prcnn_gt_box_chunk(void) { return GT_CHUNK; }
 
 /* HOST: (cos ry, sin ry) of every box as the host path's point test evaluates them (csrc/roipool_host.hip point_in_box) */
@@ -203,7 +162,7 @@ extern "C" int prcnn_gt_extract_count(const prcnn_gt_batch *b, void *stream)
     if (rc != PRCNN_OK) return rc;
     if (b->n_scenes == 0 || b->max_boxes == 0 || b->max_tiles == 0) return PRCNN_OK;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(gt_count_kernel, gt_grid(b), dim3(GT_THREADS), 0, st, *b);
+    hipLaunchKernelGGL(gt_count_kernel, tile_grid(b->max_tiles, b->n_scenes, GT_THREADS), dim3(GT_THREADS), 0, st, *b);
     hipLaunchKernelGGL(gt_scan_kernel, dim3(b->max_boxes, b->n_scenes), dim3(GT_THREADS), 0, st, *b);
     return check_launch("gt_extract_count");
 }
@@ -214,6 +173,6 @@ extern "C" int prcnn_gt_extract_write(const prcnn_gt_batch *b, void *stream)
     if (rc != PRCNN_OK) return rc;
     if (b->n_scenes == 0 || b->max_boxes == 0 || b->max_tiles == 0) return PRCNN_OK;
     PRCNN_REQUIRE(b->out_off && b->out, "gt_extract_write: null pointer");
-    hipLaunchKernelGGL(gt_write_kernel, gt_grid(b), dim3(GT_THREADS), 0, (hipStream_t)stream, *b);
+    hipLaunchKernelGGL(gt_write_kernel, tile_grid(b->max_tiles, b->n_scenes, GT_THREADS), dim3(GT_THREADS), 0, (hipStream_t)stream, *b);
     return check_launch("gt_extract_write");
 }

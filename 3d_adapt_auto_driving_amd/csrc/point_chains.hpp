@@ -1,6 +1,6 @@
 // point_chains.hpp -- the per-point arithmetic of the KITTI loaders that more than one unit needs (csrc/input_stage.hip,
-// csrc/aug_scene.hip): lidar -> rectified camera frame -> image, and the in-image / depth test, as the reference's numpy code
-// evaluates them (pinned by tests/golden g11).  Moved out of input_stage.hip unchanged.
+// csrc/gt_database.hip, csrc/aug_scene.hip, csrc/train_input.hip): lidar -> rectified camera frame -> image, the in-image / depth
+// test, and the valid-point filter built from them, as the reference's numpy code evaluates them (pinned by tests/golden g11).
 #pragma once
 #include "common.hpp"
 
@@ -64,6 +64,42 @@ __device__ __forceinline__ bool in_image(const SceneCalib &cb, float x, float y,
     const float u = __fdiv_rn(hu, zz), v = __fdiv_rn(hv, zz);
     const float depth = __fsub_rn(hw, cb.p2[11]);
     return u >= 0.f && u < cb.img_w && v >= 0.f && v < cb.img_h && depth >= 0.f;
+}
+
+// The valid-point filter of ONE raw point (generate_aug_scene.py:241-249, kitti_rcnn_dataset.py:251-274 get_rpn_sample): -> its rect
+// coordinates and whether it is in the image, at depth >= 0 and inside ``scope`` (x, y, z ranges; null: no range test).  ``single``:
+// the scene has ONE point, so numpy took the gemv forms above.  ``is_rect``: the point is in the rect frame already.  The reference
+// compares the f32 coordinates with a float64 scope (70.4 is not an f32): compared in double.
+__device__ __forceinline__ bool rect_valid_point(const float4 p, const SceneCalib &cb, bool single, bool is_rect, const double *scope,
+                                                 float &x, float &y, float &z)
+{
+    x = p.x; y = p.y; z = p.z;
+    if (!is_rect) {
+        LidarToRect l2r;
+        l2r.set(cb);
+        if (single) {
+            x = gemv_row(p.x, p.y, p.z, l2r.m[0][0], l2r.m[1][0], l2r.m[2][0], l2r.m[3][0]);
+            y = gemv_row(p.x, p.y, p.z, l2r.m[0][1], l2r.m[1][1], l2r.m[2][1], l2r.m[3][1]);
+            z = gemv_row(p.x, p.y, p.z, l2r.m[0][2], l2r.m[1][2], l2r.m[2][2], l2r.m[3][2]);
+        } else {
+            x = l2r.row(0, p.x, p.y, p.z); y = l2r.row(1, p.x, p.y, p.z); z = l2r.row(2, p.x, p.y, p.z);
+        }
+    }
+    bool ok;
+    if (single) {
+        const float hu = gemv_row_t(x, y, z, cb.p2[0], cb.p2[1], cb.p2[2], cb.p2[3]);
+        const float hv = gemv_row_t(x, y, z, cb.p2[4], cb.p2[5], cb.p2[6], cb.p2[7]);
+        const float hw = gemv_row_t(x, y, z, cb.p2[8], cb.p2[9], cb.p2[10], cb.p2[11]);
+        const float zz = (z == 0.f) ? 1e-9f : z;
+        const float u = __fdiv_rn(hu, zz), v = __fdiv_rn(hv, zz);
+        ok = u >= 0.f && u < cb.img_w && v >= 0.f && v < cb.img_h && __fsub_rn(hw, cb.p2[11]) >= 0.f;
+    } else {
+        ok = in_image(cb, x, y, z);
+    }
+    if (scope)
+        ok = ok && (double)x >= scope[0] && (double)x <= scope[1] && (double)y >= scope[2] && (double)y <= scope[3] &&
+             (double)z >= scope[4] && (double)z <= scope[5];
+    return ok;
 }
 
 }  // namespace prcnn

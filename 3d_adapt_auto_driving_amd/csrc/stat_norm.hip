@@ -16,8 +16,8 @@
 // multiply-adds over the inner index, first term a plain product (tests/golden g15 pins it; a one-row product against a transposed
 // matrix goes through another kernel with the middle term first, see patch_back).  cos / sin / the scale factors come from the host.
 #include "common.hpp"
+#include "scene_tiles.hpp"
 #include <math.h>
-#include <algorithm>
 
 namespace prcnn {
 
@@ -105,29 +105,11 @@ __device__ __forceinline__ double wave_max(double v)
     return v;
 }
 
-struct TileCtx {
-    int s, tile, ntile, p0, n, idx, lane;
-    bool valid;
-};
-
-__device__ __forceinline__ bool tile_ctx(const prcnn_sn_batch &b, TileCtx &c)
-{
-    c.s = blockIdx.y;
-    c.tile = blockIdx.x * (SN_THREADS / WAVE) + threadIdx.x / WAVE;
-    c.ntile = b.tile_off[c.s + 1] - b.tile_off[c.s];
-    c.p0 = b.pt_off[c.s];
-    c.n = b.pt_off[c.s + 1] - c.p0;
-    c.lane = threadIdx.x & (WAVE - 1);
-    c.idx = c.tile * WAVE + c.lane;
-    c.valid = c.tile < c.ntile && c.idx < c.n;
-    return c.tile < c.ntile;
-}
-
-__device__ __forceinline__ void load_rect(const prcnn_sn_batch &b, const TileCtx &c, double r[3])
+__device__ __forceinline__ void load_rect(const prcnn_sn_batch &b, const SceneTile &c, double r[3])
 {
     r[0] = r[1] = r[2] = 0.0;
     if (c.valid) {
-        const float *p = b.velo + 4 * (long)(c.p0 + c.idx);
+        const float *p = b.velo + 4 * (c.p0 + c.idx);
         velo_to_rect(((const SnCalib *)b.calib)[c.s], p[0], p[1], p[2], r);
     }
 }
@@ -144,8 +126,8 @@ __device__ __forceinline__ void load_boxes(const prcnn_sn_batch &b, int b0, int 
 __global__ __launch_bounds__(SN_THREADS) void sn_count_kernel(prcnn_sn_batch b)
 {
     __shared__ double sbox[SN_CHUNK * SN_GEOM];
-    TileCtx c;
-    const bool live = tile_ctx(b, c);
+    SceneTile c;
+    scene_tile<SN_THREADS>(b, blockIdx.y, c);
     double r[3];
     load_rect(b, c, r);
     const int bb = b.box_off[c.s], nb = b.box_off[c.s + 1] - bb;
@@ -153,7 +135,7 @@ __global__ __launch_bounds__(SN_THREADS) void sn_count_kernel(prcnn_sn_batch b)
     for (int k0 = 0; k0 < nb; k0 += SN_CHUNK) {
         const int kn = min(SN_CHUNK, nb - k0);
         load_boxes(b, bb + k0, kn, sbox);
-        if (!live) continue;
+        if (!c.live) continue;
         for (int k = 0; k < kn; ++k) {
             const double *bx = sbox + k * SN_GEOM;
             double f[3];
@@ -178,32 +160,10 @@ __global__ __launch_bounds__(SN_THREADS) void sn_count_kernel(prcnn_sn_batch b)
             }
         }
     }
-    if (live) {
+    if (c.live) {
         const unsigned long long rem = __ballot(c.valid && !any);
         if (c.lane == 0) b.rem_cnt[b.tile_off[c.s] + c.tile] = __popcll(rem);
     }
-}
-
-// exclusive scan of a[0..n) in place (one workgroup); returns the total to every thread
-__device__ int block_exclusive_scan(int *a, int n, int *wsum)
-{
-    const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
-    int carry = 0;
-    for (int i0 = 0; i0 < n; i0 += SN_THREADS) {
-        const int i = i0 + threadIdx.x;
-        const int v = i < n ? a[i] : 0;
-        int inc = v;
-        for (int d = 1; d < WAVE; d <<= 1) { const int o = __shfl_up(inc, d, 64); if (lane >= d) inc += o; }
-        __syncthreads();
-        if (lane == WAVE - 1) wsum[w] = inc;
-        __syncthreads();
-        int before = carry, tot = 0;
-#pragma unroll
-        for (int q = 0; q < SN_THREADS / WAVE; ++q) { if (q < w) before += wsum[q]; tot += wsum[q]; }
-        if (i < n) a[i] = before + inc - v;
-        carry += tot;
-    }
-    return carry;
 }
 
 // ---- pass 1b: one workgroup per (box | remainder, scene): ordered offsets over the tiles, totals
@@ -215,10 +175,10 @@ __global__ __launch_bounds__(SN_THREADS) void sn_scan_kernel(prcnn_sn_batch b)
     if (k > nb) return;
     const int nt = b.tile_off[s + 1] - b.tile_off[s];
     if (k < nb) {
-        const int tot = block_exclusive_scan(b.bt_cnt + b.bt_off[s] + (long)k * nt, nt, wsum);
+        const int tot = tile_exclusive_scan<SN_THREADS>(b.bt_cnt + b.bt_off[s] + (long)k * nt, nt, 1, wsum);
         if (threadIdx.x == 0) b.boxi[(long)(bb + k) * SN_BOXI + SN_CNT] = tot;
     } else {
-        const int tot = block_exclusive_scan(b.rem_cnt + b.tile_off[s], nt, wsum);
+        const int tot = tile_exclusive_scan<SN_THREADS>(b.rem_cnt + b.tile_off[s], nt, 1, wsum);
         if (threadIdx.x == 0) b.scene_i[4 * s + 0] = tot;
     }
 }
@@ -229,8 +189,8 @@ __global__ __launch_bounds__(SN_THREADS) void sn_conflict_kernel(prcnn_sn_batch 
     __shared__ double sbox[SN_CCHUNK * SN_GEOM];
     __shared__ double sbnd[SN_CCHUNK * SN_NRATIO * 5];      // per box and ratio: xlo, xhi, ylo, zlo, zhi
     __shared__ int scnt[SN_CCHUNK];
-    TileCtx c;
-    const bool live = tile_ctx(b, c);
+    SceneTile c;
+    scene_tile<SN_THREADS>(b, blockIdx.y, c);
     double r[3];
     load_rect(b, c, r);
     const int bb = b.box_off[c.s], nb = b.box_off[c.s + 1] - bb;
@@ -252,7 +212,7 @@ __global__ __launch_bounds__(SN_THREADS) void sn_conflict_kernel(prcnn_sn_batch 
             if (q == 0) scnt[k] = b.boxi[(long)(bb + k0 + k) * SN_BOXI + SN_CNT];
         }
         __syncthreads();
-        if (!live) continue;
+        if (!c.live) continue;
         for (int k = 0; k < kn; ++k) {
             if (scnt[k] == 0) continue;
             double f[3];
@@ -323,8 +283,8 @@ __global__ __launch_bounds__(SN_THREADS) void sn_write_kernel(prcnn_sn_batch b)
 {
     __shared__ double sbox[SN_WCHUNK * SN_BOXD];
     __shared__ int sbase[SN_WCHUNK], scnt[SN_WCHUNK];
-    TileCtx c;
-    const bool live = tile_ctx(b, c);
+    SceneTile c;
+    scene_tile<SN_THREADS>(b, blockIdx.y, c);
     double r[3];
     load_rect(b, c, r);
     const SnCalib &cal = ((const SnCalib *)b.calib)[c.s];
@@ -341,7 +301,7 @@ __global__ __launch_bounds__(SN_THREADS) void sn_write_kernel(prcnn_sn_batch b)
             scnt[i] = b.boxi[(long)(bb + k0 + i) * SN_BOXI + SN_CNT];
         }
         __syncthreads();
-        if (!live) continue;
+        if (!c.live) continue;
         for (int k = 0; k < kn; ++k) {
             if (scnt[k] == 0) continue;
             const double *bx = sbox + k * SN_BOXD;
@@ -361,7 +321,7 @@ __global__ __launch_bounds__(SN_THREADS) void sn_write_kernel(prcnn_sn_batch b)
             }
         }
     }
-    const bool rest = live && c.valid && !any;
+    const bool rest = c.valid && !any;
     const unsigned long long m = __ballot(rest);
     if (rest) {
         const long pos = o0 + b.scene_i[4 * c.s + 1] + b.rem_cnt[b.tile_off[c.s] + c.tile] + __popcll(m & below);
@@ -408,19 +368,13 @@ static int sn_check(const prcnn_sn_batch *b, const char *what)
     return PRCNN_OK;
 }
 
-static dim3 sn_grid(const prcnn_sn_batch *b)
-{
-    const int per = SN_THREADS / WAVE;
-    return dim3((unsigned)std::max(1, (b->max_tiles + per - 1) / per), (unsigned)b->n_scenes);
-}
-
 extern "C" int prcnn_stat_norm_count(const prcnn_sn_batch *b, void *stream)
 {
     const int rc = sn_check(b, "stat_norm_count");
     if (rc != PRCNN_OK) return rc;
     if (b->n_scenes == 0) return PRCNN_OK;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(sn_count_kernel, sn_grid(b), dim3(SN_THREADS), 0, st, *b);
+    hipLaunchKernelGGL(sn_count_kernel, tile_grid(b->max_tiles, b->n_scenes, SN_THREADS), dim3(SN_THREADS), 0, st, *b);
     hipLaunchKernelGGL(sn_scan_kernel, dim3(b->max_boxes + 1, b->n_scenes), dim3(SN_THREADS), 0, st, *b);
     return check_launch("stat_norm_count");
 }
@@ -431,7 +385,7 @@ extern "C" int prcnn_stat_norm_choose(const prcnn_sn_batch *b, void *stream)
     if (rc != PRCNN_OK) return rc;
     if (b->n_scenes == 0) return PRCNN_OK;
     hipStream_t st = (hipStream_t)stream;
-    if (b->avoid && b->max_boxes > 0) hipLaunchKernelGGL(sn_conflict_kernel, sn_grid(b), dim3(SN_THREADS), 0, st, *b);
+    if (b->avoid && b->max_boxes > 0) hipLaunchKernelGGL(sn_conflict_kernel, tile_grid(b->max_tiles, b->n_scenes, SN_THREADS), dim3(SN_THREADS), 0, st, *b);
     hipLaunchKernelGGL(sn_choose_kernel, dim3((b->n_scenes + 63) / 64), dim3(64), 0, st, *b, b->n_scenes);
     return check_launch("stat_norm_choose");
 }
@@ -442,7 +396,7 @@ extern "C" int prcnn_stat_norm_write(const prcnn_sn_batch *b, void *stream)
     if (rc != PRCNN_OK) return rc;
     PRCNN_REQUIRE(b->out_off && b->out, "stat_norm_write: null pointer");
     if (b->n_scenes == 0) return PRCNN_OK;
-    hipLaunchKernelGGL(sn_write_kernel, sn_grid(b), dim3(SN_THREADS), 0, (hipStream_t)stream, *b);
+    hipLaunchKernelGGL(sn_write_kernel, tile_grid(b->max_tiles, b->n_scenes, SN_THREADS), dim3(SN_THREADS), 0, (hipStream_t)stream, *b);
     return check_launch("stat_norm_write");
 }
 

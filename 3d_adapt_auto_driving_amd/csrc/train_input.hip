@@ -1,16 +1,16 @@
 // train_input.hip -- the RPN training input stage (lib/datasets/kitti_rcnn_dataset.py:249-382 get_rpn_sample in TRAIN mode, with
 // apply_gt_aug_to_one_scene :428-531 and data_augmentation :533-591) for a batch of ragged scenes.  No draw of the loader depends on
 // a geometric result except through a few counts, so the host owns the random stream (train_input.py): it hands every scene the
-// ordered list of at most TRAIN_MAX_CAND database objects that reach the overlap test, and, after one round trip of a few ints per
+// ordered list of at most PLACE_MAX_CAND database objects that reach the overlap test, and, after one round trip of a few ints per
 // scene, the sampler's choice as ranks.
 //
-// Points of all scenes sit back to back (pt_off), cut into 64-point tiles (tile_off), as in aug_scene.hip; the label boxes' overlap
+// Points of all scenes sit back to back (pt_off), cut into 64-point tiles (tile_off; scene_tiles.hpp); the label boxes' overlap
 // records sit back to back too (box_off).  The database's points stay resident (db_pts).
-//   place   filter   velo -> rect -> image, valid flag (aug_scene.hip's, point_chains.hpp; a scene read from rectified_data is rect
+//   place   filter   velo -> rect -> image, valid flag (point_chains.hpp, as aug_scene.hip; a scene read from rectified_data is rect
 //                    already);
 //           place    one wave per scene: every candidate against every label box (LDS chunks of GT_CHUNK) and against every earlier
 //                    candidate under the ONLINE rule (kitti_utils.get_iou3d), all pairs in parallel, then the greedy accept in try
-//                    order from the ballots' conflict words.  The candidate x box matrix is never stored;
+//                    order from the ballots' conflict words (placement.hpp).  The candidate x box matrix is never stored;
 //           count    one flag byte per point: bit 0 kept (valid and inside no accepted box enlarged by h + 2), bit 1 near (z < 40);
 //                    per tile the kept and the near counts;  scan: ordered exclusive scans per scene, the totals -> sizes;
 //           compact  the kept / near / far points' indices in point order (every position is a prefix count: no atomics);
@@ -28,72 +28,27 @@
 //   scale     f32 product with the f32-rounded scale; flip: x negated; intensity - 0.5 in f32.
 #include "common.hpp"
 #include "gt_common.hpp"
+#include "placement.hpp"
 #include "point_chains.hpp"
+#include "scene_tiles.hpp"
 #include <math.h>
-#include <algorithm>
 
 namespace prcnn {
 
 constexpr int TR_THREADS = 256;                  // 4 waves = 4 tiles per workgroup
-constexpr int TRAIN_MAX_CAND = 16;               // candidates per scene (GT_EXTRA_NUM + 1 of the shipped configs)
-constexpr int TR_SIZES = TRAIN_MAX_CAND + 3;     // ints per scene in sizes: kept, near kept, accepted, the accepted slots in order
+constexpr int TR_SIZES = PLACE_MAX_CAND + 3;     // ints per scene in sizes: kept, near kept, accepted, the accepted slots in order
 constexpr int TR_REC = 11;                       // doubles per overlap record: 4 x (x, z), min_h, max_h, volume term
-
-struct TrTile {
-    int s, tile, ntile, n, idx, lane;
-    long p0;
-    bool live, valid;
-};
-
-__device__ __forceinline__ void tr_tile(const prcnn_train_batch &b, int s, TrTile &c)
-{
-    c.s = s;
-    c.tile = blockIdx.x * (TR_THREADS / WAVE) + threadIdx.x / WAVE;
-    c.ntile = b.tile_off[s + 1] - b.tile_off[s];
-    c.p0 = b.pt_off[s];
-    c.n = b.pt_off[s + 1] - b.pt_off[s];
-    c.lane = threadIdx.x & (WAVE - 1);
-    c.idx = c.tile * WAVE + c.lane;
-    c.live = c.tile < c.ntile;
-    c.valid = c.live && c.idx < c.n;
-}
 
 // ---- filter
 __global__ __launch_bounds__(TR_THREADS) void train_filter_kernel(prcnn_train_batch b)
 {
-    TrTile c;
-    tr_tile(b, b.scene_begin + blockIdx.y, c);
+    SceneTile c;
+    scene_tile<TR_THREADS>(b, b.scene_begin + blockIdx.y, c);
     if (!c.valid) return;
-    const SceneCalib cb = ((const SceneCalib *)b.calib)[c.s];
     const float4 p = *(const float4 *)(b.velo + 4 * (c.p0 + c.idx));
-    float x = p.x, y = p.y, z = p.z;
-    if (!b.is_rect[c.s]) {
-        LidarToRect l2r;
-        l2r.set(cb);
-        if (c.n == 1) {
-            x = gemv_row(p.x, p.y, p.z, l2r.m[0][0], l2r.m[1][0], l2r.m[2][0], l2r.m[3][0]);
-            y = gemv_row(p.x, p.y, p.z, l2r.m[0][1], l2r.m[1][1], l2r.m[2][1], l2r.m[3][1]);
-            z = gemv_row(p.x, p.y, p.z, l2r.m[0][2], l2r.m[1][2], l2r.m[2][2], l2r.m[3][2]);
-        } else {
-            x = l2r.row(0, p.x, p.y, p.z); y = l2r.row(1, p.x, p.y, p.z); z = l2r.row(2, p.x, p.y, p.z);
-        }
-    }
-    bool ok;
-    if (c.n == 1) {
-        const float hu = gemv_row_t(x, y, z, cb.p2[0], cb.p2[1], cb.p2[2], cb.p2[3]);
-        const float hv = gemv_row_t(x, y, z, cb.p2[4], cb.p2[5], cb.p2[6], cb.p2[7]);
-        const float hw = gemv_row_t(x, y, z, cb.p2[8], cb.p2[9], cb.p2[10], cb.p2[11]);
-        const float zz = (z == 0.f) ? 1e-9f : z;
-        const float u = __fdiv_rn(hu, zz), v = __fdiv_rn(hv, zz);
-        ok = u >= 0.f && u < cb.img_w && v >= 0.f && v < cb.img_h && __fsub_rn(hw, cb.p2[11]) >= 0.f;
-    } else {
-        ok = in_image(cb, x, y, z);
-    }
-    if (b.reduce_by_range) {
-        const double *sc = b.scope;
-        ok = ok && (double)x >= sc[0] && (double)x <= sc[1] && (double)y >= sc[2] && (double)y <= sc[3] && (double)z >= sc[4] &&
-             (double)z <= sc[5];
-    }
+    float x, y, z;
+    const bool ok = rect_valid_point(p, ((const SceneCalib *)b.calib)[c.s], c.n == 1, b.is_rect[c.s] != 0,
+                                     b.reduce_by_range ? b.scope : nullptr, x, y, z);
     *(float4 *)(b.rect + 4 * (c.p0 + c.idx)) = make_float4(x, y, z, p.w);
     b.valid[c.p0 + c.idx] = ok ? 1 : 0;
 }
@@ -160,72 +115,27 @@ __device__ __forceinline__ bool tr_conflict(const double *a, const double *b)
 __global__ __launch_bounds__(WAVE) void train_place_kernel(prcnn_train_batch b)
 {
     __shared__ double sorig[GT_CHUNK * TR_REC];
-    __shared__ double scand[TRAIN_MAX_CAND * TR_REC];
+    __shared__ double scand[PLACE_MAX_CAND * TR_REC];
     __shared__ unsigned srej;
     const int s = b.scene_begin + blockIdx.x, lane = threadIdx.x;
-    const int nc = min(max(b.cand_n[s], 0), TRAIN_MAX_CAND);
-    int *sizes = b.sizes + (long)TR_SIZES * s;
-    if (lane == 0) srej = 0u;
-    for (int p = lane; p < nc * TR_REC; p += WAVE) scand[p] = b.cand_rec[(long)TRAIN_MAX_CAND * TR_REC * s + p];
-    // every candidate against the scene's label boxes
-    const int bb = b.box_off[s], nb = b.box_off[s + 1] - bb;
-    for (int k0 = 0; k0 < nb; k0 += GT_CHUNK) {
-        const int kn = min(GT_CHUNK, nb - k0);
-        __syncthreads();
+    const int nc = min(max(b.cand_n[s], 0), PLACE_MAX_CAND);
+    for (int p = lane; p < nc * TR_REC; p += WAVE) scand[p] = b.cand_rec[(long)PLACE_MAX_CAND * TR_REC * s + p];
+    // every candidate against the scene's label boxes, then against every earlier candidate (the records come enlarged)
+    const int bb = b.box_off[s];
+    const unsigned rej = place_reject_by_labels<double, TR_REC, tr_conflict>(scand, nc, sorig, b.box_off[s + 1] - bb, &srej, [&](int k0, int kn) {
         for (int p = lane; p < kn * TR_REC; p += WAVE) sorig[p] = b.box_rec[(long)TR_REC * (bb + k0) + p];
-        __syncthreads();
-        for (int p = lane; p < nc * kn; p += WAVE) {
-            const int c = p / kn, k = p - c * kn;
-            if (tr_conflict(scand + c * TR_REC, sorig + k * TR_REC)) atomicOr(&srej, 1u << c);   // LDS; an OR has no order
-        }
-    }
-    __syncthreads();
-    const unsigned rej = srej;
-    // every candidate i against every earlier one jj: row i of an iteration's ballot is its 16-bit conflict word
-    unsigned conf[TRAIN_MAX_CAND];
-#pragma unroll
-    for (int it = 0; it < TRAIN_MAX_CAND * TRAIN_MAX_CAND / WAVE; ++it) {
-        const int p = it * WAVE + lane, i = p / TRAIN_MAX_CAND, jj = p % TRAIN_MAX_CAND;
-        bool bad = false;
-        if (i < nc && jj < i && !((rej >> i) & 1u) && !((rej >> jj) & 1u)) bad = tr_conflict(scand + i * TR_REC, scand + jj * TR_REC);
-        const unsigned long long m = __ballot(bad);
-#pragma unroll
-        for (int q = 0; q < WAVE / TRAIN_MAX_CAND; ++q)
-            conf[it * (WAVE / TRAIN_MAX_CAND) + q] = (unsigned)(m >> (TRAIN_MAX_CAND * q)) & 0xffffu;
-    }
-    // the greedy accept in try order (uniform in the wave)
-    unsigned acc = 0u;
-    int n_acc = 0;
-#pragma unroll
-    for (int i = 0; i < TRAIN_MAX_CAND; ++i) {
-        if (i < nc && !((rej >> i) & 1u) && !(conf[i] & acc)) {
-            acc |= 1u << i;
-            if (lane == 0) sizes[3 + n_acc] = i;
-            ++n_acc;
-        }
-    }
-    if (lane == 0) {
-        sizes[2] = n_acc;
-        for (int k = n_acc; k < TRAIN_MAX_CAND; ++k) sizes[3 + k] = -1;
-    }
+    });
+    place_accept_greedy<double, TR_REC, tr_conflict>(scand, scand, nc, rej, b.sizes + (long)TR_SIZES * s + 3);
 }
 
 // ---- count: the flag byte of every point, the kept and near counts per tile
 __global__ __launch_bounds__(TR_THREADS) void train_count_kernel(prcnn_train_batch b)
 {
-    __shared__ float sbox[TRAIN_MAX_CAND * GT_REC];
+    __shared__ float sbox[PLACE_MAX_CAND * GT_REC];
     const int s = b.scene_begin + blockIdx.y;
-    TrTile c;
-    tr_tile(b, s, c);
-    const int *sizes = b.sizes + (long)TR_SIZES * s;
-    const int na = min(max(sizes[2], 0), TRAIN_MAX_CAND);
-    if ((int)threadIdx.x < na) {
-        const int slot = min(max(sizes[3 + threadIdx.x], 0), TRAIN_MAX_CAND - 1);
-        const long q = (long)TRAIN_MAX_CAND * s + slot;
-        const float *bx = b.cand_box + 7L * q;
-        gt_box_record(bx, __fadd_rn(bx[3], 2.0f), b.cand_trig[2 * q], b.cand_trig[2 * q + 1], sbox + threadIdx.x * GT_REC);
-    }
-    __syncthreads();
+    SceneTile c;
+    scene_tile<TR_THREADS>(b, s, c);
+    const int na = stage_accepted(b.sizes + (long)TR_SIZES * s + 3, (long)PLACE_MAX_CAND * s, b.cand_box, b.cand_trig, sbox);
     if (!c.live) return;
     bool keep = false, near = false;
     if (c.valid) {
@@ -249,26 +159,10 @@ __global__ __launch_bounds__(TR_THREADS) void train_scan_kernel(prcnn_train_batc
     __shared__ int wsum[TR_THREADS / WAVE];
     const int s = b.scene_begin + blockIdx.x;
     const int nt = b.tile_off[s + 1] - b.tile_off[s];
-    const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
     for (int which = 0; which < 2; ++which) {
-        int *a = b.tile_cnt + 2L * b.tile_off[s] + which;
-        int carry = 0;
-        for (int i0 = 0; i0 < nt; i0 += TR_THREADS) {
-            const int i = i0 + threadIdx.x;
-            const int v = i < nt ? a[2L * i] : 0;
-            int inc = v;
-            for (int d = 1; d < WAVE; d <<= 1) { const int o = __shfl_up(inc, d, 64); if (lane >= d) inc += o; }
-            __syncthreads();
-            if (lane == WAVE - 1) wsum[w] = inc;
-            __syncthreads();
-            int before = carry, tot = 0;
-#pragma unroll
-            for (int q = 0; q < TR_THREADS / WAVE; ++q) { if (q < w) before += wsum[q]; tot += wsum[q]; }
-            if (i < nt) a[2L * i] = before + inc - v;
-            carry += tot;
-        }
-        if (threadIdx.x == 0) b.sizes[(long)TR_SIZES * s + which] = carry;
-        __syncthreads();
+        const int tot = tile_exclusive_scan<TR_THREADS>(b.tile_cnt + 2L * b.tile_off[s] + which, nt, 2, wsum);
+        if (threadIdx.x == 0) b.sizes[(long)TR_SIZES * s + which] = tot;
+        __syncthreads();                                               // wsum is read to the end of a scan and written by the next
     }
 }
 
@@ -276,8 +170,8 @@ __global__ __launch_bounds__(TR_THREADS) void train_scan_kernel(prcnn_train_batc
 __global__ __launch_bounds__(TR_THREADS) void train_compact_kernel(prcnn_train_batch b)
 {
     const int s = b.scene_begin + blockIdx.y;
-    TrTile c;
-    tr_tile(b, s, c);
+    SceneTile c;
+    scene_tile<TR_THREADS>(b, s, c);
     if (!c.live) return;
     const unsigned f = c.valid ? b.flag[c.p0 + c.idx] : 0u;
     const bool keep = f & 1u, near = f & 2u;
@@ -309,9 +203,9 @@ __global__ __launch_bounds__(TR_THREADS) void train_emit_kernel(prcnn_train_batc
             const int idx = b.lists[kind * total + p0 + val];
             if (idx >= 0 && idx < n) p = *(const float4 *)(b.rect + 4 * (p0 + idx));
         }
-    } else if (kind == 3 && val < b.n_db_rows && slot < TRAIN_MAX_CAND) {
+    } else if (kind == 3 && val < b.n_db_rows && slot < PLACE_MAX_CAND) {
         p = *(const float4 *)(b.db_pts + 4 * val);
-        p.y = __double2float_rn(__dsub_rn((double)p.y, b.cand_move[(long)TRAIN_MAX_CAND * s + slot]));
+        p.y = __double2float_rn(__dsub_rn((double)p.y, b.cand_move[(long)PLACE_MAX_CAND * s + slot]));
     }
     const double *g = b.aug + 6L * s;                              // m00, m10, m01, m11, scale, flags (1 rotation, 2 scaling, 4 flip)
     const int flags = (int)g[5];
@@ -353,12 +247,6 @@ static int train_check(const prcnn_train_batch *b, const char *what)
     return PRCNN_OK;
 }
 
-static dim3 train_grid(const prcnn_train_batch *b)
-{
-    const int per = TR_THREADS / WAVE;
-    return dim3((unsigned)std::max(1, (b->max_tiles + per - 1) / per), (unsigned)(b->scene_end - b->scene_begin));
-}
-
 extern "C" int prcnn_train_place(const prcnn_train_batch *b, void *stream)
 {
     const int rc = train_check(b, "train_place");
@@ -369,11 +257,11 @@ extern "C" int prcnn_train_place(const prcnn_train_batch *b, void *stream)
     const int ns = b->scene_end - b->scene_begin;
     if (ns == 0) return PRCNN_OK;
     hipStream_t st = (hipStream_t)stream;
-    if (b->max_tiles > 0) hipLaunchKernelGGL(train_filter_kernel, train_grid(b), dim3(TR_THREADS), 0, st, *b);
+    if (b->max_tiles > 0) hipLaunchKernelGGL(train_filter_kernel, tile_grid(b->max_tiles, ns, TR_THREADS), dim3(TR_THREADS), 0, st, *b);
     hipLaunchKernelGGL(train_place_kernel, dim3(ns), dim3(WAVE), 0, st, *b);
-    if (b->max_tiles > 0) hipLaunchKernelGGL(train_count_kernel, train_grid(b), dim3(TR_THREADS), 0, st, *b);
+    if (b->max_tiles > 0) hipLaunchKernelGGL(train_count_kernel, tile_grid(b->max_tiles, ns, TR_THREADS), dim3(TR_THREADS), 0, st, *b);
     hipLaunchKernelGGL(train_scan_kernel, dim3(ns), dim3(TR_THREADS), 0, st, *b);
-    if (b->max_tiles > 0) hipLaunchKernelGGL(train_compact_kernel, train_grid(b), dim3(TR_THREADS), 0, st, *b);
+    if (b->max_tiles > 0) hipLaunchKernelGGL(train_compact_kernel, tile_grid(b->max_tiles, ns, TR_THREADS), dim3(TR_THREADS), 0, st, *b);
     return check_launch("train_place");
 }
 

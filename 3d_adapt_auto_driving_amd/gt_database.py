@@ -33,10 +33,8 @@ import types
 import numpy as np
 
 from . import kitti_io
-from .stat_norm import Object3d
-
-TILE = 64                                # points per tile of the device passes (one wave)
-MAX_IO_WORKERS = 16
+from .kitti_io import Object3d
+from .scene_batch import MAX_IO_WORKERS, TILE, as_calib, boxes_of_labels, check_device, class_whitelist, cum, offsets_to_device, pack_scenes, to_device  # noqa: F401
 CLASS_TUPLES = {"Car": ("Background", "Car"), "People": ("Background", "Pedestrian", "Cyclist"),
                 "Pedestrian": ("Background", "Pedestrian"), "Cyclist": ("Background", "Cyclist")}
 VALID_LEVELS = ("Easy", "Moderate", "Hard")
@@ -78,7 +76,7 @@ def reference_object3d():
 
 
 def reference_object_dict(obj):
-    """A parsed label line (stat_norm.Object3d) -> the reference Object3d's attributes, in its order and with its value types."""
+    """A parsed label line (kitti_io.Object3d) -> the reference Object3d's attributes, in its order and with its value types."""
     pos = obj.t
     score = obj.score if obj.score is not None else -1.0
     level = obj.get_obj_level()
@@ -108,16 +106,12 @@ def save_gt_database(gt_database, path):
 
 
 # ------------------------------------------------------------------------------------------------------------------ extraction
-def _as_calib(c):
-    return c if isinstance(c, kitti_io.Calibration) else kitti_io.Calibration(c)
-
-
 def _norm_scenes(scenes):
     out = []
     for pts, calib, boxes in scenes:
         pts = np.ascontiguousarray(np.asarray(pts, dtype=np.float32).reshape(-1, 4))
         boxes = np.ascontiguousarray(np.asarray(boxes, dtype=np.float32).reshape(-1, 7))
-        out.append((pts, _as_calib(calib), boxes))
+        out.append((pts, as_calib(calib), boxes))
     return out
 
 
@@ -175,29 +169,24 @@ class GtExtractor:
         if S == 0:
             return []
         device = self.device
-        n = np.array([len(p) for p, _, _ in scenes], dtype=np.int64)
-        nt = (n + TILE - 1) // TILE
-        nb = np.array([len(b) for _, _, b in scenes], dtype=np.int64)
-        cum = lambda a: np.concatenate([[0], np.cumsum(a)]).astype(np.int64)
-        pt_off, tile_off, box_off, bt_off = cum(n), cum(nt), cum(nb), cum(nb * nt)
-        if pt_off[-1] >= 2 ** 31 or bt_off[-1] >= 2 ** 31:
+        pk = pack_scenes([p for p, _, _ in scenes], [len(b) for _, _, b in scenes], [c for _, c, _ in scenes])
+        nb, box_off, bt_off = pk.nb, pk.box_off, cum(pk.nb * pk.nt)
+        if pk.pt_off[-1] >= 2 ** 31 or bt_off[-1] >= 2 ** 31:
             raise ValueError("gt_database batch too large: split it")
-        nbox, npts = int(box_off[-1]), int(pt_off[-1])
+        nbox, npts = int(box_off[-1]), int(pk.pt_off[-1])
         empty = [[(np.zeros((0, 3), np.float32), np.zeros((0,), np.float32)) for _ in range(int(g))] for g in nb]
         if nbox == 0 or npts == 0:
             return empty
-        velo = np.concatenate([p for p, _, _ in scenes])
         boxes = np.concatenate([b for _, _, b in scenes])
-        calib = np.stack([np.dot(c.V2C.T, c.R0.T).astype(np.float32).reshape(12) for _, c, _ in scenes])
         trig = box_trig(boxes)
-        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
-        t_pt, t_tile, t_box = dev(pt_off.astype(np.int32)), dev(tile_off.astype(np.int32)), dev(box_off.astype(np.int32))
-        t_bt, t_velo, t_calib, t_boxes, t_trig = dev(bt_off), dev(velo), dev(calib), dev(boxes), dev(trig)
+        dev = to_device(device)
+        t_pt, t_tile, t_box = offsets_to_device(pk, dev)
+        t_bt, t_velo, t_calib, t_boxes, t_trig = dev(bt_off), dev(pk.velo), dev(pk.calib), dev(boxes), dev(trig)
         need = max(1, int(bt_off[-1]))
         if self._bt is None or self._bt.numel() < need or self._bt.device != t_velo.device:
             self._bt = torch.empty(need, dtype=torch.int32, device=device)
         t_cnt = torch.zeros(nbox, dtype=torch.int32, device=device)
-        b = _GtBatch(S, int(nt.max()), int(nb.max()), 0, t_pt.data_ptr(), t_tile.data_ptr(), t_box.data_ptr(), t_bt.data_ptr(),
+        b = _GtBatch(S, pk.max_tiles, int(nb.max()), 0, t_pt.data_ptr(), t_tile.data_ptr(), t_box.data_ptr(), t_bt.data_ptr(),
                      t_velo.data_ptr(), t_calib.data_ptr(), t_boxes.data_ptr(), t_trig.data_ptr(), self._bt.data_ptr(),
                      t_cnt.data_ptr(), None, None)
         stream = C.c_void_p(_lib.current_stream(t_velo))
@@ -232,8 +221,7 @@ def extract_objects(scenes, device="cuda"):
     inside two boxes goes to both."""
     if device == "cpu":
         return [_extract_cpu(p, c, b) for p, c, b in _norm_scenes(scenes)]
-    if not str(device).startswith("cuda"):
-        raise ValueError("device must be 'cpu' or 'cuda[:i]'")
+    check_device(device)
     ex = _extractors.get(str(device))
     if ex is None:
         ex = _extractors[str(device)] = GtExtractor(device)
@@ -249,9 +237,9 @@ def class_tuple(class_name):
 
 def filtrate_objects(obj_list, classes):
     """Objects of ``classes`` whose level is Easy / Moderate / Hard."""
-    out = []
+    out, white = [], class_whitelist(classes)
     for obj in obj_list:
-        if obj.cls_type not in classes:
+        if obj.cls_type not in white:
             continue
         obj.get_obj_level()
         if obj.level_str not in VALID_LEVELS:
@@ -306,10 +294,7 @@ def generate_gt_database(root, split="train", class_name="Car", subsample=-1, sh
         calib = kitti_io.Calibration(os.path.join(base, "calib", "%06d.txt" % sample_id))
         with open(os.path.join(base, "label_2", "%06d.txt" % sample_id)) as f:
             objs = filtrate_objects([Object3d(line) for line in f.readlines()], classes)
-        boxes = np.zeros((len(objs), 7), dtype=np.float32)
-        for k, obj in enumerate(objs):
-            boxes[k, 0:3], boxes[k, 3], boxes[k, 4], boxes[k, 5], boxes[k, 6] = obj.t, obj.h, obj.w, obj.l, obj.ry
-        return pts, calib, boxes, objs
+        return pts, calib, boxes_of_labels(objs), objs
 
     batch_size = max(1, int(batch_size))
     groups = [[int(i) for i in ids[k:k + batch_size]] for k in range(0, len(ids), batch_size)]

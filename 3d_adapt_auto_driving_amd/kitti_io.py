@@ -9,6 +9,7 @@ Directory layout expected (same as the reference): ``<root>/KITTI/object/{traini
 image_2}/%06d.*`` and ``<root>/KITTI/ImageSets/<split>.txt``.
 """
 import os
+import struct
 
 import numpy as np
 
@@ -70,6 +71,69 @@ def valid_flag(pts_rect, pts_img, depth, img_shape, area_scope=None):
         flag &= (pts_rect[:, 0] >= x0) & (pts_rect[:, 0] <= x1) & (pts_rect[:, 1] >= y0) & (pts_rect[:, 1] <= y1) \
             & (pts_rect[:, 2] >= z0) & (pts_rect[:, 2] <= z1)
     return flag
+
+
+# ------------------------------------------------------------------------------------------------- label lines, image headers
+def _cls_id(cls_type):
+    return {"Car": 1, "Pedestrian": 2, "Cyclist": 3, "Van": 4}.get(cls_type, -1)
+
+
+class Object3d:
+    """One KITTI label line, parsed as utils/object_3d.py does (box2d and t float32, the rest Python floats)."""
+
+    def __init__(self, line):
+        label = line.strip().split(" ")
+        self.src = line
+        self.cls_type = label[0]
+        self.cls_id = _cls_id(self.cls_type)
+        self.trucation = float(label[1])           # sic: the reference's field name
+        self.occlusion = float(label[2])
+        self.alpha = float(label[3])
+        self.box2d = np.array([float(v) for v in label[4:8]], dtype=np.float32)
+        self.h, self.w, self.l = float(label[8]), float(label[9]), float(label[10])
+        self.t = np.array([float(v) for v in label[11:14]], dtype=np.float32)
+        self.ry = float(label[14])
+        self.score = None
+        if len(label) == 16:
+            try:
+                self.score = float(label[15])
+            except ValueError:
+                self.track_id = label[15]
+
+    def get_obj_level(self):
+        """The KITTI difficulty of the label (lib/utils/object3d.py get_obj_level): sets ``level_str`` / ``level``, -> level."""
+        height = float(self.box2d[3]) - float(self.box2d[1]) + 1
+        if height >= 40 and self.trucation <= 0.15 and self.occlusion <= 0:
+            self.level_str, self.level = "Easy", 1
+        elif height >= 25 and self.trucation <= 0.3 and self.occlusion <= 1:
+            self.level_str, self.level = "Moderate", 2
+        elif height >= 25 and self.trucation <= 0.5 and self.occlusion <= 2:
+            self.level_str, self.level = "Hard", 3
+        else:
+            self.level_str, self.level = "UnKnown", 4
+        return self.level
+
+    def to_kitti_format(self):
+        vals = (self.cls_type, self.trucation, int(self.occlusion), self.alpha, self.box2d[0], self.box2d[1], self.box2d[2],
+                self.box2d[3], self.h, self.w, self.l, self.t[0], self.t[1], self.t[2], self.ry)
+        fmt = "%s %.2f %d %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f"
+        if self.score is not None:
+            return (fmt + " %.2f") % (vals + (self.score,))
+        return fmt % vals
+
+
+def read_label_lines(path):
+    with open(path) as f:
+        return [line.rstrip() for line in f]
+
+
+def png_size(path):
+    """(width, height) from a PNG file's IHDR chunk."""
+    with open(path, "rb") as f:
+        head = f.read(24)
+    if len(head) < 24 or head[:8] != b"\x89PNG\r\n\x1a\n" or head[12:16] != b"IHDR":
+        raise ValueError("%s is not a PNG file" % path)
+    return struct.unpack(">II", head[16:24])
 
 
 class KittiSource:

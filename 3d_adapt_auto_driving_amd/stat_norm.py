@@ -27,16 +27,16 @@ import ctypes as C
 import json
 import os
 import shutil
-import struct
 from itertools import chain
 
 import numpy as np
 
+from .kitti_io import Object3d, png_size, read_label_lines  # noqa: F401  (the label parser lives there; imported from here too)
+from .scene_batch import MAX_IO_WORKERS, TILE, as_calib, check_device, cum, offsets_to_device, pack_scenes, to_device  # noqa: F401
+
 RATIOS = np.arange(1, -0.1, -0.1)      # the avoid_conflict trial ratios; the last one is 2.22e-16, not 0
 STAT_SUBJECTS = ("height", "width", "length")
 SPLIT_DIRS = {"train": "training", "val": "training", "test": "testing"}
-TILE = 64                                # points per tile of the device passes (one wave)
-MAX_IO_WORKERS = 16
 
 # per-box records of csrc/stat_norm.hip (SN_* there)
 _BOXD, _BOX_SCALE, _BOX_FSCALE, _BOX_SHIFT, _BOX_FLAG1, _BOX_FLAG2 = 64, 17, 50, 53, 57, 58
@@ -44,59 +44,6 @@ _BOXI, _BI_CNT, _BI_RIDX, _BI_BASE = 16, 0, 13, 14
 
 
 # ---------------------------------------------------------------------------------------------------------------- labels, calib
-def _cls_id(cls_type):
-    return {"Car": 1, "Pedestrian": 2, "Cyclist": 3, "Van": 4}.get(cls_type, -1)
-
-
-class Object3d:
-    """One KITTI label line, parsed as utils/object_3d.py does (box2d and t float32, the rest Python floats)."""
-
-    def __init__(self, line):
-        label = line.strip().split(" ")
-        self.src = line
-        self.cls_type = label[0]
-        self.cls_id = _cls_id(self.cls_type)
-        self.trucation = float(label[1])           # sic: the reference's field name
-        self.occlusion = float(label[2])
-        self.alpha = float(label[3])
-        self.box2d = np.array([float(v) for v in label[4:8]], dtype=np.float32)
-        self.h, self.w, self.l = float(label[8]), float(label[9]), float(label[10])
-        self.t = np.array([float(v) for v in label[11:14]], dtype=np.float32)
-        self.ry = float(label[14])
-        self.score = None
-        if len(label) == 16:
-            try:
-                self.score = float(label[15])
-            except ValueError:
-                self.track_id = label[15]
-
-    def get_obj_level(self):
-        """The KITTI difficulty of the label (lib/utils/object3d.py get_obj_level): sets ``level_str`` / ``level``, -> level."""
-        height = float(self.box2d[3]) - float(self.box2d[1]) + 1
-        if height >= 40 and self.trucation <= 0.15 and self.occlusion <= 0:
-            self.level_str, self.level = "Easy", 1
-        elif height >= 25 and self.trucation <= 0.3 and self.occlusion <= 1:
-            self.level_str, self.level = "Moderate", 2
-        elif height >= 25 and self.trucation <= 0.5 and self.occlusion <= 2:
-            self.level_str, self.level = "Hard", 3
-        else:
-            self.level_str, self.level = "UnKnown", 4
-        return self.level
-
-    def to_kitti_format(self):
-        vals = (self.cls_type, self.trucation, int(self.occlusion), self.alpha, self.box2d[0], self.box2d[1], self.box2d[2],
-                self.box2d[3], self.h, self.w, self.l, self.t[0], self.t[1], self.t[2], self.ry)
-        fmt = "%s %.2f %d %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f"
-        if self.score is not None:
-            return (fmt + " %.2f") % (vals + (self.score,))
-        return fmt % vals
-
-
-def read_label_lines(path):
-    with open(path) as f:
-        return [line.rstrip() for line in f]
-
-
 def parse_calib(text):
     """A KITTI calib file's text -> dict of float arrays (the date-like lines are skipped, as the reference does)."""
     data = {}
@@ -278,7 +225,7 @@ def device_paint_occlusion(rects_per_scene, h, w, device="cuda"):
     import torch
     from . import _lib
     n = [len(r) for r in rects_per_scene]
-    off = np.concatenate([[0], np.cumsum(n)]).astype(np.int32)
+    off = cum(n).astype(np.int32)
     flat = [r for rs in rects_per_scene for r in _resolved(rs, h, w)]
     rects = torch.from_numpy(np.asarray(flat, dtype=np.int32).reshape(-1, 4) if flat else np.zeros((1, 4), np.int32)).to(device)
     offs = torch.from_numpy(off).to(device)
@@ -393,29 +340,24 @@ def _rescale_device(scenes, mapping, avoid_conflict, align_front, classes, devic
     import torch
     from . import _lib
     S = len(scenes)
-    n = np.array([len(v) for v, _, _ in scenes], dtype=np.int64)
-    nt = (n + TILE - 1) // TILE
     boxes = [[o for o in objs if o.cls_type in classes] for _, objs, _ in scenes]
-    nb = np.array([len(b) for b in boxes], dtype=np.int64)
-    cum = lambda a: np.concatenate([[0], np.cumsum(a)])
-    pt_off, tile_off, box_off, bt_off = cum(n), cum(nt), cum(nb), cum(nb * nt)
-    if pt_off[-1] >= 2 ** 31 or bt_off[-1] >= 2 ** 31:
+    pk = pack_scenes([v for v, _, _ in scenes], [len(b) for b in boxes])
+    nb, box_off, tile_off, bt_off = pk.nb, pk.box_off, pk.tile_off, cum(pk.nb * pk.nt)
+    if pk.pt_off[-1] >= 2 ** 31 or bt_off[-1] >= 2 ** 31:
         raise ValueError("stat_norm batch too large: split it")
     nbox = int(box_off[-1])
     flat = [o for b in boxes for o in b]
     boxd = np.stack([_box_record(o, mapping, avoid_conflict) for o in flat]) if flat else np.zeros((1, _BOXD))
     calib = np.stack([np.concatenate([c.V2C.ravel(), c.R0.ravel(), c.R0_inv.ravel(), c.C2V.ravel()]) for _, _, c in scenes])
-    velo = np.ascontiguousarray(np.concatenate([np.asarray(v, dtype=np.float32)[:, :4] for v, _, _ in scenes]).reshape(-1, 4)) \
-        if pt_off[-1] else np.zeros((1, 4), np.float32)
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
-    t_pt, t_tile, t_box = dev(pt_off.astype(np.int32)), dev(tile_off.astype(np.int32)), dev(box_off.astype(np.int32))
-    t_bt, t_velo, t_calib, t_boxd = dev(bt_off), dev(velo), dev(calib), dev(boxd)
+    dev = to_device(device)
+    t_pt, t_tile, t_box = offsets_to_device(pk, dev)
+    t_bt, t_velo, t_calib, t_boxd = dev(bt_off), dev(pk.velo), dev(calib), dev(boxd)
     t_boxi = torch.zeros((max(1, nbox), _BOXI), dtype=torch.int32, device=device)
     t_mm = torch.tensor([np.inf] * 3 + [-np.inf] * 3, dtype=torch.float64, device=device).repeat(max(1, nbox), 1)
     t_btc = torch.zeros(max(1, int(bt_off[-1])), dtype=torch.int32, device=device)
     t_rem = torch.zeros(max(1, int(tile_off[-1])), dtype=torch.int32, device=device)
     t_sc = torch.zeros((S, 4), dtype=torch.int32, device=device)
-    b = _SnBatch(S, int(nt.max()) if S else 0, int(nb.max()) if S else 0, int(bool(avoid_conflict)),
+    b = _SnBatch(S, pk.max_tiles, int(nb.max()) if S else 0, int(bool(avoid_conflict)),
                  t_pt.data_ptr(), t_tile.data_ptr(), t_box.data_ptr(), t_bt.data_ptr(), t_velo.data_ptr(), t_calib.data_ptr(),
                  t_boxd.data_ptr(), t_boxi.data_ptr(), t_mm.data_ptr(), t_btc.data_ptr(), t_rem.data_ptr(), t_sc.data_ptr(), None, None)
     stream = C.c_void_p(_lib.current_stream(t_velo))
@@ -452,14 +394,6 @@ def _rescale_device(scenes, mapping, avoid_conflict, align_front, classes, devic
 
 
 # -------------------------------------------------------------------------------------------------------------------- public
-def _as_calib(c):
-    if isinstance(c, Calib):
-        return c
-    if isinstance(c, str):
-        return Calib.from_file(c)
-    return Calib(c)
-
-
 def rescale_scenes(velos, label_lines, calibs, mapping, avoid_conflict=False, align_front=False, rescaled_classes=("Car", "Van"),
                    image_size=(1242, 375), device="cuda", names=None, details=False):
     """rescale_ptc + scale_labels for a batch of scenes.
@@ -468,15 +402,15 @@ def rescale_scenes(velos, label_lines, calibs, mapping, avoid_conflict=False, al
     calibs: per scene a Calib, a calib file path or the parse_calib dict; mapping: scale_map(); image_size: (w, h).
     -> (clouds, labels): per scene the (n_out, 4) float32 cloud as format_lidar_data writes it and the label lines as save_labels
     writes them; with ``details`` also the per-box ratios and inside-point counts of the rescaled objects."""
-    if device not in ("cpu",) and not str(device).startswith("cuda"):
-        raise ValueError("device must be 'cpu' or 'cuda[:i]'")
+    check_device(device)
     classes = tuple(rescaled_classes)
     w0, h0 = image_size
     names = list(names) if names is not None else [str(i) for i in range(len(velos))]
     scenes = []
     for v, lines, c in zip(velos, label_lines, calibs):
         objs = [o for o in (Object3d(line) for line in lines) if o.cls_type != "DontCare"]
-        scenes.append((np.asarray(v, dtype=np.float32).reshape(-1, 4), objs, _as_calib(c)))
+        calib = as_calib(c, Calib, Calib.from_file if isinstance(c, str) else Calib)
+        scenes.append((np.asarray(v, dtype=np.float32).reshape(-1, 4), objs, calib))
     if device == "cpu":
         res = [_rescale_cpu(v, o, c, mapping, avoid_conflict, align_front, classes) for v, o, c in scenes]
         clouds, ratios, counts = [r[0] for r in res], [r[1] for r in res], [r[2] for r in res]
@@ -492,15 +426,6 @@ def rescale_scenes(velos, label_lines, calibs, mapping, avoid_conflict=False, al
     if details:
         return clouds, labels, ratios, counts
     return clouds, labels
-
-
-def png_size(path):
-    """(width, height) from a PNG file's IHDR chunk."""
-    with open(path, "rb") as f:
-        head = f.read(24)
-    if len(head) < 24 or head[:8] != b"\x89PNG\r\n\x1a\n" or head[12:16] != b"IHDR":
-        raise ValueError("%s is not a PNG file" % path)
-    return struct.unpack(">II", head[16:24])
 
 
 def convert_tree(src_root, dst_root, src_stats, dst_stats, avoid_conflict=False, align_front=False,

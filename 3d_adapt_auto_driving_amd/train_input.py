@@ -46,10 +46,12 @@ import numpy as np
 
 from . import kitti_io, kitti_utils
 from .aug_scene import road_plane
-from .gt_database import TILE, box_trig, class_tuple, load_gt_database
-from .stat_norm import Object3d, png_size
+from .gt_database import box_trig, class_tuple, load_gt_database
+from .kitti_io import Object3d, png_size
+from .scene_batch import (TILE, boxes_of_labels, check_device, check_pc_range, class_whitelist, cum, database_rows, enlarged,  # noqa: F401
+                          no_label_error, offsets_to_device, pack_scenes, place_on_plane, to_device, valid_points)
 
-MAX_CAND = 16                      # csrc/train_input.hip TRAIN_MAX_CAND = prcnn_aug_max_candidates()
+MAX_CAND = 16                      # csrc/placement.hpp PLACE_MAX_CAND = prcnn_aug_max_candidates()
 TRY_TIMES = 100
 HARD_POINTS = 100                  # an entry with more points is "easy"
 NEAR_DEPTH = 40.0
@@ -249,17 +251,11 @@ class _TrainBatch(C.Structure):
                 ("pts_input", C.c_void_p), ("pts_features", C.c_void_p)]
 
 
-def _cum(a):
-    return np.concatenate([[0], np.cumsum(a)]).astype(np.int64)
-
-
 class RpnTrainInput:
     def __init__(self, root, cfg, gt_database_dir=None, split="train", classes="Car", npoints=16384, npoints_faraway=4000,
                  with_replace=False, seed=None, device="cuda"):
-        dev = str(device)
-        if dev != "cpu" and not dev.startswith("cuda"):
-            raise ValueError("device must be 'cpu' or 'cuda[:i]'")
-        self.root, self.cfg, self.split, self.device = root, cfg, split, dev
+        check_device(device)
+        self.root, self.cfg, self.split, self.device = root, cfg, split, str(device)
         self.classes = class_tuple(classes)
         self.npoints, self.npoints_faraway, self.with_replace = int(npoints), int(npoints_faraway), bool(with_replace)
         self.rng = np.random.RandomState(seed)
@@ -292,14 +288,10 @@ class RpnTrainInput:
         self.db = db
         self.db_box = [np.asarray(e["gt_box3d"], dtype=np.float32).copy() for e in db]
         self.db_pos = [np.array(e["obj"].pos, dtype=np.float32) for e in db]            # the drifting copy (see the docstring)
-        self.db_n = np.array([len(e["points"]) for e in db], dtype=np.int64)
-        self.db_off = _cum(self.db_n)
+        self.db_rows, self.db_n, self.db_off = database_rows(db)
         if self.hard_ratio > 0:
             self.easy = [k for k in range(len(db)) if self.db_n[k] > HARD_POINTS]
             self.hard = [k for k in range(len(db)) if self.db_n[k] <= HARD_POINTS]
-        rows = [np.concatenate((np.asarray(e["points"], np.float32).reshape(-1, 3), np.asarray(e["intensity"], np.float32).reshape(-1, 1)), 1)
-                for e in db]
-        self.db_rows = np.ascontiguousarray(np.concatenate(rows, 0), dtype=np.float32) if rows else np.zeros((0, 4), np.float32)
         if self.device != "cpu":
             import torch
             from . import _lib
@@ -317,18 +309,9 @@ class RpnTrainInput:
         with open(os.path.join(d, "%06d.txt" % sample_id)) as f:
             return [Object3d(line) for line in f.readlines()]
 
-    def check_pc_range(self, xyz):
-        (x0, x1), (y0, y1), (z0, z1) = self.scope
-        return bool((x0 <= float(xyz[0]) <= x1) and (y0 <= float(xyz[1]) <= y1) and (z0 <= float(xyz[2]) <= z1))
-
     def filtrate_objects(self, objs):
-        white = list(self.classes)
-        if _opt(self.cfg, "INCLUDE_SIMILAR_TYPE"):
-            if "Car" in self.classes:
-                white.append("Van")
-            if "Pedestrian" in self.classes:
-                white.append("Person_sitting")
-        return [o for o in objs if o.cls_type in white and not (self.reduce and not self.check_pc_range(o.t))]
+        white = class_whitelist(self.classes, _opt(self.cfg, "INCLUDE_SIMILAR_TYPE"))
+        return [o for o in objs if o.cls_type in white and not (self.reduce and not check_pc_range(o.t, self.scope))]
 
     def load_scene(self, sample_id):
         """-> dict: pts (n, 4) f32 (raw velodyne rows, or rect rows for a pre-made aug scene), is_rect, calib, shape, all_boxes (the
@@ -344,30 +327,12 @@ class RpnTrainInput:
         every = [o for o in objs if o.cls_type != "DontCare"]
         plane = road_plane(os.path.join(self.base, "planes", "%06d.txt" % base_id)) if self.gt_aug else None
         return {"id": sample_id, "pts": np.ascontiguousarray(pts), "is_rect": sample_id >= AUG_ID_BASE, "calib": calib,
-                "shape": (int(height), int(width), 3), "all_boxes": self.objs_to_boxes3d([(o.t, o) for o in every]),
+                "shape": (int(height), int(width), 3), "all_boxes": boxes_of_labels(every),
                 "objs": self.filtrate_objects(objs), "plane": plane}
-
-    @staticmethod
-    def objs_to_boxes3d(pairs):
-        boxes = np.zeros((len(pairs), 7), dtype=np.float32)
-        for k, (pos, o) in enumerate(pairs):
-            boxes[k, 0:3], boxes[k, 3], boxes[k, 4], boxes[k, 5], boxes[k, 6] = pos, o.h, o.w, o.l, o.ry
-        return boxes
 
     def valid_points(self, sc):
         """get_rpn_sample :251-274 in numpy -> (pts_rect (m, 3) f32, intensity (m,) f32)"""
-        calib, pts = sc["calib"], sc["pts"]
-        pts_rect = pts[:, 0:3] if sc["is_rect"] else calib.lidar_to_rect(pts[:, 0:3])
-        pts_img, depth = calib.rect_to_img(pts_rect)
-        shape = sc["shape"]
-        flag = np.logical_and(np.logical_and(pts_img[:, 0] >= 0, pts_img[:, 0] < shape[1]),
-                              np.logical_and(pts_img[:, 1] >= 0, pts_img[:, 1] < shape[0]))
-        flag = np.logical_and(flag, depth >= 0)
-        if self.reduce:
-            x, y, z = (pts_rect[:, k].astype(np.float64) for k in range(3))
-            (x0, x1), (y0, y1), (z0, z1) = self.scope
-            flag = flag & (x >= x0) & (x <= x1) & (y >= y0) & (y <= y1) & (z >= z0) & (z <= z1)
-        return pts_rect[flag][:, 0:3], pts[:, 3][flag]
+        return valid_points(sc["pts"], sc["calib"], sc["shape"], self.scope, sc["is_rect"], self.reduce)
 
     # ------------------------------------------------------------------------------------------------------------ GT-aug: draws
     def _draw_entry(self):
@@ -383,23 +348,19 @@ class RpnTrainInput:
         that reaches the overlap test, after shifting the entry's drifting pos."""
         cfg = self.cfg
         extra = self.rng.randint(10, _opt(cfg, "GT_EXTRA_NUM")) if _opt(cfg, "GT_AUG_RAND_NUM") else _opt(cfg, "GT_EXTRA_NUM")
-        a, b, c, d = plane
         cnt = 0
         for _ in range(TRY_TIMES):
             if cnt > extra:
                 break
             k = self._draw_entry()
-            box = self.db_box[k].copy()
-            if self.reduce and not self.check_pc_range(box[0:3]):
+            if self.reduce and not check_pc_range(self.db_box[k][0:3], self.scope):
                 continue
             if self.db_n[k] < 5:
                 continue
-            cur_height = (-d - a * box[0] - c * box[2]) / b
-            move = np.float64(box[1]) - cur_height
-            box[1] = np.float32(np.float64(box[1]) - move)
+            box, move = place_on_plane(self.db_box[k], plane)
             self.db_pos[k][1] = np.float32(np.float64(self.db_pos[k][1]) - move)
             cnt += 1
-            yield k, box, np.float64(move)
+            yield k, box, move
 
     def replay_candidates(self, plane):
         """The draws of one apply_gt_aug_to_one_scene call -> [(entry, box, move)] in try order (the host replay)"""
@@ -409,24 +370,13 @@ class RpnTrainInput:
                              "(GT_EXTRA_NUM + 1 must be <= %d)" % (len(out), MAX_CAND, MAX_CAND))
         return out
 
-    @staticmethod
-    def _enlarged(box):
-        big = box.copy()
-        big[4] += 0.5
-        big[5] += 0.5
-        return big
-
-    def _no_boxes(self, sc):
-        return ValueError("train_input: sample %06d has no label besides DontCare: the overlap test has nothing to compare with "
-                          "(the reference raises here)" % sc["id"])
-
     # --------------------------------------------------------------------------------------------------------------- labels out
     def _gt_of(self, sc, accepted):
         """-> (gt_boxes3d (g, 7) f32, gt_alpha (g,) f32) of the class-filtered labels and the accepted entries (their DRIFTED pos)"""
-        pairs = [(o.t, o) for o in sc["objs"]] + [(self.db_pos[k], self.db[k]["obj"]) for k in accepted]
-        boxes = self.objs_to_boxes3d(pairs)
-        alpha = np.zeros(len(pairs), dtype=np.float32)
-        for i, (_, o) in enumerate(pairs):
+        objs = list(sc["objs"]) + [self.db[k]["obj"] for k in accepted]
+        boxes = boxes_of_labels(objs, [o.t for o in sc["objs"]] + [self.db_pos[k] for k in accepted])
+        alpha = np.zeros(len(objs), dtype=np.float32)
+        for i, o in enumerate(objs):
             alpha[i] = o.alpha
         return boxes, alpha
 
@@ -439,13 +389,13 @@ class RpnTrainInput:
         pts_rect, inten = self.valid_points(sc)
         accepted, n_scene = [], pts_rect.shape[0]
         if self.gt_aug and rng.rand() < _opt(cfg, "GT_AUG_APPLY_PROB"):
-            cur = overlap_records(self._enlarged_all(sc["all_boxes"]))
+            cur = overlap_records(enlarged(sc["all_boxes"]))
             flag = np.ones(pts_rect.shape[0], dtype=np.int32)
             new_pts, new_int = [], []
             for k, box, move in self._tries(sc["plane"]):
-                rec = overlap_records(self._enlarged(box).reshape(1, 7))[0]
+                rec = overlap_records(enlarged(box).reshape(1, 7))[0]
                 if cur.shape[0] == 0:
-                    raise self._no_boxes(sc)
+                    raise no_label_error("train_input", sc["id"])
                 iou = np.array([record_iou3d(rec, r) for r in cur], dtype=np.float32)
                 ok = bool(iou.max() < 1e-8)
                 self.decisions.append((sample_id, int(k), ok, float(iou.max())))
@@ -493,12 +443,6 @@ class RpnTrainInput:
         info["gt_boxes3d"] = aug_gt
         return info
 
-    def _enlarged_all(self, boxes):
-        cur = boxes.copy()
-        cur[:, 4] += 0.5
-        cur[:, 5] += 0.5
-        return cur
-
     @staticmethod
     def collate(samples):
         """collate_batch (kitti_rcnn_dataset.py:1125-1158) for numpy samples"""
@@ -526,21 +470,16 @@ class RpnTrainInput:
         cfg, rng, device = self.cfg, self.rng, self.device
         S, NP = len(ids), self.npoints
         scenes = [self.load_scene(i) for i in ids]
-        n = np.array([len(sc["pts"]) for sc in scenes], dtype=np.int64)
-        nt = (n + TILE - 1) // TILE
-        nb = np.array([len(sc["all_boxes"]) for sc in scenes], dtype=np.int64)
-        pt_off, tile_off, box_off = _cum(n), _cum(nt), _cum(nb)
-        total = int(pt_off[-1])
+        pk = pack_scenes([sc["pts"] for sc in scenes], [len(sc["all_boxes"]) for sc in scenes], [sc["calib"] for sc in scenes],
+                         [sc["shape"] for sc in scenes])
+        nt, nb, tile_off, total = pk.nt, pk.nb, pk.tile_off, int(pk.pt_off[-1])
         if total >= 2 ** 31 - 64 or S * NP >= 2 ** 40:
             raise ValueError("train_input batch too large: split it")
-        velo = np.concatenate([sc["pts"] for sc in scenes]) if total else np.zeros((1, 4), np.float32)
-        calib = np.stack([kitti_io.DeviceInputStage.pack_calib(sc["calib"], sc["shape"]) for sc in scenes]).astype(np.float32)
-        box_rec = [overlap_records(self._enlarged_all(sc["all_boxes"])) for sc in scenes]
-        box_rec = np.concatenate(box_rec) if box_off[-1] else np.zeros((1, 11), np.float64)
+        box_rec = [overlap_records(enlarged(sc["all_boxes"])) for sc in scenes]
+        box_rec = np.concatenate(box_rec) if pk.box_off[-1] else np.zeros((1, 11), np.float64)
         is_rect = np.array([sc["is_rect"] for sc in scenes], dtype=np.uint8)
-        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
-        t_in = [dev(a) for a in (pt_off.astype(np.int32), tile_off.astype(np.int32), box_off.astype(np.int32), velo, calib,
-                                 self.scope.reshape(6), is_rect, box_rec)]
+        dev = to_device(device)
+        t_in = offsets_to_device(pk, dev) + [dev(a) for a in (pk.velo, pk.calib, self.scope.reshape(6), is_rect, box_rec)]
         t_cn = torch.zeros((S,), dtype=torch.int32, device=device)
         t_crec = torch.zeros((S, MAX_CAND, 11), dtype=torch.float64, device=device)
         t_cbox = torch.zeros((S, MAX_CAND, 7), dtype=torch.float32, device=device)
@@ -557,7 +496,7 @@ class RpnTrainInput:
         t_prect = torch.empty((S, NP, 3), dtype=torch.float32, device=device)
         t_pin = torch.empty((S, NP, C_in), dtype=torch.float32, device=device)
         t_feat = torch.empty((S, NP, 1), dtype=torch.float32, device=device)
-        b = _TrainBatch(S, int(nt.max()) if S else 0, NP, C_in, int(self.reduce), 0, 0, 0, len(self.db_rows) if self.db is not None else 0,
+        b = _TrainBatch(S, pk.max_tiles, NP, C_in, int(self.reduce), 0, 0, 0, len(self.db_rows) if self.db is not None else 0,
                         *[t.data_ptr() for t in t_in], t_cn.data_ptr(), t_crec.data_ptr(), t_cbox.data_ptr(), t_ctrig.data_ptr(),
                         t_cmove.data_ptr(), t_rect.data_ptr(), t_valid.data_ptr(), t_flag.data_ptr(), t_cnt.data_ptr(),
                         t_lists.data_ptr(), t_sizes.data_ptr(), self.t_db.data_ptr() if self.db is not None else None, None, None,
@@ -572,13 +511,13 @@ class RpnTrainInput:
             if self.gt_aug and rng.rand() < _opt(cfg, "GT_AUG_APPLY_PROB"):
                 cand = self.replay_candidates(sc["plane"])
                 if cand and nb[s] == 0:
-                    raise self._no_boxes(sc)
+                    raise no_label_error("train_input", sc["id"])
             self.stats["draw_seconds"] += time.perf_counter() - t0
             if cand:
                 k = len(cand)
                 boxes = np.stack([box for _, box, _ in cand])
                 t_cn[s] = k
-                t_crec[s, :k] = dev(overlap_records(self._enlarged_all(boxes)))
+                t_crec[s, :k] = dev(overlap_records(enlarged(boxes)))
                 t_cbox[s, :k] = dev(boxes)
                 t_ctrig[s, :k] = dev(self.db_trig[[e for e, _, _ in cand]])
                 t_cmove[s, :k] = dev(np.array([mv for _, _, mv in cand], dtype=np.float64))

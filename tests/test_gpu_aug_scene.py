@@ -97,6 +97,32 @@ def test_tile_boundaries_in_one_batch():
     assert len(want[8][0]) == 121 and len(want[-1][0]) == 64
 
 
+def test_scan_carry_past_256_tiles():
+    """16385 points are 257 tiles (the scan's second round holds one tile), 2 * 16384 + 65 points three rounds with a ragged last
+    tile; invalid points among the valid ones.  Two jobs per scene; the clouds are unordered, so the accepted boxes remove points in the
+    first round and in the last, and kept rows land behind a non-zero carry."""
+    rng = np.random.default_rng(1908)
+    places = [(8.0, 12.0), (20.0, 30.0), (30.0, 50.0)]
+    db = [entry(rng, x, z, ry) for (x, z), ry in zip(places, (0.0, 0.7, -1.2))] + [entry(rng, 12.0, 60.0)]
+    sizes = (16385, 2 * 16384 + 65)
+    clouds = [cloud(rng, n - 1500, 1500, places) for n in sizes]
+    clouds[0][-1], clouds[1][-1] = (8.0, 1.0, 12.0, 0.5), (20.0, 1.0, 30.0, 0.5)           # the last tile's last point: under entry 0 / 1
+    scenes = [scene(c) for c in clouds]
+    assert [len(s[0]) for s in scenes] == list(sizes)
+    jobs = [(0, [0, 1, 2]), (0, [2, 0]), (1, [0, 1, 2]), (1, [1])]
+    want = check(scenes, jobs, db)
+    assert [[i for i, _ in acc] for _, acc in want] == [[0, 1, 2], [2, 0], [0, 1, 2], [1]]
+    for (s, _), (rows, acc) in zip(jobs, want):
+        pts, n = scenes[s][0], sizes[s]
+        assert abs(n_valid(scenes[s]) - (n - 1500)) <= 1                                   # (the planted point took a row's place)
+        kept = {r.tobytes() for r in rows[:len(rows) - 40 * len(acc)]}
+        ok = (pts[:, 0] >= 1) & (pts[:, 1] >= 0.05) & (pts[:, 2] <= 66)                      # cloud()'s valid rows (rect = velodyne here)
+        gone = np.array([ok[i] and pts[i].tobytes() not in kept for i in range(n)])
+        assert len(kept) + gone.sum() == n_valid(scenes[s])
+        last = 16384 * ((n - 1) // 16384)                                                  # where the scan's last round begins
+        assert gone[:16384].any() and gone[last:].any() and gone[n - 1]
+
+
 def test_more_label_boxes_than_one_chunk():
     C = G.box_chunk()
     rng = np.random.default_rng(1902)

@@ -87,6 +87,26 @@ def test_tile_boundaries():
     assert len(check([(pts, cal, box)])[0][0][0]) == 1
 
 
+def test_scan_carry_past_256_tiles():
+    """16385 points are 257 tiles (the scan's second round holds one tile), 2 * 16384 + 65 points three rounds with a ragged last
+    tile.  The boxes stand on points of the first, the 257th and the last tile; the cloud is unordered, so every box also holds points
+    of tiles in between, and its rows from the later rounds land behind a non-zero carry."""
+    rng = np.random.default_rng(1805)
+    scenes = []
+    for n in (16385, 2 * 16384 + 65):
+        cal, rect = calib_of(rng), cloud(rng, n)
+        b = helpers.boxes3d(rng, 3)
+        at = rect[[5, 256 * 64, n - 1]]
+        b[:, 0], b[:, 1], b[:, 2] = at[:, 0], at[:, 1] + b[:, 3] / 2, at[:, 2]
+        scenes.append((to_velo(rect, cal, rng), cal, b.astype(np.float32)))
+    want = check(scenes, min_points=6)
+    for (pts, cal, _), objs in zip(scenes, want):
+        rect = kitti_io.Calibration(cal).lidar_to_rect(pts[:, :3])
+        idx = [[int(np.flatnonzero((rect == row).all(1))[0]) for row in p] for p, _ in objs]       # the objects' points in the cloud
+        assert all(i == sorted(i) for i in idx) and 5 in idx[0] and 256 * 64 in idx[1] and len(pts) - 1 in idx[2]
+        assert all(i[0] < 16384 <= i[-1] for i in idx[1:]), idx                  # rows of the first round and rows behind it
+
+
 def test_box_chunk_boundaries():
     C = G.box_chunk()
     rng = np.random.default_rng(1802)

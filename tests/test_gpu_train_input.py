@@ -129,13 +129,14 @@ def test_device_fixed_and_no_gt_aug(tree_db):
 # ------------------------------------------------------------------------------------------------------------------- the sweep
 SWEEP = ((1, 1), (63, 64), (64, 65), (65, 1), (2000, 1))                         # (raw points, non-DontCare labels) per scene
 DB_NODES = ((4, 1), (6, 2), (5, 4), (7, 1), (3, 3), (6, 5))
+BIG_ID, BIG_BACKGROUND = 30, 2 * 16384 + 64 + 37                                 # with its car's 200 points: 517 tiles, the last one ragged
 
 
 @pytest.fixture(scope="module")
 def sweep_db(tmp_path_factory):
     """Two scenes that make the database (cars on DB_NODES, half of them with more than 100 points), then split ``sweep``: clouds
-    of 1, 63, 64, 65 and 2000 points inside the image with 1, 64, 65, 1, 1 label boxes, and ``packed``: a scene on a flat plane whose
-    points all lie inside the (free) database nodes' removal boxes.  Every object stands on train_tree's grid: no pair can come near 0 < IoU < 1e-3."""
+    of 1, 63, 64, 65 and 2000 points inside the image with 1, 64, 65, 1, 1 label boxes, ``packed``: a scene on a flat plane whose
+    points all lie inside the (free) database nodes' removal boxes, and ``big``: a scene of more than 32768 + 64 points.  Every object stands on train_tree's grid: no pair can come near 0 < IoU < 1e-3."""
     root = str(tmp_path_factory.mktemp("sweep_tree"))
     rng = np.random.default_rng(77)
     cars = [train_tree.car_on_node(rng, i, j) for i, j in DB_NODES]
@@ -164,9 +165,15 @@ def sweep_db(tmp_path_factory):
     Rv, tv = cal["Tr_velo_to_cam"][:, :3], cal["Tr_velo_to_cam"][:, 3]
     velo = np.concatenate([(rect @ cal["R0_rect"] - tv) @ Rv, srng.random((len(rect), 1))], 1).astype(np.float32)
     train_tree.write_scene(root, 20, velo, cal, lines, plane)
+    # more than 512 tiles: the scans of the kept and the near counts carry over two rounds of 256 tiles, with a ragged last tile
+    hwl, p, ry = train_tree.car_on_node(rng, 5, 1)
+    lines = [train_tree._line("Car", hwl, p, ry, 0.6)]
+    lidar, cal, plane, _ = train_tree.make_scene(np.random.default_rng(400), lines, [(hwl, p, ry, 200)], BIG_BACKGROUND)
+    train_tree.write_scene(root, BIG_ID, lidar, cal, lines, plane)
     train_tree.write_split(root, "train", (0, 1))
     train_tree.write_split(root, "sweep", ids)
     train_tree.write_split(root, "packed", (20,))
+    train_tree.write_split(root, "big", (BIG_ID,))
     return root, make_db(root)
 
 
@@ -214,3 +221,21 @@ def test_every_scene_point_removed_by_the_pasted_boxes(sweep_db, npoints, farawa
     assert len(accepted) == len(DB_NODES)                                        # every node was pasted
     db_xz = {(float(x), float(z)) for k in accepted for x, _, z in cpu.db[k]["points"]}
     assert all((float(x), float(z)) in db_xz for x, _, z in want["pts_rect"][0])
+
+
+def test_scan_carry_past_512_tiles(sweep_db):
+    """a scene of more than 32768 + 64 raw points with GT-aug on: the strided scan carries over two rounds for the kept and for the near
+    count, and train_compact_kernel ranks the points of the later rounds behind those carries"""
+    cfg = make_cfg(0.6, True, prob=1.0, rand_num=False, extra=15)
+    dev = source(sweep_db, cfg, "cuda", 43, 1024, 128, split="big")
+    cpu = source(sweep_db, cfg, "cpu", 43, 1024, 128, split="big")
+    want = cpu.batch([0])
+    same(dev.batch([0]), want)
+    same_state(dev, cpu)
+    no_discards(cpu)
+    sc = cpu.load_scene(BIG_ID)
+    n_raw, n_valid = len(sc["pts"]), len(cpu.valid_points(sc)[0])
+    assert n_raw > 32768 + 64 and n_raw % 64 != 0
+    assert any(d[2] for d in cpu.decisions) and 1024 < cpu.last_kept[0][1] < n_valid      # points were removed; the near / far sampler ran
+    tail = cpu.valid_points(dict(sc, pts=sc["pts"][32768:]))[0]                           # valid points of the scan's third round, ...
+    assert (tail[:, 2] < 40.0).any() and (tail[:, 2] >= 40.0).any()                       # ... near and far
