@@ -143,6 +143,11 @@ SIGNATURES = {
     "prcnn_aug_write": [_P, _P],
     "prcnn_train_place": [_P, _P],
     "prcnn_train_emit": [_P, _P],
+    "prcnn_rcnn_assign": [_I, _I, _I, _P, _P, _F, _F, _F, _P, _P, _P, _P, _P, _P, _P],
+    "prcnn_rcnn_max_rois": [],
+    "prcnn_rcnn_max_tries": [],
+    "prcnn_rcnn_aug_rois": [_P, _P],
+    "prcnn_rcnn_targets": [_P, _P],
 }
 
 _lib = None

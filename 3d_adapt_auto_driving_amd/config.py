@@ -5,8 +5,8 @@ reading ``cfg.RPN.SA_CONFIG.NPOINTS`` etc. works unchanged, but an ordinary obje
 passed around explicitly; ``make_cfg()`` returns a fresh tree holding the library defaults and
 ``apply_eval_defaults()`` overlays the values the reference evaluates with
 (pointrcnn/tools/cfgs/default.yaml + the eval_mode 'rcnn' switches of eval_rcnn.py:883-887).
-Only keys that the inference path reads are kept; training-only keys are accepted on merge and
-stored, never interpreted.
+Only keys that the inference path and the training input stages read are kept; other training-only
+keys are accepted on merge and stored, never interpreted.
 """
 import copy
 from ast import literal_eval
@@ -39,6 +39,7 @@ _LIBRARY_DEFAULTS = {
     "CLASSES": "Car",
     "INCLUDE_SIMILAR_TYPE": False,
     "PC_REDUCE_BY_RANGE": True,
+    "AUG_DATA": True, "AUG_ROT_RANGE": 18,
     "PC_AREA_SCOPE": np.array([[-40, 40], [-1, 3], [0, 70.4]], dtype=np.float64),
     "CLS_MEAN_SIZE": np.array([[1.52, 1.63, 3.88]], dtype=np.float32),
     "RPN": {
@@ -68,6 +69,9 @@ _LIBRARY_DEFAULTS = {
                       "MLPS": [[128, 128, 128], [128, 128, 256], [256, 256, 512]]},
         "CLS_FC": [256, 256], "REG_FC": [256, 256],
         "LOSS_CLS": "BinaryCrossEntropy", "SCORE_THRESH": 0.3, "NMS_THRESH": 0.1,
+        # the training target stage (rcnn_targets.py; lib/config.py:92-135)
+        "ROI_FG_AUG_TIMES": 10, "REG_AUG_METHOD": "multiple", "CLS_FG_THRESH": 0.6, "CLS_BG_THRESH": 0.45, "CLS_BG_THRESH_LO": 0.05,
+        "REG_FG_THRESH": 0.55, "FG_RATIO": 0.5, "ROI_PER_IMAGE": 64, "HARD_BG_RATIO": 0.6,
     },
     "TRAIN": {"SPLIT": "train", "VAL_SPLIT": "smallval", "RPN_PRE_NMS_TOP_N": 12000,
               "RPN_POST_NMS_TOP_N": 2048, "RPN_NMS_THRESH": 0.85, "RPN_DISTANCE_BASED_PROPOSE": True},

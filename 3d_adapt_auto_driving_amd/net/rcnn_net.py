@@ -1,5 +1,6 @@
-"""Box refinement network (inference branch of pointrcnn/lib/net/rcnn_net.py:14-190): RoI point
-pooling, canonical transform, xyz-up / merge MLPs, three SA levels, cls / reg heads."""
+"""Box refinement network (pointrcnn/lib/net/rcnn_net.py:14-190): RoI point pooling, canonical
+transform, xyz-up / merge MLPs, three SA levels, cls / reg heads.  In training mode with
+RCNN.ROI_SAMPLE_JIT the input comes from the proposal target stage (rcnn_targets.py)."""
 import torch
 import torch.nn as nn
 
@@ -39,6 +40,7 @@ class RCNNNet(nn.Module):
         reg_channel = per_loc_bin_num * 4 + R.NUM_HEAD_BIN * 2 + 3
         reg_channel += (1 if not R.LOC_Y_BY_BIN else loc_y_bin_num * 2)
         self.reg_layer = _head(channel_in, R.REG_FC, reg_channel, R.USE_BN, R.DP_RATIO)
+        self.target_seed, self._targets = None, None
         self.init_weights()
 
     def init_weights(self):
@@ -48,6 +50,15 @@ class RCNNNet(nn.Module):
                 if m.bias is not None:
                     nn.init.constant_(m.bias, 0)
         nn.init.normal_(self.reg_layer[-1].conv.weight, mean=0, std=0.001)
+
+    def target_stage(self, device):
+        """The proposal target stage of the training branch (rcnn_targets.RcnnTargets), made on first use for the inputs' device; it
+        owns its generators (``self.target_seed``, None = unseeded)."""
+        kind = "cuda" if device.type == "cuda" else "cpu"
+        if self._targets is None or self._targets[0] != kind:
+            from ..rcnn_targets import RcnnTargets
+            self._targets = (kind, RcnnTargets(self.cfg, seed=self.target_seed, device=str(device) if kind == "cuda" else "cpu"))
+        return self._targets[1]
 
     def pool_rois(self, input_data):
         """RoI pooling + canonical transform -> pts_input (B*M, NUM_POINTS, 3+extra+C)."""
@@ -70,9 +81,16 @@ class RCNNNet(nn.Module):
 
     def forward(self, input_data):
         R = self.cfg.RCNN
+        target_dict = None
         if self.training:
-            raise NotImplementedError("RCNNNet: training branch (proposal target layer) is out of scope")
-        pts_input = self.pool_rois(input_data) if R.ROI_SAMPLE_JIT else input_data["pts_input"]
+            if not R.ROI_SAMPLE_JIT:
+                raise NotImplementedError("RCNNNet: the training branch needs RCNN.ROI_SAMPLE_JIT (offline RoI samples are out of scope)")
+            with torch.no_grad():                     # lib/net/rcnn_net.py:120-126: the target stage makes the network's input
+                target_dict = self.target_stage(input_data["roi_boxes3d"].device).forward(input_data)
+            pts_input = torch.cat((target_dict["sampled_pts"], target_dict["pts_feature"]), dim=2)
+            target_dict["pts_input"] = pts_input
+        else:
+            pts_input = self.pool_rois(input_data) if R.ROI_SAMPLE_JIT else input_data["pts_input"]
 
         xyz = pts_input[..., 0:3].contiguous()
         if R.USE_RPN_FEATURES:
@@ -92,4 +110,7 @@ class RCNNNet(nn.Module):
 
         rcnn_cls = self.cls_layer(l_features[-1]).transpose(1, 2).contiguous().squeeze(dim=1)
         rcnn_reg = self.reg_layer(l_features[-1]).transpose(1, 2).contiguous().squeeze(dim=1)
-        return {"rcnn_cls": rcnn_cls, "rcnn_reg": rcnn_reg}
+        ret_dict = {"rcnn_cls": rcnn_cls, "rcnn_reg": rcnn_reg}
+        if target_dict is not None:
+            ret_dict.update(target_dict)
+        return ret_dict

@@ -798,6 +798,53 @@ int prcnn_train_place(const prcnn_train_batch *batch, void *stream);
 /* the B x npoints output rows (codes / aug / outputs set by the caller after it has read sizes) */
 int prcnn_train_emit(const prcnn_train_batch *batch, void *stream);
 
+/* RCNN training targets (lib/rpn/proposal_target_layer.py; csrc/rcnn_targets.hip, rcnn_targets.py).  Device pointers.
+ * (a) rois (b, m, 7), gt (b, g, 7) with trailing zero-sum rows -> per RoI the row maximum of the 3-D IoU (max_ov), the first index
+ * that attains it (assign), its list cls (b, m) u8 (0 fg: >= fg_thresh, 1 hard bg: [bg_lo, bg_thresh), 2 easy bg: < bg_lo, 3 none);
+ * lists (b, 3, m) i32 the three ascending index lists; sizes (b, 4) i32 = their lengths and the ground-truth rows that remain: the
+ * block the host reads.  Work: tile_cnt (b, 3, ceil(m / 64)) i32. */
+int prcnn_rcnn_assign(int b, int m, int g, const float *rois, const float *gt, float fg_thresh, float bg_thresh, float bg_lo,
+                      float *max_ov, int *assign, unsigned char *cls, int *tile_cnt, int *lists, int *sizes, void *stream);
+/* sampled RoIs per scene (128) and tries per RoI (64) that prcnn_rcnn_aug_rois holds */
+int prcnn_rcnn_max_rois(void);
+int prcnn_rcnn_max_tries(void);
+/* (b) the noise tries of ONE scene's n_rois sampled RoIs, the first n_fg of them foreground (fg_times tries at most, the others
+ * bg_times = 0 | 1).  rois (m, 7), gt (g, 7), max_ov / assign (m), lists (3, m): the scene's part of (a)'s arrays; pick (n_rois, 2) i32
+ * = (list, position in it) of every sampled RoI.  The pools, indexed by the position in the scene's numpy try stream: keep (n_pool)
+ * u8 = the draw was < 0.2 (the RoI itself is tried), noise (n_pool, 8) f32 = the noise level and the seven uniforms the try at that
+ * position reads from the torch stream; method 0 'single', 1 'multiple'.  Work: table (n_fg, n_pool) f32.  Out: out_rois the tried
+ * boxes that stay, out_pool_rois the same enlarged by pool_extra_width, out_gt (n_rois, 7) their ground truth, out_iou the gt_iou rule,
+ * out_src the source RoI, out_cnt / out_keep the try count and the last try's keep flag, out_tried (n_rois, max(fg_times, bg_times, 1))
+ * every tried IoU (NaN behind them), used[0] = the numpy draws consumed.  The field layout is rcnn_targets.py's _AugArgs. */
+typedef struct prcnn_rcnn_aug {
+    int m, g, n_rois, n_fg, fg_times, bg_times, method, n_pool;
+    float pos_thresh, pool_extra_width;
+    const float *rois, *gt, *max_ov;
+    const int *assign, *lists, *pick;
+    const unsigned char *keep;
+    const float *noise;
+    float *table;
+    float *out_rois, *out_pool_rois, *out_gt, *out_iou;
+    int *out_src, *out_cnt, *out_keep;
+    float *out_tried;
+    int *used;
+} prcnn_rcnn_aug;
+int prcnn_rcnn_aug_rois(const prcnn_rcnn_aug *args, void *stream);
+/* (c) one pass over the pooled rows: pooled (rows, s, cin) f32 and empty (rows) i32 as prcnn_roipool3d leaves them, rows = scenes x
+ * sampled RoIs; aug_rand (3, rows) f32 the rotation / scale / flip uniforms (read when aug_data), rot_scale = pi / AUG_ROT_RANGE ->
+ * rois_out, gt_out (rows, 7) (augmented RoI; target box in the RoI's canonical frame), sampled_pts (rows, s, 3), pts_feature
+ * (rows, s, cin - 3), cls_label and reg_valid (rows) i64.  The field layout is rcnn_targets.py's _TargetArgs. */
+typedef struct prcnn_rcnn_target_args {
+    int rows, s, cin, aug_data;
+    float rot_scale, reg_fg, cls_fg, cls_bg;
+    const float *pooled;
+    const int *empty;
+    const float *aug_rand, *rois_in, *gt_in, *gt_iou;
+    float *rois_out, *gt_out, *sampled_pts, *pts_feature;
+    long long *cls_label, *reg_valid;
+} prcnn_rcnn_target_args;
+int prcnn_rcnn_targets(const prcnn_rcnn_target_args *args, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
