@@ -148,6 +148,10 @@ SIGNATURES = {
     "prcnn_rcnn_max_tries": [],
     "prcnn_rcnn_aug_rois": [_P, _P],
     "prcnn_rcnn_targets": [_P, _P],
+    "prcnn_loss_workspace": [],
+    "prcnn_loss_stats": [_P, _P],
+    "prcnn_cls_loss": [_P, _P],
+    "prcnn_reg_loss": [_P, _P],
 }
 
 _lib = None

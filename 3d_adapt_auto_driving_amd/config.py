@@ -5,7 +5,7 @@ reading ``cfg.RPN.SA_CONFIG.NPOINTS`` etc. works unchanged, but an ordinary obje
 passed around explicitly; ``make_cfg()`` returns a fresh tree holding the library defaults and
 ``apply_eval_defaults()`` overlays the values the reference evaluates with
 (pointrcnn/tools/cfgs/default.yaml + the eval_mode 'rcnn' switches of eval_rcnn.py:883-887).
-Only keys that the inference path and the training input stages read are kept; other training-only
+Only keys that the inference path, the training input stages and the losses read are kept; other training-only
 keys are accepted on merge and stored, never interpreted.
 """
 import copy
@@ -56,6 +56,8 @@ _LIBRARY_DEFAULTS = {
         "FP_MLPS": [[128, 128], [256, 256], [512, 512], [512, 512]],
         "CLS_FC": [128], "REG_FC": [128], "DP_RATIO": 0.5,
         "LOSS_CLS": "DiceLoss", "NMS_TYPE": "normal", "SCORE_THRESH": 0.3,
+        # the training loss (losses.py; lib/config.py:69-73)
+        "FG_WEIGHT": 15, "FOCAL_ALPHA": [0.25, 0.75], "FOCAL_GAMMA": 2.0, "LOSS_WEIGHT": [1.0, 1.0],
     },
     "RCNN": {
         "ENABLED": False, "USE_RPN_FEATURES": True, "USE_MASK": True, "MASK_TYPE": "seg",
@@ -72,6 +74,8 @@ _LIBRARY_DEFAULTS = {
         # the training target stage (rcnn_targets.py; lib/config.py:92-135)
         "ROI_FG_AUG_TIMES": 10, "REG_AUG_METHOD": "multiple", "CLS_FG_THRESH": 0.6, "CLS_BG_THRESH": 0.45, "CLS_BG_THRESH_LO": 0.05,
         "REG_FG_THRESH": 0.55, "FG_RATIO": 0.5, "ROI_PER_IMAGE": 64, "HARD_BG_RATIO": 0.6,
+        # the training loss (losses.py; lib/config.py:126-127: the reference has no FG_WEIGHT or LOSS_WEIGHT for this stage)
+        "FOCAL_ALPHA": [0.25, 0.75], "FOCAL_GAMMA": 2.0,
     },
     "TRAIN": {"SPLIT": "train", "VAL_SPLIT": "smallval", "RPN_PRE_NMS_TOP_N": 12000,
               "RPN_POST_NMS_TOP_N": 2048, "RPN_NMS_THRESH": 0.85, "RPN_DISTANCE_BASED_PROPOSE": True},

@@ -845,6 +845,45 @@ typedef struct prcnn_rcnn_target_args {
 } prcnn_rcnn_target_args;
 int prcnn_rcnn_targets(const prcnn_rcnn_target_args *args, void *stream);
 
+/* Training losses of both stages with their gradients (lib/net/train_functions.py get_rpn_loss / get_rcnn_loss, lib/utils/loss_utils.py;
+ * csrc/losses.hip, losses.py).  Device pointers.  n classification entries = n regression rows of c channels.  One stage's loss is the
+ * three calls below in this order on one stream, with no host read between them; every sum goes through per-block partials in `work`
+ * that are combined in a fixed order (no floating-point atomics: the same input gives the same bits).
+ *   label (n) i64: -1 ignored, 0 background, > 0 foreground; reg_mask (n) i64 or NULL: the regression rows are reg_mask > 0 (NULL:
+ *   label > 0); cls (n) logits; reg (n, c); reg_label (n, 7) = dx dy dz h w l ry; anchors NULL (the anchor is anchor[3]) or (n, 7)
+ *   boxes whose [3:6] is the row's anchor.  cls_kind 0 DiceLoss, 1 SigmoidFocalLoss (alpha, gamma), 2 BinaryCrossEntropy (fg_weight).
+ *   Out: grad_cls (n), grad_reg (n, c) = d loss / d cls, d loss / d reg (rows outside the mask: zeros, written without reading reg),
+ *   parts (PRCNN_LOSS_PARTS) f32, the layout below.  work: prcnn_loss_workspace() doubles.
+ * Decisions (bin labels, the heading's fold, BCE's sigmoid and clamps) are taken in f32 exactly as the reference's operators take
+ * them; the arithmetic on top of them and every sum run in f64 and are rounded to f32 once. */
+enum { PRCNN_LOSS_DICE = 0, PRCNN_LOSS_FOCAL = 1, PRCNN_LOSS_BCE = 2 };
+enum {
+    PRCNN_LP_LOSS = 0, PRCNN_LP_CLS, PRCNN_LP_REG, PRCNN_LP_LOC, PRCNN_LP_ANGLE, PRCNN_LP_SIZE /* x 3 */, PRCNN_LP_CLS_POS, PRCNN_LP_CLS_NEG,
+    PRCNN_LP_X_BIN, PRCNN_LP_Z_BIN, PRCNN_LP_X_RES, PRCNN_LP_Z_RES, PRCNN_LP_Y_BIN, PRCNN_LP_Y_RES, PRCNN_LP_Y_OFFSET, PRCNN_LP_RY_BIN,
+    PRCNN_LP_RY_RES, PRCNN_LP_SIZE_RAW /* before the x 3 */, PRCNN_LP_N_POS, PRCNN_LP_N_NEG, PRCNN_LP_N_VALID, PRCNN_LP_N_REG_FG,
+    PRCNN_LP_DICE_MIN, PRCNN_LP_DICE_MAX, PRCNN_LOSS_PARTS
+};
+typedef struct prcnn_loss_args {
+    int n, c, cls_kind;
+    int xz_fine, y_by_bin, ry_fine;
+    int nbin_loc, nbin_y, nbin_head;
+    float loc_scope, loc_bin, y_scope, y_bin;
+    float alpha, gamma, fg_weight, w_cls, w_reg;
+    float anchor[3];
+    const float *cls;
+    const long long *label, *reg_mask;
+    const float *reg, *reg_label, *anchors;
+    float *grad_cls, *grad_reg, *parts;
+    double *work;
+} prcnn_loss_args;
+int prcnn_loss_workspace(void);
+/* counts of pos / neg / valid / regression rows; for Dice also sum min(p, t) m and sum max(p, t) m */
+int prcnn_loss_stats(const prcnn_loss_args *args, void *stream);
+/* the classification loss's terms and grad_cls (normalisers read from work) */
+int prcnn_cls_loss(const prcnn_loss_args *args, void *stream);
+/* the bin-based regression loss's terms and grad_reg, then the one-block finish that writes parts */
+int prcnn_reg_loss(const prcnn_loss_args *args, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
