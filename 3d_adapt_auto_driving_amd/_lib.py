@@ -1,164 +1,123 @@
-"""ctypes binding of libprcnn_hip.so -- the C ABI declared in include/prcnn_hip.h.
+"""ctypes binding of libprcnn_hip.so, read from include/prcnn_hip.h: the header is the one place where a signature, a struct layout or a
+boundary constant is written.  This module parses it once per process, at import, and builds the argument types, the Structure classes
+and the enum constants from it.
 
-There is NO fallback: if the shared library is missing or an entry point fails, an exception is
-raised.  Nothing in this package imports the CPU oracle.
+There is NO fallback: if the header or the shared library is missing or an entry point fails, an exception is raised.  Nothing in this
+package imports the CPU oracle.
 """
+import collections
 import ctypes as C
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libprcnn_hip.so")
-
-_P = C.c_void_p
-_I = C.c_int
-_F = C.c_float
-_D = C.c_double
-_L = C.c_longlong
-
-class GatherProblem(C.Structure):
-    """prcnn_gather_problem (include/prcnn_hip.h)"""
-    _fields_ = [("b", _I), ("n", _I), ("c1", _I), ("max_tiles", C.c_long), ("P", _P), ("wxyz", _P), ("rowinfo", _P), ("rowdxyz", _P),
-                ("tilecloud", _P), ("hdr", _P), ("out", _P)]
-
-
-class LayerProblem(C.Structure):
-    """prcnn_layer_problem (include/prcnn_hip.h)"""
-    _fields_ = [("hdr", _P), ("rows", C.c_long), ("max_tiles", C.c_long), ("K", _I), ("N", _I), ("n_store", _I), ("A", _P), ("lda", C.c_long),
-                ("W", _P), ("bias", _P), ("relu", _I), ("out", _P), ("ldo", C.c_long), ("b", _I), ("m", _I), ("rowinfo", _P), ("tilecloud", _P),
-                ("out_col", _I), ("out_is_zero", _I)]
-
-
-class SaProblem(C.Structure):
-    """prcnn_sa_problem (include/prcnn_hip.h)"""
-    _fields_ = [("b", _I), ("n", _I), ("m", _I), ("c3", _I), ("max_tiles", C.c_long), ("P", _P), ("wxyz", _P), ("rowinfo", _P), ("rowdxyz", _P),
-                ("tilecloud", _P), ("hdr", _P), ("w2t", _P), ("b2", _P), ("w3t", _P), ("b3", _P), ("out", _P), ("out_stride", _I),
-                ("out_col", _I), ("out_is_zero", _I), ("c1", _I), ("c2", _I)]
-
-
-# name -> argument types (return type is always int except where noted)
-SIGNATURES = {
-    "prcnn_version": [],
-    "prcnn_opt_n_threads": [_I],
-    "prcnn_set_ball_query_mode": [_I],
-    "prcnn_ball_query": [_I, _I, _I, _F, _I, _P, _P, _P, _P],
-    "prcnn_fps_new_xyz": [_I, _I, _I, _P, _P, _P, _P],
-    "prcnn_fps_new_xyz_nested": [_I, _I, _I, _P, _P, _P, _P],
-    "prcnn_fps_nested_supported": [_I, _I],
-    "prcnn_fps_prefix_check": [_I, _I, _I, _P, _P, _P, _P, _P],
-    "prcnn_fps_new_xyz_flagged": [_I, _I, _I, _P, _P, _P, _P, _P],
-    "prcnn_ball_query_limit": [_I, _I, _I, _F, _I, _P, _P, _P, _P, _P],
-    "prcnn_group_points": [_I, _I, _I, _I, _I, _P, _P, _P, _P],
-    "prcnn_group_points_grad": [_I, _I, _I, _I, _I, _P, _P, _P, _P],
-    "prcnn_gather_points": [_I, _I, _I, _I, _P, _P, _P, _P],
-    "prcnn_gather_points_grad": [_I, _I, _I, _I, _P, _P, _P, _P],
-    "prcnn_furthest_point_sampling": [_I, _I, _I, _P, _P, _P, _P],
-    "prcnn_set_fps_arithmetic": [_I],
-    "prcnn_ball_query_full": [_I, _I, _I, _F, _I, _P, _P, _P, _P],
-    "prcnn_point_aux": [_L, _F, _P, _P, _P, _P, _P, _P],
-    "prcnn_three_nn": [_I, _I, _I, _P, _P, _P, _P, _P],
-    "prcnn_three_nn_weights": [_I, _I, _I, _P, _P, _P, _P, _P],
-    "prcnn_three_interpolate": [_I, _I, _I, _I, _P, _P, _P, _P, _P],
-    "prcnn_three_interpolate_grad": [_I, _I, _I, _I, _P, _P, _P, _P, _P],
-    "prcnn_query_and_group": [_I, _I, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P],
-    "prcnn_bias_relu_inplace": [C.c_long, _I, C.c_long, _P, _P, _P],
-    "prcnn_maxpool_bias_relu": [_I, _I, _I, _I, _P, _P, _P, _P],
-    "prcnn_group_cat_pm": [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
-    "prcnn_gather_affine_relu_pm": [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P],
-    "prcnn_sa_mlp_fused": [_I] * 7 + [_P] * 10 + [_I, _I, _P],
-    "prcnn_ball_pack": [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
-    "prcnn_ball_pack_ex": [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P],
-    "prcnn_rcnn_postprocess_blobs": [_I, _I, _I, _F, _F, _I, _I, _F, _F, _P, _F, _F, _P, _P, _P, _P, _P, _I, _P],
-    "prcnn_ball_pack_groups": [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
-    "prcnn_ball_pack_rep": [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
-    "prcnn_dup_rep": [_I, _I, _I, _P, _P, _P, _P, _P],
-    "prcnn_rcnn_roi_geometry": [_I, _I, _I, _F, _I, _I, _F, _I] + [_P] * 9,
-    "prcnn_rcnn_roi_geometry_packs": [_I, _I, _I, _F, _I, _I, _F, _I] + [_P] * 21 + [_I, _P],
-    "prcnn_rows_gemm128_rows": [_L, _P, _I, _I, _P, _P, _I, _P, _P, _P, _P],
-    "prcnn_sa_packed_mlp": [_I, _I, _I, _I, C.c_long] + [_P] * 11 + [_I, _I, _I, _P],
-    "prcnn_packed_gather_affine": [_I, _I, _I, C.c_long] + [_P] * 7 + [_P],
-    "prcnn_packed_layer": [_P, C.c_long, C.c_long, _I, _I, _I, _P, C.c_long, _P, _P, _I, _P, C.c_long, _P],
-    "prcnn_split_weights_bf16x3": [_I, _I, _P, _P, _P],
-    "prcnn_rows_layer_bf16x3": [C.c_long, _I, _I, _I, _P, C.c_long, _P, _P, _I, _P, C.c_long, _P],
-    "prcnn_packed_layer_interp": [C.c_long, _I, _I, _P, C.c_long, _P, _P, _I, _P, C.c_long, _I, _I, _P, C.c_long, _P, _P, _P],
-    "prcnn_sa_xyz_mlp_packed": [_I, _I, _I, _I, _I, C.c_long] + [_P] * 11 + [_I, _I, _I, _P],
-    "prcnn_rows_dot": [C.c_long, _I, _I, _P, C.c_long, _P, _P, _P, C.c_long, _P],
-    "prcnn_sa_wide_fused_supported": [_I, _I, _I],
-    "prcnn_sa_wide_fused": [_I, _I, _I, _I, _I, _I, C.c_long] + [_P] * 11 + [_I, _I, _I, _P],
-    "prcnn_sa_wide_fused3_supported": [_I, _I, _I, _I],
-    "prcnn_sa_wide_fused3": [_I, _I, _I, _I, _I, _I, _I, C.c_long] + [_P] * 11 + [_I, _I, _I, _P],
-    "prcnn_sa_packed_mlp_batch": [_I, C.POINTER(SaProblem), _P],
-    "prcnn_packed_gather_affine_batch": [_I, C.POINTER(GatherProblem), _P],
-    "prcnn_packed_layer_batch": [_I, C.POINTER(LayerProblem), _I, _P],
-    "prcnn_rpn_tail": [_I, _I, _I] + [_P] * 7 + [_I] + [_P] * 4,
-    "prcnn_rpn_tail_lin": [_I, _I, _I] + [_P] * 7 + [_I] + [_P] * 4,
-    "prcnn_rpn_tail_boxes_supported": [_I, _F, _F, _I, _I],
-    "prcnn_rpn_tail_lin_boxes": [_I, _I, _I] + [_P] * 7 + [_I, _F, _F, _I, _I] + [_P] * 6,
-    "prcnn_selftest_fmod_two_pi": [_L, _P, _P, _P, _P],
-    "prcnn_rpn_proposals_boxes": [_I, _I, _I, _I, _F, _I, _P, _P, _P, _P, _P],
-    "prcnn_packed_layer_segmax": [_I, _I, C.c_long, _I, _I, _P, C.c_long, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
-    "prcnn_maxpool_pm": [C.c_long, _I, _I, _P, _P, _I, _I, _P],
-    "prcnn_three_interpolate_pm": [_I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P],
-    "prcnn_three_interpolate_cat_pm": [_I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P],
-    "prcnn_boxes_overlap_bev": [_I, _P, _I, _P, _P, _P],
-    "prcnn_boxes_iou_bev": [_I, _P, _I, _P, _P, _P],
-    "prcnn_nms": [_I, _P, _P, _F, _P],
-    "prcnn_nms_normal": [_I, _P, _P, _F, _P],
-    "prcnn_nms_device": [_I, _I, _P, _P, _F, _I, _I, _P, _P, _P],
-    "prcnn_rows_gemm128": [_L, _I, _P, _I, _I, _P, _I, _I, _P, _P, _I, _P, _P],
-    "prcnn_rcnn_point_mlp": [_L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
-    "prcnn_pooled_tiles": [_I, _I, _P, _P, _P, _P],
-    "prcnn_pooled_rows": [_I, _I, _P, _P, _P, _I, _P],
-    "prcnn_rcnn_point_mlp_rows": [_L, _I, _I] + [_P] * 13,
-    "prcnn_sa_xyz_mlp_supported": [_I, _I, _I, _I],
-    "prcnn_sa_xyz_mlp": [_I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P],
-    "prcnn_rpn_proposals": [_I, _I, _I, _F, _F, _I, _I, _P, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P],
-    "prcnn_rcnn_postprocess": [_I, _I, _I, _F, _F, _I, _I, _F, _F, _P, _F, _F, _P, _P, _P, _P, _P, _P, _P, _P],
-    "prcnn_roipool3d": [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
-    "prcnn_host_pts_in_boxes3d": [_I, _I, _P, _P, _P],
-    "prcnn_host_roipool3d": [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
-    "prcnn_roipool3d_canonical": [_I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
-    "prcnn_roipool3d_canonical_xyz": [_I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
-    "prcnn_point_groups": [_I, _I, _P, _P, _P, _P],
-    "prcnn_input_stage": [_I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _F, _I, _P, _P, _P, _P, _P],
-    "prcnn_valid_flags": [_I, _I, _I, _I, _I, _P, _P, _P, _P, _F, _P, _P, _P],
-    "prcnn_rotate_iou_eval": [_I, _I, _P, _P, _P, _I, _P],
-    "prcnn_rotate_iou_eval_segmented": [_I, _L, _P, _P, _P, _P, _P, _P, _I, _P],
-    "prcnn_bev_best_match": [_I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P],
-    "prcnn_eval_align": [_I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P],
-    "prcnn_kitti_image_stats": [_I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _D, _D, _I, _I, _P, _P, _P, _P],
-    "prcnn_kitti_collect_scores": [_I, _P, _P, _P, _P, _P, _P, _P, _I, _D, _P, _P],
-    "prcnn_kitti_accumulate_pr": [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _D, _P, _I, _I, _P],
-    "prcnn_stat_norm_count": [_P, _P],
-    "prcnn_stat_norm_choose": [_P, _P],
-    "prcnn_stat_norm_write": [_P, _P],
-    "prcnn_stat_norm_occlusion": [_I, _I, _I, _I, _P, _P, _P, _P],
-    "prcnn_rpn_labels_workspace": [_I, _I, _P],
-    "prcnn_rpn_labels": [_I, _I, _I, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P],
-    "prcnn_gt_box_chunk": [],
-    "prcnn_gt_box_trig": [_I, _P, _P],
-    "prcnn_gt_extract_count": [_P, _P],
-    "prcnn_gt_extract_write": [_P, _P],
-    "prcnn_aug_max_candidates": [],
-    "prcnn_aug_place": [_P, _P],
-    "prcnn_aug_write": [_P, _P],
-    "prcnn_train_place": [_P, _P],
-    "prcnn_train_emit": [_P, _P],
-    "prcnn_rcnn_assign": [_I, _I, _I, _P, _P, _F, _F, _F, _P, _P, _P, _P, _P, _P, _P],
-    "prcnn_rcnn_max_rois": [],
-    "prcnn_rcnn_max_tries": [],
-    "prcnn_rcnn_aug_rois": [_P, _P],
-    "prcnn_rcnn_targets": [_P, _P],
-    "prcnn_loss_workspace": [],
-    "prcnn_loss_stats": [_P, _P],
-    "prcnn_cls_loss": [_P, _P],
-    "prcnn_reg_loss": [_P, _P],
-}
-
-_lib = None
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "prcnn_hip.h")
 
 
 class PrcnnError(RuntimeError):
     pass
+
+
+# ---- the reader: the subset of C that the header uses.  Whatever it does not recognise raises; it never guesses.
+_SCALARS = {"int": C.c_int, "unsigned int": C.c_uint, "long": C.c_long, "long long": C.c_longlong, "unsigned long long": C.c_ulonglong,
+            "float": C.c_float, "double": C.c_double, "unsigned char": C.c_ubyte}
+_DECLARATION = re.compile(r"\s*(?:typedef\s+struct\s+(?P<tag>\w+)\s*\{(?P<fields>[^{}]*)\}\s*(?P<struct>\w+)|enum\s*\{(?P<enum>[^{}]*)\}|"
+                          r"(?P<ret>\w[\w\s*]*?)\b(?P<fn>\w+)\s*\((?P<params>[^()]*)\))\s*;")
+_NAME = r"[A-Za-z_]\w*"
+
+Abi = collections.namedtuple("Abi", ["functions", "structs", "enums"])   # name -> (restype, argtypes) | Structure subclass | int
+
+
+def _declarators(text, structs, arrays=False):
+    """'const int *a, *b' | 'float anchor[3]' -> [(name, ctypes type)]: one base type, then comma declarators"""
+    what = " ".join(text.split())
+    tok = re.findall(r"\w+|[*,\[\]]", text)
+    if "".join(tok) != what.replace(" ", ""):
+        raise PrcnnError("prcnn_hip.h: unknown construct in %r" % what)
+    k = 0
+    while k < len(tok) and re.match(_NAME + "$", tok[k]):
+        k += 1
+    if k and (k == len(tok) or tok[k] != "*"):
+        k -= 1                                   # no star behind the leading words: the last of them is the first name
+    base, out = " ".join(w for w in tok[:k] if w != "const"), []
+    for d in " ".join(tok[k:]).split(" , "):
+        m = re.match(r"((?:\* )*)(%s)(?: \[ (\d+) \])?$" % _NAME, d)
+        if not m or (m.group(3) and not arrays):
+            raise PrcnnError("prcnn_hip.h: unknown construct in %r" % what)
+        stars = m.group(1).count("*")
+        if stars == 0 and base in _SCALARS:
+            t = _SCALARS[base]
+        elif stars == 1 and base in structs:
+            t = C.POINTER(structs[base])
+        elif stars == 1 and (base in _SCALARS or base in ("void", "char")):
+            t = C.c_void_p                        # callers pass data_ptr() ints, None and byref
+        else:
+            raise PrcnnError("prcnn_hip.h: unknown type in %r" % what)
+        out.append((m.group(2), t * int(m.group(3)) if m.group(3) else t))
+    return out
+
+
+def read_header(text):
+    """Header text -> Abi.  Comments and preprocessor lines are dropped (an ``#ifdef __cplusplus`` block with them); what remains must be
+    ``typedef struct NAME { ... } NAME;``, anonymous ``enum { A = 0, B };`` and prototypes that return int or const char *."""
+    abi = Abi({}, {}, {})
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#[ \t]*ifdef[ \t]+__cplusplus\b.*?^[ \t]*#[ \t]*endif\b[^\n]*$", " ", text, flags=re.S | re.M)
+    text = re.sub(r"^[ \t]*#(?:\\\n|[^\n])*$", " ", text, flags=re.M)
+    pos = 0
+    while text[pos:].strip():
+        m = _DECLARATION.match(text, pos)
+        if not m:
+            raise PrcnnError("prcnn_hip.h: unknown declaration %r" % " ".join(text[pos:].split(";")[0].split()))
+        pos = m.end()
+        if m.group("struct"):
+            name = m.group("struct")
+            if m.group("tag") != name:
+                raise PrcnnError("prcnn_hip.h: struct %s is typedef'd as %s" % (m.group("tag"), name))
+            fields = [f for stmt in m.group("fields").split(";") if stmt.strip() for f in _declarators(stmt, abi.structs, arrays=True)]
+            abi.structs[name] = type(name, (C.Structure,), {"_fields_": fields, "__doc__": name + " (include/prcnn_hip.h)"})
+        elif m.group("enum") is not None:
+            value = -1
+            for item in m.group("enum").split(","):
+                e = re.match(r"\s*(%s)\s*(?:=\s*(-?\d+)\s*)?$" % _NAME, item)
+                if e:
+                    value = abi.enums[e.group(1)] = int(e.group(2)) if e.group(2) else value + 1
+                elif item.strip():
+                    raise PrcnnError("prcnn_hip.h: unknown enumerator %r" % item.strip())
+        else:
+            restype = {"int": C.c_int, "const char *": C.c_char_p}.get(" ".join(m.group("ret").replace("*", " * ").split()))
+            if restype is None:
+                raise PrcnnError("prcnn_hip.h: unknown return type in %r" % " ".join(m.group(0).split()))
+            params = m.group("params").split(",") if m.group("params").strip() != "void" else []
+            abi.functions[m.group("fn")] = (restype, [t for p in params for _, t in _declarators(p, abi.structs)])
+    return abi
+
+
+def _read_header_file():
+    if not os.path.exists(HEADER_PATH):
+        raise PrcnnError("%s not found: the binding is read from it (no second copy of the ABI exists)" % HEADER_PATH)
+    with open(HEADER_PATH) as f:
+        return read_header(f.read())
+
+
+_abi = _read_header_file()
+ENUMS = _abi.enums                               # the header's enum constants by name; each is a module attribute too (_lib.PRCNN_CALIB_ROW)
+globals().update(ENUMS)
+# name -> argument types of every entry that returns int: a plain dict (a probe may drop entries before load())
+SIGNATURES = {name: argtypes for name, (restype, argtypes) in _abi.functions.items() if restype is C.c_int}
+
+
+def struct(name):
+    """The ctypes.Structure subclass of a struct that the header declares"""
+    if name not in _abi.structs:
+        raise PrcnnError("prcnn_hip.h declares no struct %r" % name)
+    return _abi.structs[name]
+
+
+GatherProblem, LayerProblem, SaProblem = struct("prcnn_gather_problem"), struct("prcnn_layer_problem"), struct("prcnn_sa_problem")
+
+_lib = None
 
 
 def load():
@@ -179,9 +138,8 @@ def load():
         for name, argtypes in SIGNATURES.items():
             fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
             fn.argtypes = argtypes
-            fn.restype = _I
-        lib.prcnn_last_error.restype = C.c_char_p
-        lib.prcnn_last_error.argtypes = []
+            fn.restype = C.c_int
+        lib.prcnn_last_error.restype, lib.prcnn_last_error.argtypes = _abi.functions["prcnn_last_error"]
         _lib = lib
     return _lib
 

@@ -52,7 +52,7 @@ import threading
 
 import numpy as np
 
-from . import kitti_io, kitti_utils
+from . import _lib, kitti_io, kitti_utils
 from .gt_database import box_trig, class_tuple, load_gt_database, sample_id_list
 from .kitti_io import Object3d, png_size
 from .scene_batch import (MAX_IO_WORKERS, TILE, as_calib, boxes_of_labels, check_device, check_pc_range, class_whitelist, cum,  # noqa: F401
@@ -237,14 +237,7 @@ def _place_cpu(scenes, jobs, db, scope, ids):
 
 
 # ------------------------------------------------------------------------------------------------------------------ device path
-class _AugBatch(C.Structure):
-    """prcnn_aug_batch (include/prcnn_hip.h)"""
-    _fields_ = [("n_scenes", C.c_int), ("n_jobs", C.c_int), ("max_tiles", C.c_int), ("n_db", C.c_int),
-                ("pt_off", C.c_void_p), ("tile_off", C.c_void_p), ("box_off", C.c_void_p), ("velo", C.c_void_p), ("calib", C.c_void_p),
-                ("scope", C.c_void_p), ("boxes", C.c_void_p), ("rect", C.c_void_p), ("valid", C.c_void_p), ("job_scene", C.c_void_p),
-                ("jt_off", C.c_void_p), ("cand_n", C.c_void_p), ("cand_db", C.c_void_p), ("cand_box", C.c_void_p),
-                ("cand_trig", C.c_void_p), ("cand_move", C.c_void_p), ("sizes", C.c_void_p), ("tile_cnt", C.c_void_p),
-                ("db_pts", C.c_void_p), ("db_off", C.c_void_p), ("out_off", C.c_void_p), ("obj_off", C.c_void_p), ("out", C.c_void_p)]
+_AugBatch = _lib.struct("prcnn_aug_batch")
 
 
 class AugPlacer:
@@ -252,7 +245,6 @@ class AugPlacer:
 
     def __init__(self, db, device="cuda"):
         import torch
-        from . import _lib
         if _lib.call("prcnn_aug_max_candidates") != MAX_CAND:
             raise _lib.PrcnnError("aug_scene: MAX_CAND differs from the library's")
         self.device, self.db = device, db
@@ -264,7 +256,6 @@ class AugPlacer:
 
     def __call__(self, scenes, jobs, scope, ids=None):
         import torch
-        from . import _lib
         scenes = [_norm_scene(s) for s in scenes]
         jobs = [(int(s), [int(i) for i in cand]) for s, cand in jobs]
         _check_jobs(scenes, jobs, self.db, ids)

@@ -209,7 +209,7 @@ extern "C" int prcnn_aug_place(const prcnn_aug_batch *b, void *stream)
     const int rc = aug_check(b, "aug_place");
     if (rc != PRCNN_OK) return rc;
     if (b->n_scenes == 0 || b->n_jobs == 0) return PRCNN_OK;
-    PRCNN_REQUIRE(sizeof(SceneCalib) == 35 * sizeof(float), "aug_place: calib layout");
+    PRCNN_REQUIRE(sizeof(SceneCalib) == PRCNN_CALIB_ROW * sizeof(float), "aug_place: calib layout");
     hipStream_t st = (hipStream_t)stream;
     if (b->max_tiles > 0) hipLaunchKernelGGL(aug_filter_kernel, tile_grid(b->max_tiles, b->n_scenes, AUG_THREADS), dim3(AUG_THREADS), 0, st, *b);
     hipLaunchKernelGGL(aug_place_kernel, dim3(b->n_jobs), dim3(WAVE), 0, st, *b);

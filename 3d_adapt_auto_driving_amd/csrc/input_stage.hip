@@ -266,7 +266,7 @@ extern "C" int prcnn_input_stage(int b, int n_max, int stride, int lidar_frame, 
     PRCNN_REQUIRE(b >= 0 && n_max >= 0 && (stride == 3 || stride == 4), "input_stage: bad sizes (stride 3 or 4)");
     PRCNN_REQUIRE(npoints > 0 && npoints <= IS_MAX_OUT, "input_stage: npoints=%d not in 1..%d", npoints, IS_MAX_OUT);
     PRCNN_REQUIRE(npoints_faraway >= 0, "input_stage: bad npoints_faraway");
-    PRCNN_REQUIRE(sizeof(SceneCalib) == 35 * sizeof(float), "input_stage: calib layout");
+    PRCNN_REQUIRE(sizeof(SceneCalib) == PRCNN_CALIB_ROW * sizeof(float), "input_stage: calib layout");
     if (b == 0) return PRCNN_OK;
     PRCNN_REQUIRE(counts && calib && seeds && out && stats && (raw || n_max == 0), "input_stage: null pointer");
     hipStream_t st = (hipStream_t)stream;

@@ -28,12 +28,10 @@ constexpr int SN_WCHUNK = 48;                    //                      write p
 constexpr int SN_OCC_MAX = 2048;                 // objects per scene in the occlusion pass (LDS)
 constexpr int SN_NRATIO = 11;                    // np.arange(1, -0.1, -0.1)
 
-// per-box f64 record (boxd, SN_BOXD doubles; stat_norm.py _BOX_* mirrors it): the first SN_GEOM are what the point tests read
-constexpr int SN_T = 0, SN_R = 3, SN_XLO = 12, SN_XHI = 13, SN_YLO = 14, SN_ZLO = 15, SN_ZHI = 16, SN_GEOM = 17;
-constexpr int SN_SCALE = 17;                     // 11 x 3 candidate scales (l, h, w axis order = box-frame x, y, z)
-constexpr int SN_FSCALE = 50, SN_SHIFT = 53, SN_FLAG1 = 57, SN_FLAG2 = 58, SN_BOXD = 64;   // write pass: chosen scale, shifts
-// per-box int record (boxi, SN_BOXI ints)
-constexpr int SN_CNT = 0, SN_ENV0 = 1, SN_ENV = 2, SN_RIDX = 13, SN_BASE = 14, SN_BOXI = 16;
+// per-box f64 record (boxd, PRCNN_SN_BOXD doubles: the layout is prcnn_hip.h's): the first SN_GEOM are what the point tests read
+constexpr int SN_GEOM = PRCNN_SN_SCALE;
+// per-box int record (boxi, PRCNN_SN_BOXI ints): the fields between the count and the ratio index never leave the device
+constexpr int SN_ENV0 = 1, SN_ENV = 2, SN_BASE = 14;   // env_mask0 count, 11 env counts, patch base
 
 struct SnCalib {                                 // row-major f64, as kitti_util.Calibration holds them
     double v2c[12], r0[9], r0inv[9], c2v[12];
@@ -79,19 +77,19 @@ __device__ __forceinline__ void rect_to_velo(const SnCalib &c, const double p[3]
 // box frame of a rect point: np.dot(p - t, R)
 __device__ __forceinline__ void box_frame(const double *bx, const double r[3], double f[3])
 {
-    const double d0 = r[0] - bx[SN_T], d1 = r[1] - bx[SN_T + 1], d2 = r[2] - bx[SN_T + 2];
+    const double d0 = r[0] - bx[PRCNN_SN_T], d1 = r[1] - bx[PRCNN_SN_T + 1], d2 = r[2] - bx[PRCNN_SN_T + 2];
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
-        double a = d0 * bx[SN_R + j];
-        a = fma(d1, bx[SN_R + 3 + j], a);
-        f[j] = fma(d2, bx[SN_R + 6 + j], a);
+        double a = d0 * bx[PRCNN_SN_R + j];
+        a = fma(d1, bx[PRCNN_SN_R + 3 + j], a);
+        f[j] = fma(d2, bx[PRCNN_SN_R + 6 + j], a);
     }
 }
 
 __device__ __forceinline__ bool inside_box(const double *bx, const double f[3], bool env)
 {
-    return f[0] > bx[SN_XLO] && f[0] < bx[SN_XHI] && f[1] > bx[SN_YLO] && f[1] < (env ? -0.5 : 0.0) && f[2] > bx[SN_ZLO] &&
-           f[2] < bx[SN_ZHI];
+    return f[0] > bx[PRCNN_SN_XLO] && f[0] < bx[PRCNN_SN_XHI] && f[1] > bx[PRCNN_SN_YLO] && f[1] < (env ? -0.5 : 0.0) && f[2] > bx[PRCNN_SN_ZLO] &&
+           f[2] < bx[PRCNN_SN_ZHI];
 }
 
 __device__ __forceinline__ double wave_min(double v)
@@ -118,7 +116,7 @@ __device__ __forceinline__ void load_boxes(const prcnn_sn_batch &b, int b0, int 
 {
     __syncthreads();
     for (int i = threadIdx.x; i < nb * SN_GEOM; i += SN_THREADS)
-        lds[i] = b.boxd[(long)(b0 + i / SN_GEOM) * SN_BOXD + i % SN_GEOM];
+        lds[i] = b.boxd[(long)(b0 + i / SN_GEOM) * PRCNN_SN_BOXD + i % SN_GEOM];
     __syncthreads();
 }
 
@@ -145,7 +143,7 @@ __global__ __launch_bounds__(SN_THREADS) void sn_count_kernel(prcnn_sn_batch b)
             any |= in;
             const unsigned long long bin = __ballot(in), be0 = __ballot(e0);
             const int g = bb + k0 + k;
-            int *bi = b.boxi + (long)g * SN_BOXI;
+            int *bi = b.boxi + (long)g * PRCNN_SN_BOXI;
             if (c.lane == 0) {
                 b.bt_cnt[b.bt_off[c.s] + (long)(k0 + k) * c.ntile + c.tile] = __popcll(bin);
                 if (be0) atomicAdd(bi + SN_ENV0, (int)__popcll(be0));
@@ -176,7 +174,7 @@ __global__ __launch_bounds__(SN_THREADS) void sn_scan_kernel(prcnn_sn_batch b)
     const int nt = b.tile_off[s + 1] - b.tile_off[s];
     if (k < nb) {
         const int tot = tile_exclusive_scan<SN_THREADS>(b.bt_cnt + b.bt_off[s] + (long)k * nt, nt, 1, wsum);
-        if (threadIdx.x == 0) b.boxi[(long)(bb + k) * SN_BOXI + SN_CNT] = tot;
+        if (threadIdx.x == 0) b.boxi[(long)(bb + k) * PRCNN_SN_BOXI + PRCNN_SN_CNT] = tot;
     } else {
         const int tot = tile_exclusive_scan<SN_THREADS>(b.rem_cnt + b.tile_off[s], nt, 1, wsum);
         if (threadIdx.x == 0) b.scene_i[4 * s + 0] = tot;
@@ -200,7 +198,7 @@ __global__ __launch_bounds__(SN_THREADS) void sn_conflict_kernel(prcnn_sn_batch 
         for (int i = threadIdx.x; i < kn * SN_NRATIO; i += SN_THREADS) {
             const int k = i / SN_NRATIO, q = i % SN_NRATIO;
             const double *mm = b.mm + 6L * (bb + k0 + k);
-            const double *sc = b.boxd + (long)(bb + k0 + k) * SN_BOXD + SN_SCALE + 3 * q;
+            const double *sc = b.boxd + (long)(bb + k0 + k) * PRCNN_SN_BOXD + PRCNN_SN_SCALE + 3 * q;
             double lo[3], hi[3];
 #pragma unroll
             for (int j = 0; j < 3; ++j) {                    // min / max of (inside coordinate * scale)
@@ -209,7 +207,7 @@ __global__ __launch_bounds__(SN_THREADS) void sn_conflict_kernel(prcnn_sn_batch 
             }
             double *o = sbnd + (long)i * 5;
             o[0] = lo[0]; o[1] = hi[0]; o[2] = lo[1]; o[3] = lo[2]; o[4] = hi[2];
-            if (q == 0) scnt[k] = b.boxi[(long)(bb + k0 + k) * SN_BOXI + SN_CNT];
+            if (q == 0) scnt[k] = b.boxi[(long)(bb + k0 + k) * PRCNN_SN_BOXI + PRCNN_SN_CNT];
         }
         __syncthreads();
         if (!c.live) continue;
@@ -217,7 +215,7 @@ __global__ __launch_bounds__(SN_THREADS) void sn_conflict_kernel(prcnn_sn_batch 
             if (scnt[k] == 0) continue;
             double f[3];
             box_frame(sbox + k * SN_GEOM, r, f);
-            int *env = b.boxi + (long)(bb + k0 + k) * SN_BOXI + SN_ENV;
+            int *env = b.boxi + (long)(bb + k0 + k) * PRCNN_SN_BOXI + SN_ENV;
             for (int q = 0; q < SN_NRATIO; ++q) {
                 const double *o = sbnd + (long)(k * SN_NRATIO + q) * 5;
                 const bool e = c.valid && f[0] > o[0] && f[0] < o[1] && f[1] > o[2] && f[1] < -0.5 && f[2] > o[3] && f[2] < o[4];
@@ -235,8 +233,8 @@ __global__ void sn_choose_kernel(prcnn_sn_batch b, int n_scenes)
     if (s >= n_scenes) return;
     int base = 0;
     for (int g = b.box_off[s]; g < b.box_off[s + 1]; ++g) {
-        int *bi = b.boxi + (long)g * SN_BOXI;
-        const int cnt = bi[SN_CNT];
+        int *bi = b.boxi + (long)g * PRCNN_SN_BOXI;
+        const int cnt = bi[PRCNN_SN_CNT];
         int q = -1;                                           // no inside point: ratio 0
         if (cnt > 0) {
             q = 0;                                            // ratio 1
@@ -246,7 +244,7 @@ __global__ void sn_choose_kernel(prcnn_sn_batch b, int n_scenes)
                     if (bi[SN_ENV + i] - bi[SN_ENV0] < 10) { q = i; break; }
             }
         }
-        bi[SN_RIDX] = q;
+        bi[PRCNN_SN_RIDX] = q;
         bi[SN_BASE] = base;
         base += cnt;
     }
@@ -258,18 +256,18 @@ __global__ void sn_choose_kernel(prcnn_sn_batch b, int n_scenes)
 // product, which OpenBLAS runs through its gemv kernel: the middle term first.
 __device__ __forceinline__ void patch_back(const double *bx, const double f[3], int single, double p[3])
 {
-    const double *fs = bx + SN_FSCALE;
+    const double *fs = bx + PRCNN_SN_FSCALE;
     const double a0 = f[0] * fs[0], a1 = f[1] * fs[1], a2 = f[2] * fs[2];
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
-        const double *Rj = bx + SN_R + 3 * j;                 // row j of R = column j of R^T
+        const double *Rj = bx + PRCNN_SN_R + 3 * j;                 // row j of R = column j of R^T
         double a;
         if (single) { a = a1 * Rj[1]; a = fma(a0, Rj[0], a); a = fma(a2, Rj[2], a); }
         else { a = a0 * Rj[0]; a = fma(a1, Rj[1], a); a = fma(a2, Rj[2], a); }
-        p[j] = a + bx[SN_T + j];
+        p[j] = a + bx[PRCNN_SN_T + j];
     }
-    if (bx[SN_FLAG1] != 0.0) { p[0] = p[0] + bx[SN_SHIFT]; p[2] = p[2] + bx[SN_SHIFT + 1]; }
-    if (bx[SN_FLAG2] != 0.0) { p[0] = p[0] + bx[SN_SHIFT + 2]; p[2] = p[2] + bx[SN_SHIFT + 3]; }
+    if (bx[PRCNN_SN_FLAG1] != 0.0) { p[0] = p[0] + bx[PRCNN_SN_SHIFT]; p[2] = p[2] + bx[PRCNN_SN_SHIFT + 1]; }
+    if (bx[PRCNN_SN_FLAG2] != 0.0) { p[0] = p[0] + bx[PRCNN_SN_SHIFT + 2]; p[2] = p[2] + bx[PRCNN_SN_SHIFT + 3]; }
 }
 
 // the scene's rows are [o0, o1): a row outside them would be a counting bug, never a write into another scene or past the buffer
@@ -281,7 +279,7 @@ __device__ __forceinline__ void store_point(float *out, long pos, long o0, long 
 // ---- pass 3: the output clouds
 __global__ __launch_bounds__(SN_THREADS) void sn_write_kernel(prcnn_sn_batch b)
 {
-    __shared__ double sbox[SN_WCHUNK * SN_BOXD];
+    __shared__ double sbox[SN_WCHUNK * PRCNN_SN_BOXD];
     __shared__ int sbase[SN_WCHUNK], scnt[SN_WCHUNK];
     SceneTile c;
     scene_tile<SN_THREADS>(b, blockIdx.y, c);
@@ -295,16 +293,16 @@ __global__ __launch_bounds__(SN_THREADS) void sn_write_kernel(prcnn_sn_batch b)
     for (int k0 = 0; k0 < nb; k0 += SN_WCHUNK) {
         const int kn = min(SN_WCHUNK, nb - k0);
         __syncthreads();
-        for (int i = threadIdx.x; i < kn * SN_BOXD; i += SN_THREADS) sbox[i] = b.boxd[(long)(bb + k0) * SN_BOXD + i];
+        for (int i = threadIdx.x; i < kn * PRCNN_SN_BOXD; i += SN_THREADS) sbox[i] = b.boxd[(long)(bb + k0) * PRCNN_SN_BOXD + i];
         for (int i = threadIdx.x; i < kn; i += SN_THREADS) {
-            sbase[i] = b.boxi[(long)(bb + k0 + i) * SN_BOXI + SN_BASE];
-            scnt[i] = b.boxi[(long)(bb + k0 + i) * SN_BOXI + SN_CNT];
+            sbase[i] = b.boxi[(long)(bb + k0 + i) * PRCNN_SN_BOXI + SN_BASE];
+            scnt[i] = b.boxi[(long)(bb + k0 + i) * PRCNN_SN_BOXI + PRCNN_SN_CNT];
         }
         __syncthreads();
         if (!c.live) continue;
         for (int k = 0; k < kn; ++k) {
             if (scnt[k] == 0) continue;
-            const double *bx = sbox + k * SN_BOXD;
+            const double *bx = sbox + k * PRCNN_SN_BOXD;
             double f[3];
             box_frame(bx, r, f);
             const bool in = c.valid && inside_box(bx, f, false);

@@ -18,7 +18,7 @@
 //           object's y shift), then rotation, scale, flip -> pts_rect, pts_input, pts_features.
 // Arithmetic (-ffp-contract=off):
 //   overlap   get_iou3d works on the f32 corner arrays of boxes3d_to_corners3d; the host makes them with numpy (a handful of boxes) and
-//             passes every box as a record of 11 doubles: the four BEV corners, min_h, max_h (the f32 corner means) and its f32 volume
+//             passes every box as a record of PRCNN_TR_REC doubles: the four BEV corners x, z, min_h, max_h (the f32 corner means) and its f32 volume
 //             term.  The polygon intersection is a Sutherland-Hodgman clip in f64, operation by operation as train_input.py's
 //             quad_intersection_area; h_overlap is an f32 difference; iou = f32(o3 / ((f32 vol_a + vol_b) - o3)); a candidate is placed
 //             when every value is < 1e-8 (a NaN rejects, as np.max would);
@@ -37,7 +37,6 @@ namespace prcnn {
 
 constexpr int TR_THREADS = 256;                  // 4 waves = 4 tiles per workgroup
 constexpr int TR_SIZES = PLACE_MAX_CAND + 3;     // ints per scene in sizes: kept, near kept, accepted, the accepted slots in order
-constexpr int TR_REC = 11;                       // doubles per overlap record: 4 x (x, z), min_h, max_h, volume term
 
 // ---- filter
 __global__ __launch_bounds__(TR_THREADS) void train_filter_kernel(prcnn_train_batch b)
@@ -114,18 +113,18 @@ __device__ __forceinline__ bool tr_conflict(const double *a, const double *b)
 
 __global__ __launch_bounds__(WAVE) void train_place_kernel(prcnn_train_batch b)
 {
-    __shared__ double sorig[GT_CHUNK * TR_REC];
-    __shared__ double scand[PLACE_MAX_CAND * TR_REC];
+    __shared__ double sorig[GT_CHUNK * PRCNN_TR_REC];
+    __shared__ double scand[PLACE_MAX_CAND * PRCNN_TR_REC];
     __shared__ unsigned srej;
     const int s = b.scene_begin + blockIdx.x, lane = threadIdx.x;
     const int nc = min(max(b.cand_n[s], 0), PLACE_MAX_CAND);
-    for (int p = lane; p < nc * TR_REC; p += WAVE) scand[p] = b.cand_rec[(long)PLACE_MAX_CAND * TR_REC * s + p];
+    for (int p = lane; p < nc * PRCNN_TR_REC; p += WAVE) scand[p] = b.cand_rec[(long)PLACE_MAX_CAND * PRCNN_TR_REC * s + p];
     // every candidate against the scene's label boxes, then against every earlier candidate (the records come enlarged)
     const int bb = b.box_off[s];
-    const unsigned rej = place_reject_by_labels<double, TR_REC, tr_conflict>(scand, nc, sorig, b.box_off[s + 1] - bb, &srej, [&](int k0, int kn) {
-        for (int p = lane; p < kn * TR_REC; p += WAVE) sorig[p] = b.box_rec[(long)TR_REC * (bb + k0) + p];
+    const unsigned rej = place_reject_by_labels<double, PRCNN_TR_REC, tr_conflict>(scand, nc, sorig, b.box_off[s + 1] - bb, &srej, [&](int k0, int kn) {
+        for (int p = lane; p < kn * PRCNN_TR_REC; p += WAVE) sorig[p] = b.box_rec[(long)PRCNN_TR_REC * (bb + k0) + p];
     });
-    place_accept_greedy<double, TR_REC, tr_conflict>(scand, scand, nc, rej, b.sizes + (long)TR_SIZES * s + 3);
+    place_accept_greedy<double, PRCNN_TR_REC, tr_conflict>(scand, scand, nc, rej, b.sizes + (long)TR_SIZES * s + 3);
 }
 
 // ---- count: the flag byte of every point, the kept and near counts per tile
@@ -194,16 +193,16 @@ __global__ __launch_bounds__(TR_THREADS) void train_emit_kernel(prcnn_train_batc
     if (row >= (long long)b.n_scenes * b.npoints) return;
     const int s = (int)(row / b.npoints);
     const long long code = b.codes[row];
-    const int kind = (int)((code >> 56) & 0xff), slot = (int)((code >> 48) & 0xff);
-    const long long val = code & 0xffffffffffffLL;
+    const int kind = (int)((code >> PRCNN_TR_KIND_SHIFT) & 0xff), slot = (int)((code >> PRCNN_TR_SLOT_SHIFT) & 0xff);
+    const long long val = code & ((1LL << PRCNN_TR_SLOT_SHIFT) - 1);
     const long p0 = b.pt_off[s], n = b.pt_off[s + 1] - p0, total = b.pt_off[b.n_scenes];
     float4 p = make_float4(0.f, 0.f, 0.f, 0.f);                    // a code that names nothing readable stays a zero row
-    if (kind <= 2) {
+    if (kind <= PRCNN_TR_FAR) {                                    // PRCNN_TR_KEPT / NEAR / FAR: the list's index
         if (val < n) {
             const int idx = b.lists[kind * total + p0 + val];
             if (idx >= 0 && idx < n) p = *(const float4 *)(b.rect + 4 * (p0 + idx));
         }
-    } else if (kind == 3 && val < b.n_db_rows && slot < PLACE_MAX_CAND) {
+    } else if (kind == PRCNN_TR_DB && val < b.n_db_rows && slot < PLACE_MAX_CAND) {
         p = *(const float4 *)(b.db_pts + 4 * val);
         p.y = __double2float_rn(__dsub_rn((double)p.y, b.cand_move[(long)PLACE_MAX_CAND * s + slot]));
     }
@@ -252,7 +251,7 @@ extern "C" int prcnn_train_place(const prcnn_train_batch *b, void *stream)
     const int rc = train_check(b, "train_place");
     if (rc != PRCNN_OK) return rc;
     if (b->n_scenes == 0) return PRCNN_OK;
-    PRCNN_REQUIRE(sizeof(SceneCalib) == 35 * sizeof(float), "train_place: calib layout");
+    PRCNN_REQUIRE(sizeof(SceneCalib) == PRCNN_CALIB_ROW * sizeof(float), "train_place: calib layout");
     PRCNN_REQUIRE(0 <= b->scene_begin && b->scene_begin <= b->scene_end && b->scene_end <= b->n_scenes, "train_place: bad scene range");
     const int ns = b->scene_end - b->scene_begin;
     if (ns == 0) return PRCNN_OK;

@@ -32,7 +32,7 @@ import types
 
 import numpy as np
 
-from . import kitti_io
+from . import _lib, kitti_io
 from .kitti_io import Object3d
 from .scene_batch import MAX_IO_WORKERS, TILE, as_calib, boxes_of_labels, check_device, class_whitelist, cum, offsets_to_device, pack_scenes, to_device  # noqa: F401
 CLASS_TUPLES = {"Car": ("Background", "Car"), "People": ("Background", "Pedestrian", "Cyclist"),
@@ -131,23 +131,16 @@ def _extract_cpu(pts, calib, boxes):
     return out
 
 
-class _GtBatch(C.Structure):
-    """prcnn_gt_batch (include/prcnn_hip.h)"""
-    _fields_ = [("n_scenes", C.c_int), ("max_tiles", C.c_int), ("max_boxes", C.c_int), ("reserved", C.c_int),
-                ("pt_off", C.c_void_p), ("tile_off", C.c_void_p), ("box_off", C.c_void_p), ("bt_off", C.c_void_p),
-                ("velo", C.c_void_p), ("calib", C.c_void_p), ("boxes", C.c_void_p), ("trig", C.c_void_p),
-                ("bt_cnt", C.c_void_p), ("counts", C.c_void_p), ("out_off", C.c_void_p), ("out", C.c_void_p)]
+_GtBatch = _lib.struct("prcnn_gt_batch")
 
 
 def box_chunk():
     """Boxes per LDS chunk of the kernels."""
-    from . import _lib
     return _lib.call("prcnn_gt_box_chunk")
 
 
 def box_trig(boxes):
     """(g, 7) f32 boxes -> (g, 2) f32 (cos ry, sin ry) as the host point test evaluates them."""
-    from . import _lib
     boxes = np.ascontiguousarray(boxes, dtype=np.float32).reshape(-1, 7)
     trig = np.zeros((boxes.shape[0], 2), dtype=np.float32)
     _lib.call("prcnn_gt_box_trig", boxes.shape[0], boxes.ctypes.data_as(C.c_void_p), trig.ctypes.data_as(C.c_void_p))
@@ -163,7 +156,6 @@ class GtExtractor:
 
     def __call__(self, scenes):
         import torch
-        from . import _lib
         scenes = _norm_scenes(scenes)
         S = len(scenes)
         if S == 0:

@@ -13,7 +13,7 @@ import struct
 
 import numpy as np
 
-from . import synth
+from . import _lib, synth
 
 
 class Calibration:
@@ -255,7 +255,7 @@ class DeviceInputStage:
     def pack_calib(calib, shape):
         v2c = getattr(calib, "V2C", None)
         r0 = getattr(calib, "R0", None)
-        row = np.zeros(35, dtype=np.float32)
+        row = np.zeros(_lib.PRCNN_CALIB_ROW, dtype=np.float32)
         row[0:12] = (np.asarray(v2c, np.float32) if v2c is not None else np.eye(3, 4, dtype=np.float32)).reshape(-1)
         row[12:21] = (np.asarray(r0, np.float32) if r0 is not None else np.eye(3, dtype=np.float32)).reshape(-1)
         row[21:33] = np.asarray(calib.P2, np.float32).reshape(-1)
@@ -291,7 +291,6 @@ class DeviceInputStage:
     def _run(self, raws, packed, calibs, shapes, scene_ids, lidar_frame, image_filter, return_choice):
         import ctypes
         import torch
-        from . import _lib
         cfg = self.cfg
         dev = self.device
         if packed is None:
@@ -324,16 +323,17 @@ class DeviceInputStage:
         raw = host.to(dev, non_blocking=True)
         # the per-scene calibration rows travel as one pinned block; counts and seeds are two tiny uploads
         # ... in ONE upload (round 6: counts and seeds used to leave from pageable memory, two staged copies that block the feeding
-        # thread): [calibration rows B x 35 f32 | counts B i32 | pad to 8 bytes | seeds B i64] as 4-byte words of the pinned block
-        so = (B * 36 + 1) & ~1                        # seeds start on an 8-byte boundary
+        # thread): [calibration rows B x PRCNN_CALIB_ROW f32 | counts B i32 | pad to 8 bytes | seeds B i64] as 4-byte words of the pinned block
+        CAL = _lib.PRCNN_CALIB_ROW
+        so = (B * (CAL + 1) + 1) & ~1                 # seeds start on an 8-byte boundary
         words = so + 2 * B
         blk = pin_small[:words].numpy()
-        blk[:B * 35] = np.stack([self.pack_calib(c, s) for c, s in zip(calibs, shapes)], 0).reshape(-1)
-        blk[B * 35:B * 35 + B].view(np.int32)[:] = np.asarray(lengths, dtype=np.int32)
+        blk[:B * CAL] = np.stack([self.pack_calib(c, s) for c, s in zip(calibs, shapes)], 0).reshape(-1)
+        blk[B * CAL:B * CAL + B].view(np.int32)[:] = np.asarray(lengths, dtype=np.int32)
         blk[so:words].view(np.int64)[:] = np.asarray([self.seed + int(i) for i in scene_ids], dtype=np.int64)
         small_dev = pin_small[:words].to(dev, non_blocking=True)
-        cal = small_dev[:B * 35].view(B, 35)
-        counts = small_dev[B * 35:B * 35 + B].view(torch.int32)
+        cal = small_dev[:B * CAL].view(B, CAL)
+        counts = small_dev[B * CAL:B * CAL + B].view(torch.int32)
         seeds = small_dev[so:words].view(torch.int64)
         done = torch.cuda.Event()
         done.record(torch.cuda.current_stream(dev))
@@ -365,7 +365,6 @@ def device_valid_flags(cfg, device, raws, calibs, shapes, lidar_frame=True, imag
     numpy results (tests/golden g11)."""
     import ctypes
     import torch
-    from . import _lib
     dev = torch.device(device)
     B, stride = len(raws), raws[0].shape[1]
     n_max = max(1, max(r.shape[0] for r in raws))

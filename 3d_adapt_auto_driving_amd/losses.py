@@ -30,23 +30,17 @@ import ctypes as C
 
 import numpy as np
 
-PART_NAMES = ("loss", "cls", "reg", "loc", "angle", "size", "cls_pos", "cls_neg", "x_bin", "z_bin", "x_res", "z_res", "y_bin", "y_res",
-              "y_offset", "ry_bin", "ry_res", "size_raw", "n_pos", "n_neg", "n_valid", "n_reg_fg", "dice_min", "dice_max")
-PARTS = len(PART_NAMES)
-P = {name: i for i, name in enumerate(PART_NAMES)}
-CLS_KINDS = {"DiceLoss": 0, "SigmoidFocalLoss": 1, "BinaryCrossEntropy": 2}
+from . import _lib
+
+P = {name[len("PRCNN_LP_"):].lower(): i for name, i in _lib.ENUMS.items() if name.startswith("PRCNN_LP_")}   # PRCNN_LP_X_BIN -> "x_bin": 8
+PART_NAMES = tuple(sorted(P, key=P.get))
+PARTS = _lib.PRCNN_LOSS_PARTS
+CLS_KINDS = {"DiceLoss": _lib.PRCNN_LOSS_DICE, "SigmoidFocalLoss": _lib.PRCNN_LOSS_FOCAL, "BinaryCrossEntropy": _lib.PRCNN_LOSS_BCE}
 
 ModelReturn = collections.namedtuple("ModelReturn", ["loss", "tb_dict", "disp_dict"])
 
 
-class _LossArgs(C.Structure):
-    """prcnn_loss_args (include/prcnn_hip.h)"""
-    _fields_ = [("n", C.c_int), ("c", C.c_int), ("cls_kind", C.c_int), ("xz_fine", C.c_int), ("y_by_bin", C.c_int), ("ry_fine", C.c_int),
-                ("nbin_loc", C.c_int), ("nbin_y", C.c_int), ("nbin_head", C.c_int), ("loc_scope", C.c_float), ("loc_bin", C.c_float),
-                ("y_scope", C.c_float), ("y_bin", C.c_float), ("alpha", C.c_float), ("gamma", C.c_float), ("fg_weight", C.c_float),
-                ("w_cls", C.c_float), ("w_reg", C.c_float), ("anchor", C.c_float * 3), ("cls", C.c_void_p), ("label", C.c_void_p),
-                ("reg_mask", C.c_void_p), ("reg", C.c_void_p), ("reg_label", C.c_void_p), ("anchors", C.c_void_p), ("grad_cls", C.c_void_p),
-                ("grad_reg", C.c_void_p), ("parts", C.c_void_p), ("work", C.c_void_p)]
+_LossArgs = _lib.struct("prcnn_loss_args")
 
 
 class Spec(collections.namedtuple("Spec", ["stage", "cls_kind", "alpha", "gamma", "fg_weight", "w_cls", "w_reg", "loc_scope", "loc_bin",
@@ -213,7 +207,6 @@ def _stage_cpu(spec, cls, reg, label, reg_mask, reg_label, anchors):
 # ---------------------------------------------------------------------------------------------------------------------- device path
 def _device_function():
     import torch
-    from . import _lib
 
     class StageLoss(torch.autograd.Function):
         @staticmethod

@@ -37,6 +37,8 @@ import threading
 
 import numpy as np
 
+from . import _lib
+
 MULTIPLE_RANGES = [[0.2, 0.1, np.pi / 12, 0.7], [0.3, 0.15, np.pi / 12, 0.6], [0.5, 0.15, np.pi / 9, 0.5], [0.8, 0.15, np.pi / 6, 0.3],
                    [1.0, 0.15, np.pi / 3, 0.2]]                # pos_range, hwl_range, angle_range, mean_iou
 KEEP_PROB = 0.2                                                 # a try keeps the RoI itself when rand() < 0.2
@@ -72,23 +74,10 @@ def host_backend():
             iou3d_utils.iou3d_cuda, roipool3d_utils.roipool3d_cuda = saved
 
 
-class _AugArgs(C.Structure):
-    """prcnn_rcnn_aug (include/prcnn_hip.h)"""
-    _fields_ = [("m", C.c_int), ("g", C.c_int), ("n_rois", C.c_int), ("n_fg", C.c_int), ("fg_times", C.c_int), ("bg_times", C.c_int),
-                ("method", C.c_int), ("n_pool", C.c_int), ("pos_thresh", C.c_float), ("pool_extra_width", C.c_float),
-                ("rois", C.c_void_p), ("gt", C.c_void_p), ("max_ov", C.c_void_p), ("assign", C.c_void_p), ("lists", C.c_void_p),
-                ("pick", C.c_void_p), ("keep", C.c_void_p), ("noise", C.c_void_p), ("table", C.c_void_p), ("out_rois", C.c_void_p),
-                ("out_pool_rois", C.c_void_p), ("out_gt", C.c_void_p), ("out_iou", C.c_void_p), ("out_src", C.c_void_p),
-                ("out_cnt", C.c_void_p), ("out_keep", C.c_void_p), ("out_tried", C.c_void_p), ("used", C.c_void_p)]
+_AugArgs = _lib.struct("prcnn_rcnn_aug")
 
 
-class _TargetArgs(C.Structure):
-    """prcnn_rcnn_target_args (include/prcnn_hip.h)"""
-    _fields_ = [("rows", C.c_int), ("s", C.c_int), ("cin", C.c_int), ("aug_data", C.c_int), ("rot_scale", C.c_float),
-                ("reg_fg", C.c_float), ("cls_fg", C.c_float), ("cls_bg", C.c_float), ("pooled", C.c_void_p), ("empty", C.c_void_p),
-                ("aug_rand", C.c_void_p), ("rois_in", C.c_void_p), ("gt_in", C.c_void_p), ("gt_iou", C.c_void_p),
-                ("rois_out", C.c_void_p), ("gt_out", C.c_void_p), ("sampled_pts", C.c_void_p), ("pts_feature", C.c_void_p),
-                ("cls_label", C.c_void_p), ("reg_valid", C.c_void_p)]
+_TargetArgs = _lib.struct("prcnn_rcnn_target_args")
 
 
 def _opt(cfg, name, default):
@@ -113,7 +102,6 @@ class RcnnTargets:
         if self.n_rois < 1 or self.aug_times < 0:
             raise ValueError("rcnn_targets: ROI_PER_IMAGE %d / ROI_FG_AUG_TIMES %d" % (self.n_rois, self.aug_times))
         if self.device != "cpu":
-            from . import _lib
             if self.n_rois > _lib.call("prcnn_rcnn_max_rois"):
                 raise ValueError("rcnn_targets: ROI_PER_IMAGE %d is above the %d the device code holds" %
                                  (self.n_rois, _lib.call("prcnn_rcnn_max_rois")))
@@ -363,7 +351,6 @@ class RcnnTargets:
 
     def _forward_device(self, d):
         import torch
-        from . import _lib
         cfg, Rc, dev = self.cfg, self.cfg.RCNN, self.device
         _check_inputs(d, Rc, cuda=True)
         rois, gt = d["roi_boxes3d"], d["gt_boxes3d"]

@@ -36,7 +36,7 @@ def to_device(device):
 def pack_scenes(clouds, n_boxes, calibs=None, shapes=None):
     """Scenes back to back.  clouds: per scene (n, 4) f32; n_boxes: boxes per scene -> n, nt (tiles), nb, their offsets pt_off,
     tile_off, box_off (int64; the kernels read them as int32), velo (sum n, 4) (one zero row when there is no point), max_tiles
-    and, with ``calibs`` (kitti_io.Calibration), calib (S, 35) f32 = DeviceInputStage.pack_calib with the image ``shapes``, or
+    and, with ``calibs`` (kitti_io.Calibration), calib (S, PRCNN_CALIB_ROW) f32 = DeviceInputStage.pack_calib with the image ``shapes``, or
     without them (S, 12) f32 = the lidar -> rect matrix np.dot(V2C.T, R0.T)."""
     p = types.SimpleNamespace()
     p.n = np.array([len(c) for c in clouds], dtype=np.int64)

@@ -31,6 +31,7 @@ from itertools import chain
 
 import numpy as np
 
+from . import _lib
 from .kitti_io import Object3d, png_size, read_label_lines  # noqa: F401  (the label parser lives there; imported from here too)
 from .scene_batch import MAX_IO_WORKERS, TILE, as_calib, check_device, cum, offsets_to_device, pack_scenes, to_device  # noqa: F401
 
@@ -38,9 +39,8 @@ RATIOS = np.arange(1, -0.1, -0.1)      # the avoid_conflict trial ratios; the la
 STAT_SUBJECTS = ("height", "width", "length")
 SPLIT_DIRS = {"train": "training", "val": "training", "test": "testing"}
 
-# per-box records of csrc/stat_norm.hip (SN_* there)
-_BOXD, _BOX_SCALE, _BOX_FSCALE, _BOX_SHIFT, _BOX_FLAG1, _BOX_FLAG2 = 64, 17, 50, 53, 57, 58
-_BOXI, _BI_CNT, _BI_RIDX, _BI_BASE = 16, 0, 13, 14
+_T, _R, _XLO = _lib.PRCNN_SN_T, _lib.PRCNN_SN_R, _lib.PRCNN_SN_XLO      # the boxd record's layout (include/prcnn_hip.h)
+_SCALE, _FSCALE, _SHIFT, _FLAG1 = _lib.PRCNN_SN_SCALE, _lib.PRCNN_SN_FSCALE, _lib.PRCNN_SN_SHIFT, _lib.PRCNN_SN_FLAG1
 
 
 # ---------------------------------------------------------------------------------------------------------------- labels, calib
@@ -223,7 +223,6 @@ def _resolved(rects, h, w):
 def device_paint_occlusion(rects_per_scene, h, w, device="cuda"):
     """paint_occlusion for a batch of scenes in one launch (csrc/stat_norm.hip sn_occlusion_kernel) -> list of int64 arrays."""
     import torch
-    from . import _lib
     n = [len(r) for r in rects_per_scene]
     off = cum(n).astype(np.int32)
     flat = [r for rs in rects_per_scene for r in _resolved(rs, h, w)]
@@ -316,29 +315,22 @@ def _rescale_cpu(velo, objs, calib, mapping, avoid_conflict, align_front, classe
 
 
 # ---------------------------------------------------------------------------------------------------------------- device path
-class _SnBatch(C.Structure):
-    """prcnn_sn_batch (include/prcnn_hip.h)"""
-    _fields_ = [("n_scenes", C.c_int), ("max_tiles", C.c_int), ("max_boxes", C.c_int), ("avoid", C.c_int),
-                ("pt_off", C.c_void_p), ("tile_off", C.c_void_p), ("box_off", C.c_void_p), ("bt_off", C.c_void_p),
-                ("velo", C.c_void_p), ("calib", C.c_void_p), ("boxd", C.c_void_p), ("boxi", C.c_void_p), ("mm", C.c_void_p),
-                ("bt_cnt", C.c_void_p), ("rem_cnt", C.c_void_p), ("scene_i", C.c_void_p), ("out_off", C.c_void_p),
-                ("out", C.c_void_p)]
+_SnBatch = _lib.struct("prcnn_sn_batch")
 
 
 def _box_record(obj, mapping, avoid_conflict):
-    rec = np.zeros(_BOXD)
-    rec[0:3] = obj.t
-    rec[3:12] = _rot(obj.ry).reshape(-1)
-    rec[12:17] = (-obj.l / 2.0, obj.l / 2.0, -obj.h, -obj.w / 2.0, obj.w / 2.0)
+    rec = np.zeros(_lib.PRCNN_SN_BOXD)
+    rec[_T:_T + 3] = obj.t
+    rec[_R:_R + 9] = _rot(obj.ry).reshape(-1)
+    rec[_XLO:_XLO + 5] = (-obj.l / 2.0, obj.l / 2.0, -obj.h, -obj.w / 2.0, obj.w / 2.0)        # XLO, XHI, YLO, ZLO, ZHI
     if avoid_conflict:
-        rec[_BOX_SCALE:_BOX_SCALE + 33] = np.concatenate([mapping(obj, r).reshape(-1) for r in RATIOS])
+        rec[_SCALE:_SCALE + 33] = np.concatenate([mapping(obj, r).reshape(-1) for r in RATIOS])
     return rec
 
 
 def _rescale_device(scenes, mapping, avoid_conflict, align_front, classes, device):
     """scenes: list of (velo (n, 4) f32, objects without DontCare, Calib) -> clouds, ratios, inside counts per scene."""
     import torch
-    from . import _lib
     S = len(scenes)
     boxes = [[o for o in objs if o.cls_type in classes] for _, objs, _ in scenes]
     pk = pack_scenes([v for v, _, _ in scenes], [len(b) for b in boxes])
@@ -347,12 +339,12 @@ def _rescale_device(scenes, mapping, avoid_conflict, align_front, classes, devic
         raise ValueError("stat_norm batch too large: split it")
     nbox = int(box_off[-1])
     flat = [o for b in boxes for o in b]
-    boxd = np.stack([_box_record(o, mapping, avoid_conflict) for o in flat]) if flat else np.zeros((1, _BOXD))
+    boxd = np.stack([_box_record(o, mapping, avoid_conflict) for o in flat]) if flat else np.zeros((1, _lib.PRCNN_SN_BOXD))
     calib = np.stack([np.concatenate([c.V2C.ravel(), c.R0.ravel(), c.R0_inv.ravel(), c.C2V.ravel()]) for _, _, c in scenes])
     dev = to_device(device)
     t_pt, t_tile, t_box = offsets_to_device(pk, dev)
     t_bt, t_velo, t_calib, t_boxd = dev(bt_off), dev(pk.velo), dev(calib), dev(boxd)
-    t_boxi = torch.zeros((max(1, nbox), _BOXI), dtype=torch.int32, device=device)
+    t_boxi = torch.zeros((max(1, nbox), _lib.PRCNN_SN_BOXI), dtype=torch.int32, device=device)
     t_mm = torch.tensor([np.inf] * 3 + [-np.inf] * 3, dtype=torch.float64, device=device).repeat(max(1, nbox), 1)
     t_btc = torch.zeros(max(1, int(bt_off[-1])), dtype=torch.int32, device=device)
     t_rem = torch.zeros(max(1, int(tile_off[-1])), dtype=torch.int32, device=device)
@@ -363,7 +355,7 @@ def _rescale_device(scenes, mapping, avoid_conflict, align_front, classes, devic
     stream = C.c_void_p(_lib.current_stream(t_velo))
     _lib.call("prcnn_stat_norm_count", C.byref(b), stream)
     _lib.call("prcnn_stat_norm_choose", C.byref(b), stream)
-    small = torch.cat([t_boxi[:, [_BI_CNT, _BI_RIDX]].reshape(-1), t_sc.reshape(-1)]).cpu().numpy()   # the one D2H that sizes
+    small = torch.cat([t_boxi[:, [_lib.PRCNN_SN_CNT, _lib.PRCNN_SN_RIDX]].reshape(-1), t_sc.reshape(-1)]).cpu().numpy()   # the one D2H that sizes
     cnt_ridx = small[:2 * max(1, nbox)].reshape(-1, 2)[:nbox]
     n_out = small[2 * max(1, nbox):].reshape(S, 4)[:, 2].astype(np.int64)
     ratios_flat = []
@@ -373,13 +365,13 @@ def _rescale_device(scenes, mapping, avoid_conflict, align_front, classes, devic
         ratios_flat.append(ratio)
         if cnt:
             lhw = None
-            boxd[g, _BOX_FSCALE:_BOX_FSCALE + 3] = mapping(obj, ratio).reshape(-1)
+            boxd[g, _FSCALE:_FSCALE + 3] = mapping(obj, ratio).reshape(-1)
             if align_front:
                 lhw = _new_size(obj, mapping, ratio)
                 for k, sh in enumerate(_align_shifts(obj, lhw)):
                     if sh is not None:
-                        boxd[g, _BOX_SHIFT + 2 * k:_BOX_SHIFT + 2 * k + 2] = sh
-                        boxd[g, _BOX_FLAG1 + k] = 1.0
+                        boxd[g, _SHIFT + 2 * k:_SHIFT + 2 * k + 2] = sh
+                        boxd[g, _FLAG1 + k] = 1.0
     out_off = cum(n_out)
     t_boxd.copy_(torch.from_numpy(boxd))
     t_off = dev(out_off)

@@ -44,7 +44,7 @@ import time
 
 import numpy as np
 
-from . import kitti_io, kitti_utils
+from . import _lib, kitti_io, kitti_utils
 from .aug_scene import road_plane
 from .gt_database import box_trig, class_tuple, load_gt_database
 from .kitti_io import Object3d, png_size
@@ -62,7 +62,8 @@ DEFAULTS = {"AUG_DATA": True, "AUG_METHOD_LIST": ["rotation", "scaling", "flip"]
             "AUG_METHOD_PROB": [0.5, 0.5, 0.5], "AUG_ROT_RANGE": 18, "GT_AUG_ENABLED": False, "GT_EXTRA_NUM": 15,
             "GT_AUG_RAND_NUM": False, "GT_AUG_APPLY_PROB": 0.75, "GT_AUG_HARD_RATIO": 0.6, "PC_REDUCE_BY_RANGE": True,
             "INCLUDE_SIMILAR_TYPE": False}                                   # lib/config.py's values for the keys config.py lacks
-KIND_KEPT, KIND_NEAR, KIND_FAR, KIND_DB = 0, 1, 2, 3
+KIND_KEPT, KIND_NEAR, KIND_FAR, KIND_DB = _lib.PRCNN_TR_KEPT, _lib.PRCNN_TR_NEAR, _lib.PRCNN_TR_FAR, _lib.PRCNN_TR_DB   # emit codes:
+KIND_SHIFT, SLOT_SHIFT, REC = _lib.PRCNN_TR_KIND_SHIFT, _lib.PRCNN_TR_SLOT_SHIFT, _lib.PRCNN_TR_REC    # kind | slot | value; record doubles
 
 
 def _opt(cfg, name):
@@ -122,11 +123,11 @@ def quad_intersection_area(A, B):
 
 
 def overlap_records(boxes):
-    """(k, 7) f32 boxes (already enlarged) -> (k, 11) f64: what get_iou3d reads of boxes3d_to_corners3d(boxes): the four BEV corners
+    """(k, 7) f32 boxes (already enlarged) -> (k, REC) f64: what get_iou3d reads of boxes3d_to_corners3d(boxes): the four BEV corners
     (x, z) of the bottom face, min_h, max_h (f32 corner means) and area * (max_h - min_h) as the reference's numpy rounds it (a Python
     float times an f32 scalar: f32)."""
     boxes = np.asarray(boxes, dtype=np.float32).reshape(-1, 7)
-    rec = np.zeros((boxes.shape[0], 11), dtype=np.float64)
+    rec = np.zeros((boxes.shape[0], REC), dtype=np.float64)
     if boxes.shape[0] == 0:
         return rec
     corners = kitti_utils.boxes3d_to_corners3d(boxes)
@@ -238,17 +239,7 @@ def rotation_terms(angle):
     return float(t[0, 0]), float(t[1, 0]), float(t[0, 1]), float(t[1, 1])
 
 
-class _TrainBatch(C.Structure):
-    """prcnn_train_batch (include/prcnn_hip.h)"""
-    _fields_ = [("n_scenes", C.c_int), ("max_tiles", C.c_int), ("npoints", C.c_int), ("input_channels", C.c_int),
-                ("reduce_by_range", C.c_int), ("scene_begin", C.c_int), ("scene_end", C.c_int), ("reserved", C.c_int),
-                ("n_db_rows", C.c_longlong),
-                ("pt_off", C.c_void_p), ("tile_off", C.c_void_p), ("box_off", C.c_void_p), ("velo", C.c_void_p), ("calib", C.c_void_p),
-                ("scope", C.c_void_p), ("is_rect", C.c_void_p), ("box_rec", C.c_void_p), ("cand_n", C.c_void_p),
-                ("cand_rec", C.c_void_p), ("cand_box", C.c_void_p), ("cand_trig", C.c_void_p), ("cand_move", C.c_void_p),
-                ("rect", C.c_void_p), ("valid", C.c_void_p), ("flag", C.c_void_p), ("tile_cnt", C.c_void_p), ("lists", C.c_void_p),
-                ("sizes", C.c_void_p), ("db_pts", C.c_void_p), ("codes", C.c_void_p), ("aug", C.c_void_p), ("pts_rect", C.c_void_p),
-                ("pts_input", C.c_void_p), ("pts_features", C.c_void_p)]
+_TrainBatch = _lib.struct("prcnn_train_batch")
 
 
 class RpnTrainInput:
@@ -294,7 +285,6 @@ class RpnTrainInput:
             self.hard = [k for k in range(len(db)) if self.db_n[k] <= HARD_POINTS]
         if self.device != "cpu":
             import torch
-            from . import _lib
             if _lib.call("prcnn_aug_max_candidates") != MAX_CAND:
                 raise _lib.PrcnnError("train_input: MAX_CAND differs from the library's")
             self.t_db = torch.from_numpy(self.db_rows if len(self.db_rows) else np.zeros((1, 4), np.float32)).to(self.device)
@@ -410,7 +400,7 @@ class RpnTrainInput:
                 p[:, 1] = (p[:, 1].astype(np.float64) - move).astype(np.float32)
                 new_pts.append(p)
                 new_int.append(np.asarray(self.db[k]["intensity"], dtype=np.float32))
-                cur = np.concatenate((cur, rec.reshape(1, 11)), axis=0)
+                cur = np.concatenate((cur, rec.reshape(1, REC)), axis=0)
                 accepted.append(k)
             if accepted:
                 n_scene = int((flag == 1).sum())
@@ -466,7 +456,7 @@ class RpnTrainInput:
     # -------------------------------------------------------------------------------------------------------------- device path
     def _batch_device(self, ids):
         import torch
-        from . import _lib, rpn_eval
+        from . import rpn_eval
         cfg, rng, device = self.cfg, self.rng, self.device
         S, NP = len(ids), self.npoints
         scenes = [self.load_scene(i) for i in ids]
@@ -476,12 +466,12 @@ class RpnTrainInput:
         if total >= 2 ** 31 - 64 or S * NP >= 2 ** 40:
             raise ValueError("train_input batch too large: split it")
         box_rec = [overlap_records(enlarged(sc["all_boxes"])) for sc in scenes]
-        box_rec = np.concatenate(box_rec) if pk.box_off[-1] else np.zeros((1, 11), np.float64)
+        box_rec = np.concatenate(box_rec) if pk.box_off[-1] else np.zeros((1, REC), np.float64)
         is_rect = np.array([sc["is_rect"] for sc in scenes], dtype=np.uint8)
         dev = to_device(device)
         t_in = offsets_to_device(pk, dev) + [dev(a) for a in (pk.velo, pk.calib, self.scope.reshape(6), is_rect, box_rec)]
         t_cn = torch.zeros((S,), dtype=torch.int32, device=device)
-        t_crec = torch.zeros((S, MAX_CAND, 11), dtype=torch.float64, device=device)
+        t_crec = torch.zeros((S, MAX_CAND, REC), dtype=torch.float64, device=device)
         t_cbox = torch.zeros((S, MAX_CAND, 7), dtype=torch.float32, device=device)
         t_ctrig = torch.zeros((S, MAX_CAND, 2), dtype=torch.float32, device=device)
         t_cmove = torch.zeros((S, MAX_CAND), dtype=torch.float64, device=device)
@@ -531,13 +521,13 @@ class RpnTrainInput:
             t0 = time.perf_counter()
             if accepted:
                 rows = np.concatenate([np.arange(self.db_off[cand[v][0]], self.db_off[cand[v][0] + 1], dtype=np.int64) |
-                                       (np.int64(v) << 48) | (np.int64(KIND_DB) << 56) for v in slots])
-                rows_near = self.db_rows[rows & 0xffffffffffff, 2] < np.float32(NEAR_DEPTH)
+                                       (np.int64(v) << SLOT_SHIFT) | (np.int64(KIND_DB) << KIND_SHIFT) for v in slots])
+                rows_near = self.db_rows[rows & ((1 << SLOT_SHIFT) - 1), 2] < np.float32(NEAR_DEPTH)
             else:
                 rows, rows_near = np.zeros((0,), np.int64), np.zeros((0,), bool)
             if NP < n_kept + len(rows):
-                near_ids = np.concatenate((np.arange(n_near, dtype=np.int64) | (np.int64(KIND_NEAR) << 56), rows[rows_near]))
-                far_ids = np.concatenate((np.arange(n_kept - n_near, dtype=np.int64) | (np.int64(KIND_FAR) << 56), rows[~rows_near]))
+                near_ids = np.concatenate((np.arange(n_near, dtype=np.int64) | (np.int64(KIND_NEAR) << KIND_SHIFT), rows[rows_near]))
+                far_ids = np.concatenate((np.arange(n_kept - n_near, dtype=np.int64) | (np.int64(KIND_FAR) << KIND_SHIFT), rows[~rows_near]))
                 codes[s] = sample_choice(rng, near_ids, far_ids, NP, self.npoints_faraway, self.with_replace)
             else:
                 if n_kept + len(rows) == 0:

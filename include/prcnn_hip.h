@@ -609,12 +609,13 @@ int prcnn_eval_align(int nseg, int n, const int *box_off, const int *q_off, doub
 
 /* get_lidar + get_valid_flag + the near/far sampler of get_rpn_sample (kitti_rcnn_dataset.py:249-324) with
  * calibration.py:51-71, one workgroup per scene.  raw (b,n_max,stride) f32, stride 3 or 4, as read from velodyne .bin
- * (lidar_frame = 1) or already rectified (0); counts (b) i32; calib (b,35) f32 = V2C 3x4 | R0 3x3 | P2 3x4 | img h, w;
+ * (lidar_frame = 1) or already rectified (0); counts (b) i32; calib (b,PRCNN_CALIB_ROW) f32 = V2C 3x4 | R0 3x3 | P2 3x4 | img h, w;
  * image_filter 0/1 (in-image + depth >= 0 test); scope_host = 6 HOST floats x0,x1,y0,y1,z0,z1 or NULL;
  * seeds (b) u64 DEVICE.  -> out (b,npoints,3), stats (b,3) i32 = #valid, #near, #far, choice (b,npoints) i32 = raw
  * index of each output point (may be NULL).  npoints <= 16384.
  * The subset is random (distinct-key selection + key-sorted shuffle): same distribution as the reference's
  * np.random.choice / shuffle, not the same draws; transform and filter are bitwise the reference's (see prcnn_valid_flags). */
+enum { PRCNN_CALIB_ROW = 35 };   /* floats per calibration row, here and in every batch struct below whose `calib` has this layout */
 int prcnn_input_stage(int b, int n_max, int stride, int lidar_frame, int image_filter, const int *counts,
                       const float *raw, const float *calib, const float *scope_host, int npoints, float far_depth,
                       int npoints_faraway, const unsigned long long *seeds, float *out, int *stats, int *choice,
@@ -658,10 +659,19 @@ int prcnn_kitti_accumulate_pr(int n_img, const long long *gt_nums, const long lo
 
 /* Statistical normalization (stat_norm/norm.py:186-330 rescale_ptc) over a batch of ragged scenes (csrc/stat_norm.hip).
  * Device pointers; offsets are prefix sums over the scenes (n_scenes + 1 entries).  Points: velo (sum n, 4) f32 raw .bin rows,
- * pt_off; 64-point tiles: tile_off; rescaled boxes: box_off, boxd (n_box, 64) f64 records, boxi (n_box, 16) i32 state (zeroed),
+ * pt_off; 64-point tiles: tile_off; rescaled boxes: box_off, boxd (n_box, PRCNN_SN_BOXD) f64 records, boxi (n_box, PRCNN_SN_BOXI) i32 state (zeroed),
  * mm (n_box, 6) f64 min xyz / max xyz (+inf / -inf; avoid_conflict only); bt_cnt (sum nbox * ntile) i32 at bt_off per scene;
  * rem_cnt (sum ntile) i32; scene_i (n_scenes, 4) i32 = [remainder, patch points, output points, -]; calib (n_scenes, 42) f64 =
- * V2C, R0, inv(R0), C2V; out_off / out (sum n_out, 4) f32 for the write pass.  The field layout is stat_norm.py's _SnBatch. */
+ * V2C, R0, inv(R0), C2V; out_off / out (sum n_out, 4) f32 for the write pass. */
+/* a boxd record, in doubles: what the host fills -- translation, rotation (3 x 3 row-major) and the box-frame bounds before the count pass,
+ * with avoid_conflict the 11 x 3 candidate scales (l, h, w axis order = box-frame x, y, z); before the write pass the chosen scale, the two
+ * align_front shifts (x, z each) and their flags */
+enum {
+    PRCNN_SN_T = 0, PRCNN_SN_R = 3, PRCNN_SN_XLO = 12, PRCNN_SN_XHI, PRCNN_SN_YLO, PRCNN_SN_ZLO, PRCNN_SN_ZHI, PRCNN_SN_SCALE = 17,
+    PRCNN_SN_FSCALE = 50, PRCNN_SN_SHIFT = 53, PRCNN_SN_FLAG1 = 57, PRCNN_SN_FLAG2 = 58, PRCNN_SN_BOXD = 64
+};
+/* a boxi record, in ints: what the host reads after the choose pass -- the inside count and the ratio index -- and the record's width */
+enum { PRCNN_SN_CNT = 0, PRCNN_SN_RIDX = 13, PRCNN_SN_BOXI = 16 };
 typedef struct prcnn_sn_batch {
     int n_scenes, max_tiles, max_boxes, avoid;
     const int *pt_off, *tile_off, *box_off;
@@ -699,8 +709,7 @@ int prcnn_rpn_labels(int b, int n, int g, const float *pts, const float *gt, con
  * into bt_cnt (sum n_box * n_tile) i32; velo (sum n, 4) f32 raw points; calib (n_scenes, 12) f32 = np.dot(V2C.T, R0.T), (4, 3)
  * row-major; boxes (sum g, 7) f32 [x, y_bottom, z, h, w, l, ry]; trig (sum g, 2) f32 from prcnn_gt_box_trig; counts (sum g) i32
  * (zeroed by the caller) = points inside every box; out_off (sum g + 1) i64 = exclusive sums of counts; out (sum counts, 4) f32 =
- * rect x, y, z | intensity, every object's rows in point-index order.  max_tiles / max_boxes: the largest scene's.
- * The field layout is gt_database.py's _GtBatch. */
+ * rect x, y, z | intensity, every object's rows in point-index order.  max_tiles / max_boxes: the largest scene's. */
 typedef struct prcnn_gt_batch {
     int n_scenes, max_tiles, max_boxes, reserved;
     const int *pt_off, *tile_off, *box_off;
@@ -721,7 +730,7 @@ int prcnn_gt_extract_write(const prcnn_gt_batch *batch, void *stream);
 
 /* Augmented-scene generation (tools/generate_aug_scene.py:150-249) for a batch of ragged scenes and of jobs = (epoch, scene) pairs
  * over them (csrc/aug_scene.hip).  Device pointers.  Scenes: pt_off / tile_off / box_off (n_scenes + 1) i32 as in prcnn_gt_batch; velo
- * (sum n, 4) f32 raw points; calib (n_scenes, 35) f32 = V2C | R0 | P2 | image height, width (prcnn_valid_flags' layout); scope 6 f64
+ * (sum n, 4) f32 raw points; calib (n_scenes, PRCNN_CALIB_ROW) f32 = V2C | R0 | P2 | image height, width (prcnn_valid_flags' layout); scope 6 f64
  * x0, x1, y0, y1, z0, z1 (PC_AREA_SCOPE); boxes (sum g, 7) f32 = the scenes' non-DontCare label boxes; rect (sum n, 4) f32 and valid
  * (sum n) u8: the filter's results (rect x, y, z | intensity; valid flag).  Jobs: job_scene (n_jobs) i32; jt_off (n_jobs + 1) i64 into
  * tile_cnt (sum of the jobs' scenes' tiles) i32; cand_n (n_jobs) i32 <= 16 candidates in try order with cand_db (n_jobs, 16) i32 =
@@ -729,8 +738,7 @@ int prcnn_gt_extract_write(const prcnn_gt_batch *batch, void *stream);
  * cand_move (n_jobs, 16) f64 = move_height; sizes (n_jobs, 18) i32 = [kept points, accepted, the accepted slots in acceptance order
  * (-1 behind them)].  Database: db_pts (sum m, 4) f32 rect x, y, z | intensity, db_off (n_db + 1) i64.  Output: out_off (n_jobs + 1) i64
  * rows per job, obj_off (n_jobs, 17) i64 = first row of every accepted object (and the end of the last), out (rows, 4) f32 = the kept
- * points in point order, then the accepted objects' points.  max_tiles: the largest scene's.  The field layout is aug_scene.py's
- * _AugBatch. */
+ * points in point order, then the accepted objects' points.  max_tiles: the largest scene's. */
 typedef struct prcnn_aug_batch {
     int n_scenes, n_jobs, max_tiles, n_db;
     const int *pt_off, *tile_off, *box_off;
@@ -759,18 +767,21 @@ int prcnn_aug_write(const prcnn_aug_batch *batch, void *stream);
 /* RPN training input stage (lib/datasets/kitti_rcnn_dataset.py:249-382 get_rpn_sample in TRAIN mode, GT-aug :428-531 and
  * data_augmentation :533-591 included) for a batch of ragged scenes (csrc/train_input.hip).  Device pointers.  Scenes: pt_off /
  * tile_off / box_off (n_scenes + 1) i32 as in prcnn_aug_batch; velo (sum n, 4) f32 raw points, or rect x, y, z | intensity where
- * is_rect (n_scenes) u8 is set; calib (n_scenes, 35) f32 and scope 6 f64 as in prcnn_aug_batch, the scope applied when reduce_by_range;
- * box_rec (sum g, 11) f64 = the overlap records of the scenes' non-DontCare boxes (w, l + 0.5): the four BEV corners x, z of the f32
- * corner array, min_h, max_h, the f32 volume term; cand_n (n_scenes) i32, cand_rec (n_scenes, 16, 11) f64 the candidates' records,
+ * is_rect (n_scenes) u8 is set; calib (n_scenes, PRCNN_CALIB_ROW) f32 and scope 6 f64 as in prcnn_aug_batch, the scope applied when reduce_by_range;
+ * box_rec (sum g, PRCNN_TR_REC) f64 = the overlap records of the scenes' non-DontCare boxes (w, l + 0.5): the four BEV corners x, z of the f32
+ * corner array, min_h, max_h, the f32 volume term; cand_n (n_scenes) i32, cand_rec (n_scenes, 16, PRCNN_TR_REC) f64 the candidates' records,
  * cand_box (n_scenes, 16, 7) f32 placed boxes, cand_trig (n_scenes, 16, 2) f32, cand_move (n_scenes, 16) f64 = move_height.
  * Work: rect (sum n, 4) f32, valid and flag (sum n) u8 (flag: bit 0 kept, bit 1 near), tile_cnt (2 * tiles) i32 interleaved kept /
  * near ordered exclusive offsets, lists (3, sum n) i32 = the kept / near / far points' indices in point order.  sizes (n_scenes, 19)
  * i32 = [kept points, near kept points, accepted, the accepted slots in acceptance order (-1 behind them)]: the block the host reads.
  * Emit: db_pts (n_db_rows, 4) f32 resident rect x, y, z | intensity; codes (n_scenes, npoints) i64 = kind << 56 | slot << 48 | value
- * with kind 0 / 1 / 2 a rank in the kept / near / far list and kind 3 a database row whose object sits in candidate slot `slot`; aug
+ * with kind 0 / 1 / 2 (PRCNN_TR_KEPT / NEAR / FAR) a rank in the kept / near / far list and kind 3 (PRCNN_TR_DB) a database row whose object sits in candidate slot `slot`; aug
  * (n_scenes, 6) f64 = rotmat.T as m00, m10, m01, m11, the f32 scale, flags (1 rotation, 2 scaling, 4 flip); pts_rect (n_scenes,
  * npoints, 3), pts_input (n_scenes, npoints, input_channels = 3 | 4), pts_features (n_scenes, npoints, 1) f32.  max_tiles: the largest tile count among the scenes
- * [scene_begin, scene_end) of a place call (it sizes the grid).  The field layout is train_input.py's _TrainBatch. */
+ * [scene_begin, scene_end) of a place call (it sizes the grid). */
+enum { PRCNN_TR_REC = 11 };   /* doubles per overlap record */
+/* an emit code: kind << PRCNN_TR_KIND_SHIFT | slot << PRCNN_TR_SLOT_SHIFT | value (the bits below the slot) */
+enum { PRCNN_TR_KEPT = 0, PRCNN_TR_NEAR, PRCNN_TR_FAR, PRCNN_TR_DB, PRCNN_TR_SLOT_SHIFT = 48, PRCNN_TR_KIND_SHIFT = 56 };
 typedef struct prcnn_train_batch {
     int n_scenes, max_tiles, npoints, input_channels, reduce_by_range, scene_begin, scene_end, reserved;
     long long n_db_rows;
@@ -815,7 +826,7 @@ int prcnn_rcnn_max_tries(void);
  * position reads from the torch stream; method 0 'single', 1 'multiple'.  Work: table (n_fg, n_pool) f32.  Out: out_rois the tried
  * boxes that stay, out_pool_rois the same enlarged by pool_extra_width, out_gt (n_rois, 7) their ground truth, out_iou the gt_iou rule,
  * out_src the source RoI, out_cnt / out_keep the try count and the last try's keep flag, out_tried (n_rois, max(fg_times, bg_times, 1))
- * every tried IoU (NaN behind them), used[0] = the numpy draws consumed.  The field layout is rcnn_targets.py's _AugArgs. */
+ * every tried IoU (NaN behind them), used[0] = the numpy draws consumed. */
 typedef struct prcnn_rcnn_aug {
     int m, g, n_rois, n_fg, fg_times, bg_times, method, n_pool;
     float pos_thresh, pool_extra_width;
@@ -833,7 +844,7 @@ int prcnn_rcnn_aug_rois(const prcnn_rcnn_aug *args, void *stream);
 /* (c) one pass over the pooled rows: pooled (rows, s, cin) f32 and empty (rows) i32 as prcnn_roipool3d leaves them, rows = scenes x
  * sampled RoIs; aug_rand (3, rows) f32 the rotation / scale / flip uniforms (read when aug_data), rot_scale = pi / AUG_ROT_RANGE ->
  * rois_out, gt_out (rows, 7) (augmented RoI; target box in the RoI's canonical frame), sampled_pts (rows, s, 3), pts_feature
- * (rows, s, cin - 3), cls_label and reg_valid (rows) i64.  The field layout is rcnn_targets.py's _TargetArgs. */
+ * (rows, s, cin - 3), cls_label and reg_valid (rows) i64. */
 typedef struct prcnn_rcnn_target_args {
     int rows, s, cin, aug_data;
     float rot_scale, reg_fg, cls_fg, cls_bg;
