@@ -5,7 +5,7 @@ reading ``cfg.RPN.SA_CONFIG.NPOINTS`` etc. works unchanged, but an ordinary obje
 passed around explicitly; ``make_cfg()`` returns a fresh tree holding the library defaults and
 ``apply_eval_defaults()`` overlays the values the reference evaluates with
 (pointrcnn/tools/cfgs/default.yaml + the eval_mode 'rcnn' switches of eval_rcnn.py:883-887).
-Only keys that the inference path, the training input stages and the losses read are kept; other training-only
+Only keys that the inference path, the training input stages, the losses and the train loop read are kept; other training-only
 keys are accepted on merge and stored, never interpreted.
 """
 import copy
@@ -78,7 +78,11 @@ _LIBRARY_DEFAULTS = {
         "FOCAL_ALPHA": [0.25, 0.75], "FOCAL_GAMMA": 2.0,
     },
     "TRAIN": {"SPLIT": "train", "VAL_SPLIT": "smallval", "RPN_PRE_NMS_TOP_N": 12000,
-              "RPN_POST_NMS_TOP_N": 2048, "RPN_NMS_THRESH": 0.85, "RPN_DISTANCE_BASED_PROPOSE": True},
+              "RPN_POST_NMS_TOP_N": 2048, "RPN_NMS_THRESH": 0.85, "RPN_DISTANCE_BASED_PROPOSE": True,
+              # the weight step and the loop (optim.py, train_rcnn.py; lib/config.py:147-168)
+              "OPTIMIZER": "adam", "LR": 0.002, "WEIGHT_DECAY": 0.0, "MOMS": [0.95, 0.85], "DIV_FACTOR": 10.0, "PCT_START": 0.4,
+              "GRAD_NORM_CLIP": 1.0, "BN_MOMENTUM": 0.9, "BN_DECAY": 0.5, "BNM_CLIP": 0.01,
+              "BN_DECAY_STEP_LIST": [50, 100, 150, 200, 250, 300]},
     "TEST": {"SPLIT": "val", "RPN_PRE_NMS_TOP_N": 9000, "RPN_POST_NMS_TOP_N": 300,
              "RPN_NMS_THRESH": 0.7, "RPN_DISTANCE_BASED_PROPOSE": True},
 }
@@ -91,6 +95,11 @@ _EVAL_OVERLAY = {
     "RCNN": {"ENABLED": True, "ROI_SAMPLE_JIT": True},
     "TRAIN": {"RPN_PRE_NMS_TOP_N": 9000, "RPN_POST_NMS_TOP_N": 512},
     "TEST": {"RPN_POST_NMS_TOP_N": 100, "RPN_NMS_THRESH": 0.8},
+}
+
+# values of tools/cfgs/default.yaml's TRAIN section that differ from the library defaults and that the train loop reads
+_TRAIN_OVERLAY = {
+    "TRAIN": {"OPTIMIZER": "adam_onecycle", "WEIGHT_DECAY": 0.001, "BN_MOMENTUM": 0.1, "BN_DECAY_STEP_LIST": [1000]},
 }
 
 
@@ -132,6 +141,20 @@ def apply_eval_defaults(cfg, eval_mode="rcnn"):
         cfg.RPN.ENABLED, cfg.RCNN.ENABLED = True, False
     else:
         raise ValueError("unsupported eval_mode %r" % eval_mode)
+    return cfg
+
+
+def apply_train_defaults(cfg, train_mode="rpn"):
+    """default.yaml's values, then the train_mode switches of tools/train_rcnn.py:159-166"""
+    merge_into(_EVAL_OVERLAY, cfg)
+    merge_into(_TRAIN_OVERLAY, cfg)
+    if train_mode == "rpn":
+        cfg.RPN.ENABLED, cfg.RCNN.ENABLED = True, False
+    elif train_mode == "rcnn":
+        cfg.RCNN.ENABLED = True
+        cfg.RPN.ENABLED = cfg.RPN.FIXED = True
+    else:
+        raise NotImplementedError("train_mode %r" % (train_mode,))
     return cfg
 
 

@@ -13,6 +13,10 @@ from .rpn import _head
 
 
 class RCNNNet(nn.Module):
+    # the order in which the reference registers its children (rcnn_net.py:18-81: SA_modules first).  optim.layer_groups walks the
+    # children in this order: an optimizer checkpoint keys its state by the parameter's index over the groups
+    REFERENCE_CHILD_ORDER = ("SA_modules", "xyz_up_layer", "merge_down_layer", "cls_layer", "reg_layer")
+
     def __init__(self, cfg, num_classes, input_channels=0, use_xyz=True):
         super().__init__()
         self.cfg = cfg

@@ -1,0 +1,192 @@
+"""The train loop (reference: tools/train_rcnn.py with TRAIN.OPTIMIZER 'adam_onecycle' and tools/train_utils/train_utils.py
+Trainer.train / checkpoint_state / load_checkpoint / load_part_ckpt): a KITTI-format tree and a GT database -> checkpoints.
+
+  python -m 3d_adapt_auto_driving_amd.train_rcnn --train_mode rpn|rcnn --root R [--gt_database DB.pkl] [--cfg_file Y] [--batch_size 16]
+         [--epochs 200] [--ckpt_save_interval 5] [--ckpt C] [--rpn_ckpt C] [--npoints_faraway 4000] [--output_dir D] [--seed S]
+         [--device cuda|cpu] [--set K V ...]
+
+``rpn`` trains the first stage alone (RPN.ENABLED, RCNN off); ``rcnn`` trains the second stage on a fixed first one (RCNN.ENABLED,
+RPN.ENABLED = RPN.FIXED = True; the RPN's parameters are frozen AFTER the optimizer is built, so they keep their places in its groups).
+total_steps = len(loader) x epochs, with len(loader) = len(split) // batch_size (the last short batch is dropped).
+
+Per epoch: the BatchNorm momentum from the GLOBAL iteration (as bnm_scheduler.step(it)), then a seeded permutation of the split.
+Per iteration: schedule(it), zero_grad, RpnTrainInput.batch -> losses.model_fn -> backward -> OneCycleAdam.step().
+Outputs under --output_dir: ckpt/checkpoint_epoch_N.pth = {'epoch', 'it', 'model_state', 'optimizer_state'} every --ckpt_save_interval
+epochs (the reference's layout: either side resumes the other's file), log_train.txt, and train_log.jsonl with one line per iteration
+{it, epoch, lr, loss, grad_norm, the tb_dict entries}: it stands in for the reference's tensorboard events ('it' counts finished
+iterations, as the reference's event step does; 'lr' is the rate that iteration ran with).
+--ckpt resumes the model, the optimizer, 'it' and 'epoch'; --rpn_ckpt is load_part_ckpt (the keys the model has).
+--device cpu selects the checker paths of the input stage, the losses and the optimizer; the model's operators exist for CUDA tensors
+only, so a cpu run needs the test suite's stand-ins for them and is of use to tests alone.  --set K V ... (last on the line) overrides
+configuration keys, as in eval_rcnn.
+
+Out of scope, each raising NotImplementedError with its own name before anything is written: --mgpus, --train_with_eval,
+--train_mode rcnn_offline, TRAIN.OPTIMIZER 'adam' and 'sgd' (with their LambdaLR and warm-up schedulers).
+"""
+import argparse
+import json
+import logging
+import os
+
+import numpy as np
+
+
+def load_part_ckpt(model, filename, log):
+    import torch
+    if not os.path.isfile(filename):
+        raise FileNotFoundError(filename)
+    state = torch.load(filename, map_location="cpu", weights_only=False)["model_state"]
+    own = model.state_dict()
+    update = {k: v for k, v in state.items() if k in own}
+    if not update:
+        raise RuntimeError("train_rcnn: %s holds no key of this model" % filename)
+    own.update(update)
+    model.load_state_dict(own)
+    log.info("==> Done (loaded %d/%d)" % (len(update), len(own)))
+
+
+def load_checkpoint(model, optimizer, filename, log):
+    """-> (it, epoch)"""
+    import torch
+    if not os.path.isfile(filename):
+        raise FileNotFoundError(filename)
+    log.info("==> Loading from checkpoint '%s'" % filename)
+    ckpt = torch.load(filename, map_location="cpu", weights_only=False)
+    if ckpt.get("model_state") is not None:
+        model.load_state_dict(ckpt["model_state"])
+    if ckpt.get("optimizer_state") is not None:
+        optimizer.load_state_dict(ckpt["optimizer_state"])
+    return int(ckpt.get("it", 0)), int(ckpt.get("epoch", -1))
+
+
+def save_checkpoint(model, optimizer, epoch, it, filename):
+    import torch
+    torch.save({"epoch": epoch, "it": it, "model_state": model.state_dict(), "optimizer_state": optimizer.state_dict()}, filename)
+
+
+def build_parser():
+    ap = argparse.ArgumentParser(prog="python -m 3d_adapt_auto_driving_amd.train_rcnn", description=__doc__.split("\n")[0])
+    ap.add_argument("--train_mode", type=str, required=True)
+    ap.add_argument("--root", type=str, required=True)
+    ap.add_argument("--gt_database", type=str, default=None)
+    ap.add_argument("--cfg_file", type=str, default=None)
+    ap.add_argument("--batch_size", type=int, default=16)
+    ap.add_argument("--epochs", type=int, default=200)
+    ap.add_argument("--ckpt_save_interval", type=int, default=5)
+    ap.add_argument("--ckpt", type=str, default=None)
+    ap.add_argument("--rpn_ckpt", type=str, default=None)
+    ap.add_argument("--npoints_faraway", type=int, default=4000)
+    ap.add_argument("--output_dir", type=str, default=None)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--device", type=str, default="cuda")
+    ap.add_argument("--mgpus", action="store_true")
+    ap.add_argument("--train_with_eval", action="store_true")
+    ap.add_argument("--set", dest="set_cfgs", default=None, nargs=argparse.REMAINDER)
+    return ap
+
+
+def make_cfg(a):
+    """The configuration of a run; raises for what is out of scope"""
+    from . import config
+    if a.mgpus:
+        raise NotImplementedError("train_rcnn: --mgpus is out of scope")
+    if a.train_with_eval:
+        raise NotImplementedError("train_rcnn: --train_with_eval is out of scope")
+    if a.train_mode == "rcnn_offline":
+        raise NotImplementedError("train_rcnn: --train_mode rcnn_offline is out of scope")
+    if a.train_mode not in ("rpn", "rcnn"):
+        raise NotImplementedError("train_rcnn: --train_mode %r" % (a.train_mode,))
+    cfg = config.make_cfg()
+    config.apply_train_defaults(cfg, a.train_mode)
+    if a.gt_database:
+        cfg["GT_AUG_ENABLED"], cfg["GT_AUG_RAND_NUM"], cfg["GT_AUG_APPLY_PROB"] = True, True, 1.0      # what the shipped yamls set
+    if a.cfg_file:
+        config.cfg_from_file(cfg, a.cfg_file)
+        cfg.TAG = os.path.splitext(os.path.basename(a.cfg_file))[0]
+    if a.set_cfgs:
+        config.cfg_from_list(cfg, a.set_cfgs)
+    if a.train_mode == "rpn":                                 # the mode wins over the file, as in the reference
+        cfg.RPN.ENABLED, cfg.RCNN.ENABLED = True, False
+    else:
+        cfg.RCNN.ENABLED = True
+        cfg.RPN.ENABLED = cfg.RPN.FIXED = True
+    if cfg.TRAIN.OPTIMIZER != "adam_onecycle":
+        raise NotImplementedError("train_rcnn: TRAIN.OPTIMIZER %r is out of scope (adam_onecycle is what this loop runs)" % (cfg.TRAIN.OPTIMIZER,))
+    return cfg
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
+    cfg = make_cfg(a)
+    import torch
+    from . import losses, optim
+    from .net.point_rcnn import PointRCNN
+    from .train_input import RpnTrainInput
+
+    out_dir = a.output_dir or os.path.join("output", a.train_mode, cfg.TAG)
+    ckpt_dir = os.path.join(out_dir, "ckpt")
+    os.makedirs(ckpt_dir, exist_ok=True)
+    log = logging.getLogger("train_rcnn.%s" % os.path.abspath(out_dir))
+    log.setLevel(logging.INFO)
+    log.propagate = False
+    handlers = [logging.FileHandler(os.path.join(out_dir, "log_train.txt")), logging.StreamHandler()]
+    for h in handlers:
+        h.setFormatter(logging.Formatter("%(asctime)s  %(levelname)5s  %(message)s"))
+        log.addHandler(h)
+    try:
+        log.info("**********************Start logging**********************")
+        for key, val in vars(a).items():
+            log.info("{:16} {}".format(key, val))
+        src = RpnTrainInput(a.root, cfg, a.gt_database, split=cfg.TRAIN.SPLIT, classes=cfg.CLASSES, npoints=cfg.RPN.NUM_POINTS,
+                            npoints_faraway=a.npoints_faraway, seed=a.seed, device=a.device)
+        per_epoch = len(src) // a.batch_size
+        if per_epoch < 1:
+            raise ValueError("train_rcnn: the split holds %d samples, fewer than one batch of %d" % (len(src), a.batch_size))
+        torch.manual_seed(a.seed)
+        model = PointRCNN(cfg, num_classes=2, use_xyz=True, mode="TRAIN").to(a.device)
+        T = cfg.TRAIN
+        opt = optim.OneCycleAdam(model, per_epoch * a.epochs, T.LR, list(T.MOMS), T.DIV_FACTOR, T.PCT_START, T.WEIGHT_DECAY, T.GRAD_NORM_CLIP)
+        if cfg.RPN.ENABLED and cfg.RPN.FIXED:                 # after the optimizer is built: the groups keep the RPN's parameters
+            for p in model.rpn.parameters():
+                p.requires_grad = False
+        it = start_epoch = 0
+        if a.ckpt is not None:
+            it, start_epoch = load_checkpoint(model, opt, a.ckpt, log)
+            log.info("==> resumed at epoch %d, it %d" % (start_epoch, it))
+        if a.rpn_ckpt is not None:
+            load_part_ckpt(model, a.rpn_ckpt, log)
+        order = np.random.RandomState(a.seed)
+        for _ in range(start_epoch):                          # the permutations of the epochs already trained
+            order.permutation(len(src))
+        log.info("**********************Start training**********************")
+        model.train()
+        with open(os.path.join(out_dir, "train_log.jsonl"), "a") as events:
+            for epoch in range(start_epoch, a.epochs):
+                optim.set_bn_momentum(model, optim.bn_momentum(cfg, it))
+                perm = order.permutation(len(src))
+                for k in range(per_epoch):
+                    opt.schedule(it)
+                    lr = opt.lr
+                    opt.zero_grad()
+                    batch = src.batch(perm[k * a.batch_size:(k + 1) * a.batch_size])
+                    loss, tb_dict, disp_dict = losses.model_fn(cfg, model, batch)
+                    loss.backward()
+                    opt.step()
+                    it += 1
+                    line = dict(it=it, epoch=epoch, lr=lr, loss=float(loss.detach()), grad_norm=float(opt.total_norm), **tb_dict)
+                    events.write(json.dumps(line) + "\n")
+                    events.flush()
+                    log.info("epoch %d it %d lr %.6e %s" % (epoch, it, lr, " ".join("%s %.4f" % kv for kv in sorted(disp_dict.items()))))
+                trained = epoch + 1
+                if trained % a.ckpt_save_interval == 0:
+                    save_checkpoint(model, opt, trained, it, os.path.join(ckpt_dir, "checkpoint_epoch_%d.pth" % trained))
+        log.info("**********************End training**********************")
+    finally:
+        for h in handlers:
+            log.removeHandler(h)
+            h.close()
+    return it
+
+
+if __name__ == "__main__":
+    main()

@@ -895,6 +895,30 @@ int prcnn_cls_loss(const prcnn_loss_args *args, void *stream);
 /* the bin-based regression loss's terms and grad_reg, then the one-block finish that writes parts */
 int prcnn_reg_loss(const prcnn_loss_args *args, void *stream);
 
+/* The weight step of training over every parameter tensor of a model: gradient-norm clip (torch.nn.utils.clip_grad_norm_), decoupled weight
+ * decay (tools/train_utils/fastai_optim.py OptimWrapper.step) and torch.optim.Adam, in the three calls below in this order on one stream,
+ * with no host read between them (csrc/optim.hip, optim.py).  The tensors are described by a table of plain DEVICE arrays:
+ *   per tensor (n_tensors): param / grad / exp_avg / exp_avg_sq addresses of contiguous f32 data (0: absent), numel, flags (bit 0 "decay":
+ *   param *= 1 - wd lr; bit 1 "adam": the tensor has a grad and state), step (the tensor's own Adam step count);
+ *   per chunk (n_chunks): chunk_tensor and chunk_start -- a chunk is at most PRCNN_OPTIM_CHUNK consecutive elements of one tensor, every
+ *   element of every tensor lies in exactly one chunk.
+ * work: prcnn_optim_workspace(n_chunks) doubles; after prcnn_optim_finish work[0] is the total gradient norm over every tensor with a
+ * grad address and work[1] = min(1, max_norm / (work[0] + 1e-6)).  The arithmetic runs in f64 from the f32 state and every stored value
+ * is rounded to f32 once; the sums have a fixed shape (no atomics: the same input gives the same bits).  Grads are read, never written. */
+enum { PRCNN_OPTIM_CHUNK = 2048 };
+int prcnn_optim_workspace(int n_chunks);
+/* work[2 + chunk] = sum of squares of the chunk's grads (0 where the tensor has none) */
+int prcnn_optim_sumsq(const unsigned long long *grad_addr, const long long *numel, const int *chunk_tensor, const long long *chunk_start,
+                      int n_tensors, int n_chunks, double *work, void *stream);
+/* one workgroup: work[0], work[1]; step += 1 of every tensor flagged "adam" */
+int prcnn_optim_finish(const unsigned char *flags, int *steps, int n_tensors, int n_chunks, double max_norm, double *work, void *stream);
+/* g = grad work[1]; "decay": p *= 1 - wd lr; "adam": m += (g - m)(1 - beta1), v = beta2 v + (1 - beta2) g g,
+ * p -= lr / (1 - beta1^step) m / (sqrt(v) / sqrt(1 - beta2^step) + eps) */
+int prcnn_optim_update(const unsigned long long *param_addr, const unsigned long long *grad_addr, const unsigned long long *exp_avg_addr,
+                       const unsigned long long *exp_avg_sq_addr, const long long *numel, const unsigned char *flags, const int *steps,
+                       const int *chunk_tensor, const long long *chunk_start, int n_tensors, int n_chunks, double lr, double beta1,
+                       double beta2, double eps, double wd, const double *work, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
