@@ -588,6 +588,24 @@ def rows_layer_bf16x3_wrapper(a, wt, bias, relu, out):
     return out
 
 
+def resplit_weights_bf16x3(tensors):
+    """``tensors`` were rewritten in place (FastPointRCNN.reload_weights): every cached split of a matrix that lies inside one of them
+    is made again INTO ITS OWN BUFFER (a captured graph holds its address) and filed under the tensor's new version.  A view shares
+    its base's version counter, so a slice of a rewritten matrix is found under the base's.  -> the number of splits made again."""
+    done = 0
+    for key in list(_SPLIT_W):
+        ptr, _, K, N, dev = key
+        for t in tensors:
+            lo = t.data_ptr()
+            if str(t.device) == dev and lo <= ptr and ptr + K * N * 4 <= lo + t.numel() * t.element_size():
+                ws = _SPLIT_W.pop(key)
+                _lib.call("prcnn_split_weights_bf16x3", K, N, ptr, ws.data_ptr(), _lib.current_stream(t))
+                _SPLIT_W[(ptr, t._version, K, N, dev)] = ws
+                done += 1
+                break
+    return done
+
+
 def packed_layer_interp_wrapper(a, wt, bias, relu, out, G, idx, weight):
     """out = act((a @ wt + bias) + interp3(G)): the first layer of a feature-propagation module with the interpolation behind the
     layer's linear part (prcnn_packed_layer_interp).  a (B*n, K) skip features, wt (K, N), G (B, m, N) = coarse features @ the

@@ -10,8 +10,9 @@ Differences that are deliberate:
     one all_gather at the end (the reference is single-process);
   * the reference's dataloader bug (`far_points=` keyword, eval_rcnn.py:862) is not reproduced.
 
-CLI (subset of the reference's flags):  python -m ... --cfg_file X --eval_mode rcnn --ckpt Y
+CLI (subset of the reference's flags):  python -m ... --cfg_file X --eval_mode rcnn --ckpt Y [--rpn_ckpt C] [--rcnn_ckpt C]
   --batch_size 8 --output_dir out [--set K V ...] [--scenes 64]
+  --eval_all --ckpt_dir D [--start_epoch E] [--extra_tag T] [--wait SECONDS]: every unevaluated checkpoint of D (eval_sweep.py)
 """
 import argparse
 import collections
@@ -199,7 +200,7 @@ def eval_scenes(*args, **kwargs):
 
 @torch.no_grad()
 def eval_scenes_pinned(model, cfg, device, source, scene_ids, batch_size=8, output_dir=None, workers=None, device_input=False,
-                       recall=None, stats=None):
+                       recall=None, stats=None, runner=None):
     """Evaluate ``scene_ids`` of a scene source (kitti_io.KittiSource / SyntheticSource) on this rank:
     the counterpart of the batch loop of eval_one_epoch_joint (eval_rcnn.py:493-649) incl. the KITTI
     result files.  Returns (table, counts) as pack_detections.
@@ -211,12 +212,15 @@ def eval_scenes_pinned(model, cfg, device, source, scene_ids, batch_size=8, outp
     and the near/far sampler run on the device (kitti_io.DeviceInputStage, csrc/input_stage.hip).
     ``recall``: a RecallStats that receives every batch's RoIs / refined boxes and the source's ground-truth boxes
     (the reference's recall statistics, skipped with --test).  ``stats``: a dict that receives the completion time of
-    every batch (``batch_done``), for steady-state throughput measurements."""
+    every batch (``batch_done``), for steady-state throughput measurements.  ``runner``: a runner of ``model`` that the caller
+    keeps across calls (the checkpoint sweep: its engine and captured graphs stay, the weights are reloaded in between); it comes
+    back flushed."""
     if output_dir:
         os.makedirs(output_dir, exist_ok=True)
     M = cfg.TEST.RPN_POST_NMS_TOP_N
     on_gpu = torch.device(device).type == "cuda"
-    runner = make_runner(model, cfg, device) if on_gpu else None
+    if runner is None:
+        runner = make_runner(model, cfg, device) if on_gpu else None
     budget = host_budget()
     if stats is not None:
         stats["host_budget"] = {"loaders": budget["loaders"], "writers": budget["writers"], "cores": len(budget["cores"]), "pin": len(budget["pin"]),
@@ -419,17 +423,18 @@ def steady_state_rate(stats, batch_size):
 
 @torch.no_grad()
 def eval_scenes_rpn(model, cfg, device, source, scene_ids, batch_size=8, output_dir=None, test=False, save_feature=False,
-                    stats=None, labels=None):
+                    stats=None, labels=None, runner=None):
     """--eval_mode rpn over ``scene_ids`` (eval_one_epoch_rpn, eval_rcnn.py:120-260).  Per batch: the RPN stage and proposal layer
     (RpnRunner); unless ``test``, the sources' EVAL-mode gt_boxes3d are packed and the label kernel (csrc/rpn_labels.hip) labels the
     backbone's xyz and counts (correct, fg, pred) per scene; ``stats`` (rpn_eval.RpnStats) takes the counters and the recall of the
     RoIs.  ``output_dir``: the reference's files (detections/data, seg_result, features/ with ``save_feature``), written by writer
     processes.  ``labels``: a list that receives each batch's (ids, cls (B, N) int32 host array).  Returns per scene the host
-    (rois, roi_scores_raw) in scene order."""
+    (rois, roi_scores_raw) in scene order.  ``runner``: a runner of ``model`` kept by the caller across calls (the checkpoint sweep)."""
     from . import rpn_eval
     import multiprocessing
     from concurrent.futures import ProcessPoolExecutor
-    runner = make_runner(model, cfg, device)
+    if runner is None:
+        runner = make_runner(model, cfg, device)
     thresh = float(cfg.RPN.SCORE_THRESH)
     writers, jobs, out = None, [], []
     if output_dir:
@@ -530,11 +535,19 @@ def eval_synthetic(model, cfg, device, scene_ids, batch_size=8, npoints=16384, o
     return eval_scenes(model, cfg, device, src, scene_ids, batch_size, output_dir)
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(description="PointRCNN joint evaluation on synthetic KITTI-shaped scenes (MI355X)")
     ap.add_argument("--cfg_file", type=str, default=None, help="reference-style yaml (tools/cfgs/*.yaml)")
     ap.add_argument("--eval_mode", type=str, default="rcnn")
     ap.add_argument("--ckpt", type=str, default=None, help="reference .pth checkpoint (random init if omitted)")
+    ap.add_argument("--rpn_ckpt", type=str, default=None, help="load_part_ckpt after --ckpt: the keys of this file that the model has")
+    ap.add_argument("--rcnn_ckpt", type=str, default=None, help="load_part_ckpt after --ckpt and --rpn_ckpt")
+    ap.add_argument("--eval_all", action="store_true", help="evaluate every checkpoint of --ckpt_dir that the record file does not list")
+    ap.add_argument("--ckpt_dir", type=str, default=None, help="--eval_all: directory of *checkpoint_epoch_*.pth (or a train_rcnn output directory)")
+    ap.add_argument("--start_epoch", type=int, default=0, help="--eval_all: skip checkpoints whose epoch id is below this")
+    ap.add_argument("--extra_tag", type=str, default="default", help="--eval_all: results go to <output_dir>/eval/eval_all_<extra_tag>")
+    ap.add_argument("--wait", type=float, default=None, metavar="SECONDS",
+                    help="--eval_all: when no unevaluated checkpoint is left, look again every SECONDS instead of returning")
     ap.add_argument("--batch_size", type=int, default=8)
     ap.add_argument("--scenes", type=int, default=16, help="number of synthetic scenes (ignored with --data_root)")
     ap.add_argument("--raw_points", type=int, default=None,
@@ -556,7 +569,25 @@ def main(argv=None):
     ap.add_argument("--save_rpn_feature", action="store_true", help="--eval_mode rpn: also write the backbone features (features/)")
     ap.add_argument("--test", action="store_true", help="--eval_mode rpn: no ground truth (no labels, no statistics)")
     ap.add_argument("--set", dest="set_cfgs", default=None, nargs=argparse.REMAINDER)
-    args = ap.parse_args(argv)
+    return ap
+
+
+def load_part_ckpts(model, args, log=None):
+    """--rpn_ckpt, then --rcnn_ckpt: train_rcnn.load_part_ckpt (the keys of the file that the model has; RuntimeError when none is)"""
+    from .train_rcnn import load_part_ckpt
+    import logging
+    log = log or logging.getLogger("eval_rcnn")
+    for name in (args.rpn_ckpt, args.rcnn_ckpt):
+        if name:
+            load_part_ckpt(model, name, log)
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    if args.eval_all and not args.ckpt_dir:
+        raise ValueError("eval_rcnn: --eval_all needs --ckpt_dir")
+    if args.eval_all and not args.output_dir:
+        raise ValueError("eval_rcnn: --eval_all needs --output_dir (the record file and the per-epoch results live under it)")
 
     cfg = config_mod.make_cfg()
     config_mod.apply_eval_defaults(cfg, args.eval_mode)
@@ -575,50 +606,74 @@ def main(argv=None):
     model = build_model(cfg, device)
     if args.ckpt:
         load_checkpoint(model, args.ckpt)
-    out = os.path.join(args.output_dir, "final_result", "data") if args.output_dir else None
     from . import kitti_io
     if args.data_root:
         source = kitti_io.KittiSource(args.data_root, cfg, args.split or cfg.TEST.SPLIT)
     else:
         source = kitti_io.SyntheticSource(cfg, args.scenes, raw_points=args.raw_points)
     my_ids = [source.ids[i] for i in shard_scene_ids(len(source.ids), rank, world)]
+    if args.eval_all:
+        from . import eval_sweep
+        return eval_sweep.sweep(args, model, cfg, device, source, my_ids, rank, world)
+    load_part_ckpts(model, args)
+    return evaluate_model(args, model, cfg, device, source, my_ids, rank, args.output_dir)
+
+
+def evaluate_model(args, model, cfg, device, source, my_ids, rank, output_dir, runner=None, labels=None, timings=None):
+    """One evaluation of ``model`` as it stands, in the mode of ``args``: what a --ckpt run does behind its checkpoint load, with its
+    files under ``output_dir``.  -> the mode's result dictionary (rpn: RpnStats.result(), None with --test; rcnn: scenes, detections,
+    the recalls with --recall, the AP dictionary with --eval_ap).  The sweep passes the ``runner`` it keeps, ``labels`` (the source
+    behind a label cache, for the AP) and ``timings``, a dict that receives the seconds of 'inference' and 'ap'."""
+    timings = {} if timings is None else timings
     if args.eval_mode == "rpn":
-        return _main_rpn(args, model, cfg, device, source, my_ids, rank)
+        t0 = time.perf_counter()
+        res = _main_rpn(args, model, cfg, device, source, my_ids, rank, output_dir=output_dir, runner=runner)
+        timings["inference"], timings["ap"] = time.perf_counter() - t0, 0.0
+        return res
+    out = os.path.join(output_dir, "final_result", "data") if output_dir else None
     t0 = time.perf_counter()
     recall = RecallStats(device) if args.recall else None
     stats = {}
     table, counts = eval_scenes(model, cfg, device, source, my_ids, args.batch_size, out, workers=args.workers,
-                                device_input=args.device_input, recall=recall, stats=stats)
+                                device_input=args.device_input, recall=recall, stats=stats, runner=runner)
     elapsed = time.perf_counter() - t0
+    res = {}
     if recall is not None:
-        for k, v in recall.result().items():
+        res.update(recall.result())
+        for k, v in res.items():
             print("rank %d  %s: %s" % (rank, k, v))
     table, counts = all_gather_detections(table, counts, device)
+    timings["inference"], timings["ap"] = time.perf_counter() - t0, 0.0
+    res.update({"scenes": int(table.shape[0]), "detections": int(counts.sum())})
     if rank == 0:
         print("scenes=%d detections=%d  (%.1f scenes/s on this rank incl. the host input stage%s; steady state %.1f scenes/s, "
               "loader start-up excluded)" %
               (table.shape[0], int(counts.sum()), len(my_ids) / max(elapsed, 1e-9),
                " and the result writer" if out else "", steady_state_rate(stats, args.batch_size)))
         if args.eval_ap:
-            text, _ = evaluate_detections(table, counts, source, dataset=args.ap_dataset, device_id=device.index or 0,
-                                          metric=args.ap_metric)
+            t1 = time.perf_counter()
+            text, ap = evaluate_detections(table, counts, labels if labels is not None else source, dataset=args.ap_dataset,
+                                           device_id=device.index or 0, metric=args.ap_metric)
+            timings["ap"] = time.perf_counter() - t1
+            res["ap"] = ap
             print(text)
-            if args.output_dir:
-                with open(os.path.join(args.output_dir, "final_result", "ap.txt"), "w") as f:
+            if output_dir:
+                with open(os.path.join(output_dir, "final_result", "ap.txt"), "w") as f:
                     f.write(text)
+    return res
 
 
-def _main_rpn(args, model, cfg, device, source, my_ids, rank):
+def _main_rpn(args, model, cfg, device, source, my_ids, rank, output_dir=None, runner=None):
     """--eval_mode rpn: eval_scenes_rpn on this rank's scenes and the reference's closing lines.  Returns the statistics dict
     (None with --test).  With more than one rank each rank batches its own shard, so the recall quirk's padding rows (rpn_eval)
     can differ from a single-process run."""
     from . import rpn_eval
     save = args.save_result or args.save_rpn_feature
-    result_dir = args.output_dir or "."
+    result_dir = output_dir or args.output_dir or "."
     stats = None if args.test else rpn_eval.RpnStats(device)
     t0 = time.perf_counter()
     eval_scenes_rpn(model, cfg, device, source, my_ids, args.batch_size, result_dir if save else None, test=args.test,
-                    save_feature=args.save_rpn_feature, stats=stats)
+                    save_feature=args.save_rpn_feature, stats=stats, runner=runner)
     elapsed = time.perf_counter() - t0
     print("rank %d: ---- RPN EVALUATION ---- %d scenes (%.1f scenes/s)" % (rank, len(my_ids), len(my_ids) / max(elapsed, 1e-9)))
     if stats is None:

@@ -230,7 +230,7 @@ class _Mlp:
             self.narrow = None
             w, b, relu = layers[-1]
             if self.padded and w.shape[0] <= 4 and not relu:
-                self.narrow = (_pad2(w.t(), _round128(w.shape[1]), w.shape[0]), b.contiguous())
+                self.narrow = (_pad2(w.t(), _round128(w.shape[1]), w.shape[0]), b.clone())
             return
         self.padded = False
         for i, (w, b, relu) in enumerate(layers):
@@ -244,7 +244,9 @@ class _Mlp:
                 k = w.shape[1]
                 wt = w.new_zeros((_round4(k), w.shape[0]))
                 wt[:k] = w.t()
-            self.layers.append((wt.contiguous(), b.contiguous(), relu))
+            # (b.clone(): the fold of a block without BatchNorm IS the convolution's bias parameter -- the engine owns its copies, so a
+            #  load_state_dict in front of a refused reload_weights() does not reach a batch in flight)
+            self.layers.append((wt.contiguous(), b.clone(), relu))
 
         # split form of the first layer for the "linear before ReLU" shortcut (see _sa_scale)
         self.split = None
@@ -285,8 +287,15 @@ class _Mlp:
         return a
 
 
-def _fold_shared_mlp(mlp):
-    layers = fused_mlp.folded_layers(mlp)
+def _fold_shared_mlp(mlp, fresh=None):
+    """fresh: a dict (reload_weights) -- the fold is computed from the module's current state and kept THERE, by module, instead of
+    in the module's cache (whose tensors a built engine may alias)"""
+    if fresh is None:
+        layers = fused_mlp.folded_layers(mlp)
+    else:
+        if id(mlp) not in fresh:
+            fresh[id(mlp)] = fused_mlp.fold_fresh(mlp)
+        layers = fresh[id(mlp)]
     if layers is None:
         raise NotImplementedError("fast path: unsupported SharedMLP structure")
     return [(w, b, True) for w, b in layers]
@@ -320,8 +329,27 @@ def _state_version(tensors):
     return sum(t._version for t in tensors)
 
 
+def _state_shapes(model):
+    return [(n, tuple(t.shape)) for n, t in list(model.named_parameters()) + list(model.named_buffers())]
+
+
+def _mlp_tensors(name, mlp):
+    """every weight tensor an _Mlp holds, by name: its layers and each derived form made from them"""
+    out = []
+    for i, (wt, b, _) in enumerate(mlp.layers):
+        out += [("%s.layers[%d].w" % (name, i), wt), ("%s.layers[%d].b" % (name, i), b)]
+    for form in ("split", "packed", "wide", "narrow"):
+        ts = getattr(mlp, form, None)
+        for i, t in enumerate(ts or ()):
+            out.append(("%s.%s[%d]" % (name, form, i), t))
+    if getattr(mlp, "wide_cat", None) is not None:
+        out.append((name + ".wide_cat", mlp.wide_cat))
+    return out
+
+
 class FastPointRCNN:
-    def __init__(self, model, cfg):
+    def __init__(self, model, cfg, _fresh=None):
+        """_fresh (reload_weights only): a dict that receives the SharedMLP folds instead of the modules' caches"""
         assert not model.training, "FastPointRCNN is an inference engine: call model.eval() first"
         if cfg.RCNN.ENABLED and cfg.RCNN.USE_INTENSITY:
             raise NotImplementedError("fast path: cfg.RCNN.USE_INTENSITY (reflectance as an RCNN input feature) is not covered")
@@ -335,6 +363,7 @@ class FastPointRCNN:
         self.in_feat = int(model.rpn.backbone_net.SA_modules[0].mlps[0][0].conv.in_channels) - 3
         self._state = _state_tensors(model)
         self._folded_at = _state_version(self._state)       # BN is folded into the weights HERE: see check_weights()
+        self._shapes = _state_shapes(model)                  # what reload_weights() accepts
         rpn = model.rpn
         bb = rpn.backbone_net
         self.sa = []
@@ -342,11 +371,11 @@ class FastPointRCNN:
             scales = []
             for grouper, mlp in zip(sa.groupers, sa.mlps):
                 cin = mlp[0].conv.in_channels - 3
-                scales.append((grouper.radius, grouper.nsample, _Mlp(_fold_shared_mlp(mlp), grouped_c=cin), cin))
+                scales.append((grouper.radius, grouper.nsample, _Mlp(_fold_shared_mlp(mlp, _fresh), grouped_c=cin), cin))
             self.sa.append((sa.npoint, scales))
         # FP module k consumes [features interpolated from level k+1 | skip features of level k]
         sa_w = [sum(sc[2].n_out for sc in scales) for _, scales in self.sa]
-        folded = [_fold_shared_mlp(fp.mlp) for fp in bb.FP_modules]
+        folded = [_fold_shared_mlp(fp.mlp, _fresh) for fp in bb.FP_modules]
         self.fp = []
         for k, lay in enumerate(folded):
             known = sa_w[-1] if k == len(folded) - 1 else folded[k + 1][-1][0].shape[0]
@@ -357,15 +386,15 @@ class FastPointRCNN:
         self.rpn_tail = self._fold_rpn_tail() if (USE_RPN_TAIL and PAD128 and USE_POINT_LAYER) else None
         if cfg.RCNN.ENABLED:
             r = model.rcnn_net
-            self.xyz_up = _Mlp(_fold_shared_mlp(r.xyz_up_layer))
-            self.merge_down = _Mlp(_fold_shared_mlp(r.merge_down_layer))
+            self.xyz_up = _Mlp(_fold_shared_mlp(r.xyz_up_layer, _fresh))
+            self.merge_down = _Mlp(_fold_shared_mlp(r.merge_down_layer, _fresh))
             self.rcnn_sa = []
             for sa in r.SA_modules:
                 mlp = sa.mlps[0]
                 cin = mlp[0].conv.in_channels - 3
                 g = sa.groupers[0]
                 self.rcnn_sa.append((sa.npoint, getattr(g, "radius", None), getattr(g, "nsample", None),
-                                     _Mlp(_fold_shared_mlp(mlp), grouped_c=cin), cin))
+                                     _Mlp(_fold_shared_mlp(mlp, _fresh), grouped_c=cin), cin))
             self.rcnn_cls = _Mlp(_fold_head(r.cls_layer), pad128=PAD128)
             self.rcnn_reg = _Mlp(_fold_head(r.reg_layer), pad128=PAD128)
             # both heads read the same 512 features: their first layers side by side are ONE layer of twice the width (a launch less
@@ -429,6 +458,91 @@ class FastPointRCNN:
         if _state_version(self._state) != self._folded_at:
             raise RuntimeError("FastPointRCNN: the model's parameters changed after the engine was built "
                                "(load the checkpoint first, then construct the engine / PipelinedRunner)")
+
+    def weight_tensors(self):
+        """[(name, tensor)]: every device tensor of the engine that is computed from the model's weights -- the layers of each chain and
+        every derived form (split / packed / wide / wide_cat / narrow, the fused RPN tail's concatenations, the RCNN heads' joint first
+        layer, the narrow SA level's joint per-point part once a forward has made it).  reload_weights() rewrites exactly these."""
+        out = []
+        for k, (_, scales) in enumerate(self.sa):
+            for j, sc in enumerate(scales):
+                out += _mlp_tensors("sa[%d][%d]" % (k, j), sc[2])
+        for k, m in enumerate(self.fp):
+            out += _mlp_tensors("fp[%d]" % k, m)
+        out += _mlp_tensors("rpn_cls", self.rpn_cls) + _mlp_tensors("rpn_reg", self.rpn_reg)
+        for key in ("wcat", "bcat", "wc2", "bc2", "w1", "wcat_lin"):
+            if self.rpn_tail is not None:
+                out.append(("rpn_tail[%s]" % key, self.rpn_tail[key]))
+        if self.cfg.RCNN.ENABLED:
+            out += _mlp_tensors("xyz_up", self.xyz_up) + _mlp_tensors("merge_down", self.merge_down)
+            for k, lev in enumerate(self.rcnn_sa):
+                out += _mlp_tensors("rcnn_sa[%d]" % k, lev[3])
+            out += _mlp_tensors("rcnn_cls", self.rcnn_cls) + _mlp_tensors("rcnn_reg", self.rcnn_reg)
+            if self.rcnn_head1 is not None:
+                out += [("rcnn_head1.w", self.rcnn_head1[0]), ("rcnn_head1.b", self.rcnn_head1[1])]
+        return out + self._pcat_tensors()
+
+    def _pcat_pairs(self):
+        """the SA levels whose two narrow scales share one per-point product (`_sa_level`), once a forward has made its weights"""
+        return [scales for _, scales in self.sa if len(scales) == 2 and getattr(scales[0][2], "_pcat", None) is not None]
+
+    def _pcat_tensors(self):
+        return [("sa._pcat[%d]" % i, scales[0][2]._pcat[i]) for scales in self._pcat_pairs() for i in (0, 1)]
+
+    @torch.no_grad()
+    def reload_weights(self):
+        """The model's parameters or BatchNorm buffers were changed on purpose (load_state_dict of the next checkpoint): fold again and
+        write the result THROUGH the tensors this engine already owns -- same addresses, same shapes, so graphs captured over them
+        and cached row lists stay valid -- then accept the model's new version (check_weights() passes again).  The fold and every
+        derived form are made by the constructor's own code on the side and copied over: a reloaded engine holds, bit for bit, what
+        a fresh engine built from the same model holds.  Also brought up to date in place: the folded cache of pointnet2/fused_mlp.py
+        and, under PRCNN_SPLIT_BF16, the cached bf16 splits of the rewritten matrices.
+        A model whose structure or any weight shape is not the one the engine was built for raises ValueError naming the tensor,
+        before anything is written.  Nothing allocated here outlives the call; the copies run on the caller's current stream --
+        the caller orders them against other streams that run the engine (the runners' reload_weights() do)."""
+        model = self.model
+        assert not model.training, "FastPointRCNN is an inference engine: call model.eval() first"
+        now = _state_shapes(model)
+        if [n for n, _ in now] != [n for n, _ in self._shapes]:
+            odd = sorted(set(n for n, _ in now) ^ set(n for n, _ in self._shapes))
+            raise ValueError("FastPointRCNN.reload_weights: the model's parameters and buffers are not the ones the engine was built for "
+                             "(%s)" % ", ".join(odd[:4] or ["their order changed"]))
+        for (n, shape), (_, built) in zip(now, self._shapes):
+            if shape != built:
+                raise ValueError("FastPointRCNN.reload_weights: %s has shape %s, the engine was built for %s" % (n, shape, built))
+        folds = {}
+        try:
+            fresh = FastPointRCNN(model, self.cfg, _fresh=folds)
+        except (AssertionError, NotImplementedError, IndexError, RuntimeError) as e:
+            raise ValueError("FastPointRCNN.reload_weights: the model no longer folds into this engine (%s: %s)" % (type(e).__name__, e))
+        mine = [(n, t) for n, t in self.weight_tensors() if not n.startswith("sa._pcat")]
+        new = fresh.weight_tensors()
+        if len(mine) != len(new):
+            raise ValueError("FastPointRCNN.reload_weights: the model folds into %d weight tensors, the engine holds %d" % (len(new), len(mine)))
+        for (n, old), (n2, t) in zip(mine, new):
+            if n != n2 or old.shape != t.shape or old.dtype != t.dtype or old.device != t.device:
+                raise ValueError("FastPointRCNN.reload_weights: %s is %s %s on %s, the engine holds %s %s %s on %s"
+                                 % (n2, tuple(t.shape), t.dtype, t.device, n, tuple(old.shape), old.dtype, old.device))
+        cached = [m for m in model.modules() if "_prcnn_folded" in m.__dict__]
+        for m in cached:
+            if id(m) not in folds:
+                folds[id(m)] = fused_mlp.fold_fresh(m)
+            bad = fused_mlp.refold_mismatch(m, folds[id(m)])
+            if bad:
+                raise ValueError("FastPointRCNN.reload_weights: " + bad)
+        # ---- everything fits: write
+        for m in cached:
+            fused_mlp.refold_in_place(m, folds[id(m)])
+        for (_, old), (_, t) in zip(mine, new):
+            old.copy_(t)
+        for scales in self._pcat_pairs():               # made from the packed forms just rewritten: the expressions of `_sa_level`
+            wcat, bcat = scales[0][2]._pcat[0], scales[0][2]._pcat[1]
+            wcat.copy_(torch.cat([sc[2].packed[0][:, :64] for sc in scales], 1))
+            bcat.copy_(torch.cat([sc[2].packed[2][:64] for sc in scales]))
+        if SPLIT_BF16 and getattr(pu.pointnet2, "IS_HIP_EXTENSION", False) and has_entry(pu.pointnet2, "resplit_weights_bf16x3"):
+            pu.pointnet2.resplit_weights_bf16x3([t for _, t in mine])
+        self._state = _state_tensors(model)
+        self._folded_at = _state_version(self._state)
 
     # ------------------------------------------------------------------ geometry (xyz only)
     @torch.no_grad()

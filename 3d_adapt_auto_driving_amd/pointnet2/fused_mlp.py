@@ -54,6 +54,52 @@ def folded_layers(mlp):
     return cache[1]
 
 
+def fold_fresh(mlp):
+    """The fold of `folded_layers`, computed now from the module's current state and NOT cached: new tensors, the cache untouched."""
+    layers = []
+    for block in mlp.children():
+        fb = _fold_block(block)
+        if fb is None:
+            return None
+        layers.append(fb)
+    return layers
+
+
+def refold_in_place(mlp, layers=None):
+    """The cache of `folded_layers` brought up to the module's current state THROUGH ITS OWN TENSORS (an engine's derived weights may
+    alias them, a captured graph may hold their addresses).  ``layers``: a `fold_fresh(mlp)` the caller already has.  A module without
+    a cache is left without one.  Raises ValueError when the new fold does not have the cached one's shapes; check first with
+    `refold_mismatch` where nothing may be written on failure."""
+    cache = mlp.__dict__.get("_prcnn_folded")
+    if cache is None:
+        return
+    layers = fold_fresh(mlp) if layers is None else layers
+    bad = refold_mismatch(mlp, layers)
+    if bad:
+        raise ValueError(bad)
+    if cache[1] is not None:
+        for (w_old, b_old), (w, b) in zip(cache[1], layers):
+            w_old.copy_(w)
+            b_old.copy_(b)
+    mlp.__dict__["_prcnn_folded"] = (_signature(mlp), cache[1])
+
+
+def refold_mismatch(mlp, layers):
+    """-> a message naming the first folded tensor of ``layers`` whose shape differs from the cached fold's, or None"""
+    cache = mlp.__dict__.get("_prcnn_folded")
+    if cache is None:
+        return None
+    old = cache[1]
+    if (old is None) != (layers is None) or (old is not None and len(old) != len(layers)):
+        return "folded SharedMLP: the number of foldable layers changed"
+    for i, ((w_old, b_old), (w, b)) in enumerate(zip(old or (), layers or ())):
+        for name, t_old, t in (("weight", w_old, w), ("bias", b_old, b)):
+            if t_old.shape != t.shape or t_old.device != t.device:
+                return "folded SharedMLP layer %d %s: %s %s, the cached fold has %s %s" % (i, name, tuple(t.shape), t.device,
+                                                                                         tuple(t_old.shape), t_old.device)
+    return None
+
+
 def _signature(mlp):
     """Identity + version of EVERY parameter and buffer (BN running statistics included): a partial load or an in-place
     edit of any of them invalidates the folded weights."""

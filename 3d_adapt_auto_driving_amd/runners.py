@@ -203,6 +203,23 @@ class _StagedRunner:
                 return out
             out.append(det)
 
+    def _role_streams(self):
+        """every stream besides the caller's that runs the engine for this runner"""
+        return [self.tail] + list(self.sides)
+
+    def _reload_ordered(self):
+        """engine.reload_weights() on the caller's stream, behind everything the role streams still run with the old weights (geometry
+        chains of batches that were announced and never submitted: their early SA levels read the weights) and in front of
+        everything they run next: ONE event recorded behind the refresh, waited for by each of them."""
+        main = torch.cuda.current_stream(self.device)
+        for s in self._role_streams():
+            main.wait_stream(s)
+        self.engine.reload_weights()
+        ev = torch.cuda.Event()
+        ev.record(main)
+        for s in self._role_streams():
+            s.wait_event(ev)
+
 
 # a batch between its RPN stage and its RCNN stage (PipelinedRunner._inflight): its clouds, the RPN stage's state, the proposal layer's
 # results and the event behind them, the side stream that owns its geometry, that geometry, the RCNN geometry
@@ -387,6 +404,16 @@ class PipelinedRunner(_StagedRunner):
         self._retired = []
         return det
 
+    @torch.no_grad()
+    def reload_weights(self):
+        """The model's weights were changed on purpose (the next checkpoint of a sweep): FastPointRCNN.reload_weights(), ordered
+        against the side and tail streams.  RuntimeError while a batch is in flight -- flush() first.  Geometry chains of batches that
+        were announced and not submitted are dropped (their early SA levels were computed with the old weights)."""
+        if self._inflight is not None:
+            raise RuntimeError("PipelinedRunner.reload_weights: a batch is in flight; flush() first")
+        self._chains, self._pending = [], []
+        self._reload_ordered()
+
 
 USE_GRAPHS = os.environ.get("PRCNN_GRAPHS", "1") != "0"                   # hipGraph replay of the stages (GraphedRunner); 0: eager enqueue (PipelinedRunner)
 
@@ -492,6 +519,15 @@ class ModuleRunner:
 
     def _infer(self, cur):
         return infer_batch(self.model, self.cfg, cur)
+
+    def reload_weights(self):
+        """The model's weights were changed on purpose: the engine, where the runner has one, folds them again in place
+        (FastPointRCNN.reload_weights; the nn.Module graph reads the model itself).  RuntimeError while a batch is in flight --
+        flush() first.  Everything runs on the caller's stream: no ordering is needed."""
+        if self._pending is not None:
+            raise RuntimeError("%s.reload_weights: a batch is in flight; flush() first" % type(self).__name__)
+        if getattr(self, "engine", None) is not None:
+            self.engine.reload_weights()
 
 
 class EngineRunner(ModuleRunner):
@@ -875,6 +911,20 @@ class GraphedRunner(_StagedRunner):
             while self._inflights and not self._out:
                 self._finish_inflight()
         return self._out.popleft() if self._out else None
+
+    @torch.no_grad()
+    def reload_weights(self):
+        """The model's weights were changed on purpose (the next checkpoint of a sweep): FastPointRCNN.reload_weights() writes through
+        the addresses the captured graphs replay, ordered against the side and tail streams -- NO graph is captured again
+        (`captures` stays what it was).  RuntimeError while a batch is in flight or has not been handed back -- flush() until None
+        first.  Chains of batches that were announced and not submitted are dropped, as flush() drops them."""
+        if self._pending is not None or self._inflights or self._out:
+            raise RuntimeError("GraphedRunner.reload_weights: a batch is in flight; flush() until it returns None first")
+        self._assigned[:] = []
+        self._reload_ordered()
+
+    def _role_streams(self):
+        return [self.tail, self.feat] + list(self.sides)
 
 
 def _tensors(obj):
