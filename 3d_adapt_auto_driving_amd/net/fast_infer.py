@@ -18,7 +18,9 @@ Values differ from the module path only by f32 rounding of the GEMMs (different 
 summation orders); indices (FPS / ball query / three-NN / NMS keep) are produced by the same
 kernels.  Parity is tested against the reference fixtures with the 1e-4 box tolerance.
 """
+import contextlib
 import os
+import typing
 
 import torch
 
@@ -30,43 +32,31 @@ from .. import roipool3d_utils
 from .. import iou3d_utils
 
 
-USE_ROIPOOL_CANONICAL = True   # RCNN input assembly through roipool3d_canonical_kernel (False: torch-op sequence)
-USE_RCNN_POINT_MLP = True      # RCNN entrance chain through csrc/rcnn_point_mlp.hip (False: library GEMMs + concat; tests patch it)
-USE_XYZ_MLP = True      # coordinates-only SA scales through csrc/sa_xyz_mlp.hip (False: grouped GEMM chain)
-# SA levels over the DISTINCT grouped rows only (csrc/sa_packed.hip: the back-filled copies of a ball's first hit are
-# skipped, bit-identical results).  PRCNN_NO_PACK=1 is the A/B switch back to all nsample rows (csrc/sa_mlp_fused.hip).
+# The engine's switches: what each selects, and what its other setting is (A/B).  Measurements and history: DESIGN.md section 12.
+USE_ROIPOOL_CANONICAL = True   # RCNN input assembly through roipool3d_canonical_kernel; False: the torch-op sequence
+USE_RCNN_POINT_MLP = True      # RCNN entrance chain through csrc/rcnn_point_mlp.hip; False: library GEMMs + concat
+USE_XYZ_MLP = True             # coordinates-only SA scales through csrc/sa_xyz_mlp.hip; False: the grouped GEMM chain
+# SA levels over the DISTINCT grouped rows only (csrc/sa_packed.hip, same bits); PRCNN_NO_PACK=1: all nsample rows (csrc/sa_mlp_fused.hip)
 USE_PACKED = os.environ.get("PRCNN_NO_PACK") is None
-# RoI pooling fills a box holding fewer than 512 points by repeating them (roipool3d_kernel.cu:152-159): the per-point
-# RCNN entrance chain and SA1 run over the DISTINCT pooled points only (bit-identical results).  PRCNN_NO_POOL_DEDUP=1: A/B.
+# the per-point RCNN entrance chain and SA1 over the DISTINCT pooled points of a RoI only (same bits); PRCNN_NO_POOL_DEDUP=1: all 512 rows
 USE_POOL_DEDUP = os.environ.get("PRCNN_NO_POOL_DEDUP") is None
-# SA levels 1.. sample the previous level's picks in pick order: the answer is the prefix 0 .. m-1 unless an exact tie interferes, which
-# the library checks per cloud instead of running the dependent pick loop (csrc/fps_prefix.hip, prcnn_fps_new_xyz_nested; same results).
-# PRCNN_NESTED_FPS = the largest cloud (points) that is sampled that way; 0: the plain sampling call at every level.
+# SA levels 1.. sample the previous level's picks: the prefix check of csrc/fps_prefix.hip instead of the pick loop (same results) for
+# clouds of up to PRCNN_NESTED_FPS points; 0: the plain sampling call at every level
 NESTED_FPS_MAX_N = int(os.environ.get("PRCNN_NESTED_FPS", "4096"))
-USE_POINT_LAYER = os.environ.get("PRCNN_LIB_GEMM") is None     # per-point layers (FP modules, heads) on the own MFMA layer kernel
-# every per-point width zero-padded to a multiple of 128 (SA level outputs, FP inputs, narrow head outputs), so that NO layer
-# of the engine is left to a GEMM library: fixed summation order everywhere, reproduced bit for bit by the oracle
+USE_POINT_LAYER = os.environ.get("PRCNN_LIB_GEMM") is None     # per-point layers (FP modules, heads) on the own MFMA layer kernel; set: a GEMM library
+# every per-point width zero-padded to a multiple of 128, so that no layer of the engine is left to a GEMM library (fixed summation
+# order everywhere, reproduced bit for bit by the oracle)
 PAD128 = USE_PACKED and USE_POINT_LAYER
-# the finest FP module and both RPN heads in one kernel (csrc/rpn_tail.hip); PRCNN_NO_RPN_TAIL=1: layer by layer (A/B, same bits)
+# the finest FP module and both RPN heads in one kernel (csrc/rpn_tail.hip); PRCNN_NO_RPN_TAIL=1: layer by layer (same bits)
 USE_RPN_TAIL = os.environ.get("PRCNN_NO_RPN_TAIL") is None
-# the scales of a wide MSG level (RPN SA3 / SA4) stage by stage, side by side in one launch per stage
-USE_SCALE_BATCH = True      # (a module constant since round 6; tests patch it)
-# layers 1-3 + pool of a wide scale in one kernel (csrc/sa_wide.hip); False: gather / layer / layer+pool launches
-USE_SA_NARROW = True        # RPN SA2's scales without their zero padding (csrc/sa_packed.hip), their per-point parts in one product
-USE_WIDE_FUSED = True       # (a module constant since round 6; tests/test_gpu_shadow.py patches it for the layer-by-layer variant)
+USE_SCALE_BATCH = True      # the scales of an MSG level side by side, one launch per stage; False: scale by scale (same bits)
+USE_SA_NARROW = True        # RPN SA2's scales without their zero padding, their per-point parts in one product; False: two padded products
+USE_WIDE_FUSED = True       # layers 1-3 + pool of a wide scale in one kernel (csrc/sa_wide.hip, sa_wide3.hip); False: gather / layer / layer+pool launches
 # leading SA levels of a coordinates-only backbone computed with the geometry (side stream); 0: none
 EARLY_LEVELS = int(os.environ.get("PRCNN_EARLY_LEVELS", "4"))
-EARLY_FP = int(os.environ.get("PRCNN_EARLY_FP", "2"))                 # ... plus this many of the coarsest FP modules, over the 32 clouds of a group in one launch each (round 3: 1 -- the geometry chains were the longer side then; round 4: 3, see EARLY_TAIL; round 5: 2 -- with the RCNN's padded tiles gone the feature stream has room again and the geometry chains bind: profiles/sensitivity_probe.py, 7860 -> 7980 / LiDAR-shaped 5500 -> 5570 at K = 100)
-# ... and the finest FP module + both RPN heads as well (round 4 experiment, needs EARLY_FP >= number of FP modules - 1): the RPN backbone has
-# no input features, so the WHOLE RPN stage is a function of xyz and the weights.  With the geometry chains twice as fast as in round 3 the
-# feature stream binds (1.10 ms of kernels per step against 0.6 on each geometry stream): EARLY_FP = 3 (all FP modules but the finest over
-# the 32 clouds of a group) buys +4.6 % at K = 100 (6382 against 6103 scenes/s; K = 20: level).  The fused tail on top of it -- a 256-workgroup
-# MFMA kernel of 0.7 ms per group on a geometry stream -- costs it again: 6042 at K = 100, 5158 against 5314 at K = 20.  Off.
-# (round 6: the switch PRCNN_EARLY_TAIL and its branch are gone.)
-# feature-propagation modules: the first layer is linear in front of its ReLU and the interpolation is a weighted sum, so the
-# interpolated columns of the layer are applied at the COARSE level (a quarter of the rows) and the product is interpolated in the
-# epilogue of the layer over the skip features (prcnn_packed_layer_interp).  Another association of the same sums than the
-# reference's (~1e-7 relative); PRCNN_NO_FP_LINEAR=1: interpolate, concatenate, then the layer, as the reference does (A/B).
+EARLY_FP = int(os.environ.get("PRCNN_EARLY_FP", "2"))          # ... plus this many of the coarsest FP modules, over all clouds of a group in one launch each
+# FP modules: the interpolated columns of the first layer applied at the COARSE level, the product interpolated in the layer's epilogue
+# (another association of the same sums, ~1e-7 relative); PRCNN_NO_FP_LINEAR=1: interpolate, concatenate, then the layer (the reference's order)
 USE_FP_LINEAR = os.environ.get("PRCNN_NO_FP_LINEAR") is None
 
 
@@ -85,18 +75,11 @@ class ZeroArena:
         self.buf = torch.zeros((total,), dtype=torch.float32, device=device) if total else None
 
     def take(self, shape, dtype=torch.float32):
-        n = 1
-        for d in shape:
-            n *= int(d)
+        n = torch.Size(shape).numel()
         n4 = (n + 3) // 4 * 4                                        # 16-byte slices
-        if self.buf is None:
-            self.used += n4
-            part = torch.zeros(tuple(shape), dtype=dtype, device=self.device)
-            self.parts.append(part)
-            return part
-        if self.used + n4 > self.buf.numel():
-            # the chain asks for more than its dry run did (an engine switch changed in between): a fill of its own, and a larger
-            # arena from the next pass on
+        if self.buf is None or self.used + n4 > self.buf.numel():
+            # the dry run, or the chain asks for more than its dry run did (an engine switch changed in between): a fill of its own,
+            # and a larger arena from the next pass on
             self.used += n4
             part = torch.zeros(tuple(shape), dtype=dtype, device=self.device)
             self.parts.append(part)
@@ -199,6 +182,11 @@ def point_layer(a, wt, bias, relu, n_out=None):
     return y if n_out == N else y[:, :n_out].contiguous()
 
 
+# the weights of a three-layer SA scale as the packed kernels read them (`_Mlp.packed`: every width padded to 128; `_Mlp.wide`: to 128s):
+# layer 1 split into its feature rows wf and its coordinate rows wx, then layers 2 and 3
+PackedWeights = typing.NamedTuple("PackedWeights", [(name, torch.Tensor) for name in ("wf", "wx", "b1", "w2", "b2", "w3", "b3")])
+
+
 class _Mlp:
     """Folded weights of one SharedMLP / Conv1d chain in (K, Cout) form."""
 
@@ -209,6 +197,7 @@ class _Mlp:
         then carry zero columns up to the padded K, ``n_out`` is the real width of the last layer."""
         self.layers = []
         self.n_out = layers[-1][0].shape[0]
+        self.split = self.packed = self.packed_widths = self.wide = self.wide_cat = self.narrow = None
         if pad128 and grouped_c is None:
             for i, (w, b, relu) in enumerate(layers):
                 np_ = _round128(w.shape[0])
@@ -224,10 +213,8 @@ class _Mlp:
                 else:
                     wt = _pad2(w.t(), _round128(w.shape[1]), np_)
                 self.layers.append((wt.contiguous(), _pad1(b, np_), relu))
-            self.split = self.packed = self.wide = self.wide_cat = None
             self.padded = not pad_out          # pad_out: the last layer's output keeps its zero columns (feeds another chain)
             # a 1-wide (<= 4) last layer without ReLU is a GEMV per output: its own small kernel instead of a 128-wide MFMA tile
-            self.narrow = None
             w, b, relu = layers[-1]
             if self.padded and w.shape[0] <= 4 and not relu:
                 self.narrow = (_pad2(w.t(), _round128(w.shape[1]), w.shape[0]), b.clone())
@@ -249,35 +236,41 @@ class _Mlp:
             self.layers.append((wt.contiguous(), b.clone(), relu))
 
         # split form of the first layer for the "linear before ReLU" shortcut (see _sa_scale)
-        self.split = None
         if grouped_c is not None and grouped_c >= 32 and grouped_c % 4 == 0 and self.layers[0][2]:
             wt, b, _ = self.layers[0]
             c4 = _round4(grouped_c)
             self.split = (wt[:grouped_c].contiguous(), wt[c4:c4 + 3].contiguous(), b)   # (C,Cout), (3,Cout), (Cout)
         # 128-wide (zero-padded) form for the fused MFMA kernels: c1, c2 <= 128, c3 in {128, 256}.  Zero columns give
         # relu(0) = 0 activations that meet zero weight rows in the next layer: the padded chain adds exact zeros.
-        self.packed = self.wide = self.wide_cat = None
         if self.split is not None and len(self.layers) == 3 and all(l[2] for l in self.layers):
             wf, wx, b1 = self.split
             (w2, b2, _), (w3, b3, _) = self.layers[1], self.layers[2]
             c1, c2, c3 = wf.shape[1], w2.shape[1], w3.shape[1]
             kin = _round128(wf.shape[0]) if PAD128 else wf.shape[0]      # the feature tensor arrives padded to 128s
             if c1 <= 128 and c2 <= 128 and c3 in (128, 256) and w2.shape[0] == c1 and w3.shape[0] == c2:
-                self.packed = (_pad2(wf, kin, 128), _pad2(wx, 3, 128), _pad1(b1, 128),
-                               _pad2(w2, 128, 128), _pad1(b2, 128), _pad2(w3, 128, c3), b3)
+                self.packed = PackedWeights(_pad2(wf, kin, 128), _pad2(wx, 3, 128), _pad1(b1, 128),
+                                            _pad2(w2, 128, 128), _pad1(b2, 128), _pad2(w3, 128, c3), b3)
                 self.packed_widths = (c1, c2)                          # what the padding hides (the batched kernel skips it)
             elif c3 % 128 == 0 and w2.shape[0] == c1 and w3.shape[0] == c2:
                 # wider levels: layer by layer over the packed rows (csrc/packed_layer.hip), widths padded to 128s
                 c1p, c2p = _round128(c1), _round128(c2)
-                self.wide = (_pad2(wf, kin, c1p), _pad2(wx, 3, c1p), _pad1(b1, c1p),
-                             _pad2(w2, c1p, c2p), _pad1(b2, c2p), _pad2(w3, c2p, c3), b3)
+                self.wide = PackedWeights(_pad2(wf, kin, c1p), _pad2(wx, 3, c1p), _pad1(b1, c1p),
+                                          _pad2(w2, c1p, c2p), _pad1(b2, c2p), _pad2(w3, c2p, c3), b3)
                 # w1 | w2 | w3 in one allocation: csrc/sa_wide3.hip streams all three through one buffer resource
-                self.wide_cat = torch.cat([t.reshape(-1) for t in (self.wide[0], self.wide[3], self.wide[5])]).contiguous()
+                self.wide_cat = torch.cat([t.reshape(-1) for t in (self.wide.wf, self.wide.w2, self.wide.w3)]).contiguous()
+
+    @property
+    def out_width(self):                   # columns of the last layer's output as the engine stores it
+        return self.layers[-1][0].shape[1]
+
+    @property
+    def on_packed(self):                   # this chain runs on the packed-row kernels (an RCNN level; an RPN scale: `Scale.on_packed`)
+        return self.packed is not None or self.wide is not None
 
     def __call__(self, a, start=0):
         last = len(self.layers) - 1
         for i, (wt, b, relu) in enumerate(self.layers[start:], start):
-            if USE_POINT_LAYER and i == last and getattr(self, "narrow", None) is not None and a.stride(1) == 1:
+            if USE_POINT_LAYER and i == last and self.narrow is not None and a.stride(1) == 1:
                 out = torch.empty((a.shape[0], self.n_out), dtype=torch.float32, device=a.device)
                 a = pu.pointnet2.rows_dot_wrapper(a, self.narrow[0], self.narrow[1], out)
             elif USE_POINT_LAYER:
@@ -339,12 +332,65 @@ def _mlp_tensors(name, mlp):
     for i, (wt, b, _) in enumerate(mlp.layers):
         out += [("%s.layers[%d].w" % (name, i), wt), ("%s.layers[%d].b" % (name, i), b)]
     for form in ("split", "packed", "wide", "narrow"):
-        ts = getattr(mlp, form, None)
-        for i, t in enumerate(ts or ()):
+        for i, t in enumerate(getattr(mlp, form) or ()):
             out.append(("%s.%s[%d]" % (name, form, i), t))
-    if getattr(mlp, "wide_cat", None) is not None:
+    if mlp.wide_cat is not None:
         out.append((name + ".wide_cat", mlp.wide_cat))
     return out
+
+
+class Scale(typing.NamedTuple):
+    """one (radius, nsample) scale of an RPN SA level; cin: feature channels of its grouped rows (0: coordinates only)"""
+    radius: float
+    nsample: int
+    mlp: _Mlp
+    cin: int
+
+    @property
+    def on_packed(self):                   # this scale runs on the packed-row kernels: packed / wide / the coordinates-only kernel over row lists
+        return self.mlp.on_packed or self.cin == 0
+
+
+class SaLevel(typing.NamedTuple):
+    """one MSG level of the RPN backbone.  pcat: (weights, bias) of the per-point parts of its two narrow scales side by side (RPN SA2,
+    `FastPointRCNN._sa_level`), None for a level whose weights do not have that shape"""
+    npoint: int
+    scales: list
+    pcat: typing.Optional[tuple]
+
+    @property
+    def on_packed(self):
+        return all(sc.on_packed for sc in self.scales)
+
+    @property
+    def columns(self):                     # the first output column of every scale
+        return [sum(sc.mlp.out_width for sc in self.scales[:j]) for j in range(len(self.scales))]
+
+    @property
+    def padded_width(self):                # columns of the level's output tensor: what the next level and the FP skip input read (128s under PAD128)
+        width = sum(sc.mlp.out_width for sc in self.scales)
+        return _round128(width) if PAD128 else width
+
+
+class RcnnLevel(typing.NamedTuple):
+    """one SA level of the RCNN; npoint, radius, nsample are None for GroupAll"""
+    npoint: typing.Optional[int]
+    radius: typing.Optional[float]
+    nsample: typing.Optional[int]
+    mlp: _Mlp
+    cin: int
+
+
+def _narrow_pair_weights(scales):
+    """-> (weights (K, 128), bias (128,)) of the per-point parts of a level's two scales side by side when both run on the packed kernel
+    with a first layer of 64 and a second of 64 or 96 columns under their padding, a 128-wide third layer and the same per-point input
+    width (a multiple of 128): RPN SA2.  A column's chain does not depend on its neighbours: same bits as two padded products."""
+    pk = [sc.mlp.packed for sc in scales]
+    if not (len(scales) == 2 and all(p is not None and p.w3.shape[1] == 128 for p in pk)
+            and all(c1 == 64 and c2 in (64, 96) for c1, c2 in (sc.mlp.packed_widths for sc in scales))
+            and pk[0].wf.shape[0] == pk[1].wf.shape[0] and pk[0].wf.shape[0] % 128 == 0):
+        return None
+    return (torch.cat([p.wf[:, :64] for p in pk], 1).contiguous(), torch.cat([p.b1[:64] for p in pk]).contiguous())
 
 
 class FastPointRCNN:
@@ -368,13 +414,11 @@ class FastPointRCNN:
         bb = rpn.backbone_net
         self.sa = []
         for sa in bb.SA_modules:
-            scales = []
-            for grouper, mlp in zip(sa.groupers, sa.mlps):
-                cin = mlp[0].conv.in_channels - 3
-                scales.append((grouper.radius, grouper.nsample, _Mlp(_fold_shared_mlp(mlp, _fresh), grouped_c=cin), cin))
-            self.sa.append((sa.npoint, scales))
+            cins = [mlp[0].conv.in_channels - 3 for mlp in sa.mlps]
+            scales = [Scale(g.radius, g.nsample, _Mlp(_fold_shared_mlp(mlp, _fresh), grouped_c=cin), cin) for g, mlp, cin in zip(sa.groupers, sa.mlps, cins)]
+            self.sa.append(SaLevel(sa.npoint, scales, _narrow_pair_weights(scales)))
         # FP module k consumes [features interpolated from level k+1 | skip features of level k]
-        sa_w = [sum(sc[2].n_out for sc in scales) for _, scales in self.sa]
+        sa_w = [sum(sc.mlp.n_out for sc in level.scales) for level in self.sa]
         folded = [_fold_shared_mlp(fp.mlp, _fresh) for fp in bb.FP_modules]
         self.fp = []
         for k, lay in enumerate(folded):
@@ -384,17 +428,21 @@ class FastPointRCNN:
         self.rpn_cls = _Mlp(_fold_head(rpn.rpn_cls_layer), pad128=PAD128)
         self.rpn_reg = _Mlp(_fold_head(rpn.rpn_reg_layer), pad128=PAD128)
         self.rpn_tail = self._fold_rpn_tail() if (USE_RPN_TAIL and PAD128 and USE_POINT_LAYER) else None
+        # state that is not a function of the weights: the zero bias of the FP modules' coarse products, the constants of the GroupAll
+        # level by shape (one entry per shape, never replaced: a captured graph may hold these addresses), two verdicts made on first use
+        self._zero_bias = self.rpn_cls.layers[0][0].new_zeros((max([1024] + [m.layers[0][0].shape[1] for m in self.fp]),))
+        self._groupall = {}
+        self._pm_ok = self._is_covered = None
         if cfg.RCNN.ENABLED:
             r = model.rcnn_net
             self.xyz_up = _Mlp(_fold_shared_mlp(r.xyz_up_layer, _fresh))
             self.merge_down = _Mlp(_fold_shared_mlp(r.merge_down_layer, _fresh))
             self.rcnn_sa = []
             for sa in r.SA_modules:
-                mlp = sa.mlps[0]
+                mlp, g = sa.mlps[0], sa.groupers[0]
                 cin = mlp[0].conv.in_channels - 3
-                g = sa.groupers[0]
-                self.rcnn_sa.append((sa.npoint, getattr(g, "radius", None), getattr(g, "nsample", None),
-                                     _Mlp(_fold_shared_mlp(mlp, _fresh), grouped_c=cin), cin))
+                self.rcnn_sa.append(RcnnLevel(sa.npoint, getattr(g, "radius", None), getattr(g, "nsample", None),
+                                              _Mlp(_fold_shared_mlp(mlp, _fresh), grouped_c=cin), cin))
             self.rcnn_cls = _Mlp(_fold_head(r.cls_layer), pad128=PAD128)
             self.rcnn_reg = _Mlp(_fold_head(r.reg_layer), pad128=PAD128)
             # both heads read the same 512 features: their first layers side by side are ONE layer of twice the width (a launch less
@@ -409,30 +457,23 @@ class FastPointRCNN:
         """True when every MLP of this network runs on a kernel of this build with the product switches at their defaults:
         RPN SA scales on the packed / wide / coordinates-only kernels, the fused RPN tail, the RCNN entrance chain and SA levels."""
         try:
-            ok = bool(PAD128 and self.rpn_tail is not None)
-            for _, scales in self.sa:
-                ok = ok and all(sc[2].packed is not None or sc[2].wide is not None or sc[3] == 0 for sc in scales)
+            ok = bool(PAD128 and self.rpn_tail is not None) and all(level.on_packed for level in self.sa)
             if self.cfg.RCNN.ENABLED:
-                ok = ok and self._point_mlp_ok() and all(m[3].packed is not None or m[3].wide is not None for m in self.rcnn_sa)
+                ok = ok and self._point_mlp_ok() and all(level.mlp.on_packed for level in self.rcnn_sa)
             return ok
         except Exception:
             return False
 
+    @contextlib.contextmanager
     def _strictly(self):
-        """context manager: while it is open, a layer of a covered network that falls to a GEMM library raises (gemm_bias_act)"""
-        import contextlib
-
-        @contextlib.contextmanager
-        def cm():
-            if getattr(self, "_is_covered", None) is None:
-                self._is_covered = self._covered()
-            prev = _STRICT[0]
-            _STRICT[0] = bool(self._is_covered)
-            try:
-                yield
-            finally:
-                _STRICT[0] = prev
-        return cm()
+        """while it is open, a layer of a covered network that falls to a GEMM library raises (gemm_bias_act)"""
+        if self._is_covered is None:
+            self._is_covered = self._covered()
+        prev, _STRICT[0] = _STRICT[0], bool(self._is_covered)
+        try:
+            yield
+        finally:
+            _STRICT[0] = prev
 
     def _fold_rpn_tail(self):
         """Weights of csrc/rpn_tail.hip (finest FP module + both RPN heads in one kernel) when the network has the shape that
@@ -462,32 +503,23 @@ class FastPointRCNN:
     def weight_tensors(self):
         """[(name, tensor)]: every device tensor of the engine that is computed from the model's weights -- the layers of each chain and
         every derived form (split / packed / wide / wide_cat / narrow, the fused RPN tail's concatenations, the RCNN heads' joint first
-        layer, the narrow SA level's joint per-point part once a forward has made it).  reload_weights() rewrites exactly these."""
+        layer, the narrow SA level's joint per-point part).  reload_weights() rewrites exactly these."""
         out = []
-        for k, (_, scales) in enumerate(self.sa):
-            for j, sc in enumerate(scales):
-                out += _mlp_tensors("sa[%d][%d]" % (k, j), sc[2])
+        for k, level in enumerate(self.sa):
+            for j, sc in enumerate(level.scales):
+                out += _mlp_tensors("sa[%d][%d]" % (k, j), sc.mlp)
         for k, m in enumerate(self.fp):
             out += _mlp_tensors("fp[%d]" % k, m)
         out += _mlp_tensors("rpn_cls", self.rpn_cls) + _mlp_tensors("rpn_reg", self.rpn_reg)
-        for key in ("wcat", "bcat", "wc2", "bc2", "w1", "wcat_lin"):
-            if self.rpn_tail is not None:
-                out.append(("rpn_tail[%s]" % key, self.rpn_tail[key]))
+        out += [("rpn_tail[%s]" % key, self.rpn_tail[key]) for key in ("wcat", "bcat", "wc2", "bc2", "w1", "wcat_lin") if self.rpn_tail is not None]
         if self.cfg.RCNN.ENABLED:
             out += _mlp_tensors("xyz_up", self.xyz_up) + _mlp_tensors("merge_down", self.merge_down)
-            for k, lev in enumerate(self.rcnn_sa):
-                out += _mlp_tensors("rcnn_sa[%d]" % k, lev[3])
+            for k, level in enumerate(self.rcnn_sa):
+                out += _mlp_tensors("rcnn_sa[%d]" % k, level.mlp)
             out += _mlp_tensors("rcnn_cls", self.rcnn_cls) + _mlp_tensors("rcnn_reg", self.rcnn_reg)
             if self.rcnn_head1 is not None:
-                out += [("rcnn_head1.w", self.rcnn_head1[0]), ("rcnn_head1.b", self.rcnn_head1[1])]
-        return out + self._pcat_tensors()
-
-    def _pcat_pairs(self):
-        """the SA levels whose two narrow scales share one per-point product (`_sa_level`), once a forward has made its weights"""
-        return [scales for _, scales in self.sa if len(scales) == 2 and getattr(scales[0][2], "_pcat", None) is not None]
-
-    def _pcat_tensors(self):
-        return [("sa._pcat[%d]" % i, scales[0][2]._pcat[i]) for scales in self._pcat_pairs() for i in (0, 1)]
+                out += list(zip(("rcnn_head1.w", "rcnn_head1.b"), self.rcnn_head1))
+        return out + [("sa._pcat[%d]" % i, t) for level in self.sa if level.pcat is not None for i, t in enumerate(level.pcat)]
 
     @torch.no_grad()
     def reload_weights(self):
@@ -515,8 +547,7 @@ class FastPointRCNN:
             fresh = FastPointRCNN(model, self.cfg, _fresh=folds)
         except (AssertionError, NotImplementedError, IndexError, RuntimeError) as e:
             raise ValueError("FastPointRCNN.reload_weights: the model no longer folds into this engine (%s: %s)" % (type(e).__name__, e))
-        mine = [(n, t) for n, t in self.weight_tensors() if not n.startswith("sa._pcat")]
-        new = fresh.weight_tensors()
+        mine, new = self.weight_tensors(), fresh.weight_tensors()
         if len(mine) != len(new):
             raise ValueError("FastPointRCNN.reload_weights: the model folds into %d weight tensors, the engine holds %d" % (len(new), len(mine)))
         for (n, old), (n2, t) in zip(mine, new):
@@ -535,10 +566,6 @@ class FastPointRCNN:
             fused_mlp.refold_in_place(m, folds[id(m)])
         for (_, old), (_, t) in zip(mine, new):
             old.copy_(t)
-        for scales in self._pcat_pairs():               # made from the packed forms just rewritten: the expressions of `_sa_level`
-            wcat, bcat = scales[0][2]._pcat[0], scales[0][2]._pcat[1]
-            wcat.copy_(torch.cat([sc[2].packed[0][:, :64] for sc in scales], 1))
-            bcat.copy_(torch.cat([sc[2].packed[2][:64] for sc in scales]))
         if SPLIT_BF16 and getattr(pu.pointnet2, "IS_HIP_EXTENSION", False) and has_entry(pu.pointnet2, "resplit_weights_bf16x3"):
             pu.pointnet2.resplit_weights_bf16x3([t for _, t in mine])
         self._state = _state_tensors(model)
@@ -576,34 +603,40 @@ class FastPointRCNN:
             interp.append((idx, weight))
         return {"l_xyz": l_xyz, "sa": state["sa"], "fp": interp}
 
+    @staticmethod
+    def _sample(cur_xyz, npoint, nested, roi_clouds=False):
+        """furthest-point sampling + the centres' coordinates -> (sel, new_xyz): one launch where the backend offers it (roi_clouds, the
+        RCNN's RoI clouds: up to 1024 points), else the sampling call and a gather.  nested: cur_xyz is an earlier sampling's centres"""
+        ext = pu.pointnet2
+        n = cur_xyz.shape[1]
+        fits = n <= 1024 if roi_clouds else (has_entry(ext, "fps_new_xyz_supported") and ext.fps_new_xyz_supported(n, npoint))
+        if has_entry(ext, "fps_new_xyz_wrapper") and fits:
+            # a nested level samples centres that are in pick order: prcnn_fps_new_xyz_nested (same outputs, the pick loop only for the clouds
+            # that fail the prefix check).  NOTE the form of the call: ext.PrefixExpected(npoint) IS an int, and
+            # fps_new_xyz_wrapper(cur, PrefixExpected(m)) is exactly fps_new_xyz_nested_wrapper(cur, m) (dropin/pointnet2_cuda.py) -- the hint
+            # rides on the count so that every level's sampling stays ONE kind of call for the proxies that count and shadow-check them
+            # (tests/test_gpu_shadow.py: four fps_new_xyz_wrapper calls per step, each compared with the CPU stand-in).  int(m) drops the
+            # hint: never convert it on the way (tests/test_gpu_fps_nested.py::test_engine_takes_the_nested_entry counts the C entries).
+            nested = nested and n <= NESTED_FPS_MAX_N and has_entry(ext, "fps_new_xyz_nested_wrapper") and ext.fps_new_xyz_nested_supported(n, npoint)
+            return ext.fps_new_xyz_wrapper(cur_xyz, ext.PrefixExpected(npoint) if nested else npoint)
+        sel = pu.furthest_point_sample(cur_xyz, npoint)
+        return sel, torch.gather(cur_xyz, 1, sel.long().unsqueeze(-1).expand(-1, -1, 3)).contiguous()
+
     def _geometry_level(self, state, k):
-        npoint, scales = self.sa[k]
+        npoint, scales, _ = self.sa[k]
         cur = state["l_xyz"][-1]
         ext = pu.pointnet2
-        if has_entry(ext, "fps_new_xyz_wrapper") and has_entry(ext, "fps_new_xyz_supported") and ext.fps_new_xyz_supported(cur.shape[1], npoint):
-            # sampling + the centres' coordinates, one launch (round 4: every level); level k >= 1 samples level k-1's centres, which
-            # are in pick order: prcnn_fps_new_xyz_nested (same outputs, the pick loop only for the clouds that fail the prefix check).
-            # NOTE the form of the call: ext.PrefixExpected(npoint) IS an int, and fps_new_xyz_wrapper(cur, PrefixExpected(m)) is
-            # exactly fps_new_xyz_nested_wrapper(cur, m) (dropin/pointnet2_cuda.py) -- the hint rides on the count so that every level's
-            # sampling stays ONE kind of call for the proxies that count and shadow-check them (tests/test_gpu_shadow.py: four
-            # fps_new_xyz_wrapper calls per step, each compared with the CPU stand-in).  int(m) drops the hint: never convert it on
-            # the way (tests/test_gpu_fps_nested.py::test_engine_takes_the_nested_entry counts the C entries the engine reaches).
-            nested = (k >= 1 and cur.shape[1] <= NESTED_FPS_MAX_N and has_entry(ext, "fps_new_xyz_nested_wrapper")
-                      and ext.fps_new_xyz_nested_supported(cur.shape[1], npoint))
-            sel, new_xyz = ext.fps_new_xyz_wrapper(cur, ext.PrefixExpected(npoint) if nested else npoint)
-        else:
-            sel = pu.furthest_point_sample(cur, npoint)
-            new_xyz = torch.gather(cur, 1, sel.long().unsqueeze(-1).expand(-1, -1, 3)).contiguous()
+        sel, new_xyz = self._sample(cur, npoint, k >= 1)
         if has_entry(ext, "ball_query_full_wrapper"):
             # every slot written by the kernel: no zero fill in front of each query
             B_, N_ = cur.shape[0], cur.shape[1]
             idxs = []
-            for radius, ns, _, _ in scales:
-                ix = torch.empty((B_, npoint, ns), dtype=torch.int32, device=cur.device)
-                ext.ball_query_full_wrapper(B_, N_, npoint, radius, ns, new_xyz, cur, ix)
+            for sc in scales:
+                ix = torch.empty((B_, npoint, sc.nsample), dtype=torch.int32, device=cur.device)
+                ext.ball_query_full_wrapper(B_, N_, npoint, sc.radius, sc.nsample, new_xyz, cur, ix)
                 idxs.append(ix)
         else:
-            idxs = [pu.ball_query(radius, ns, cur, new_xyz) for radius, ns, _, _ in scales]
+            idxs = [pu.ball_query(sc.radius, sc.nsample, cur, new_xyz) for sc in scales]
         lev = {"sel": sel, "new_xyz": new_xyz, "idx": idxs, "pack": [None] * len(scales)}
         if not state.get("defer_packs"):
             self._pack_level(k, cur, lev)
@@ -615,9 +648,11 @@ class FastPointRCNN:
         arena: a ZeroArena the headers come from (zero already: no memset per list)"""
         # (positional: test proxies around the extension module forward *args only)
         hdr = (lambda: (None, None, None, arena.take((4,), torch.int32))) if (arena is not None and getattr(pu.pointnet2, "IS_HIP_EXTENSION", False)) else (lambda: ())
-        lev["pack"] = [pu.pointnet2.ball_pack_wrapper(ix, cur, lev["new_xyz"], *hdr())
-                       if (USE_PACKED and (sc[2].packed is not None or sc[2].wide is not None or sc[3] == 0)) else None
-                       for ix, sc in zip(lev["idx"], self.sa[k][1])]
+        lev["pack"] = self._row_lists(k, lev, lambda ix: pu.pointnet2.ball_pack_wrapper(ix, cur, lev["new_xyz"], *hdr()))
+
+    def _row_lists(self, k, lev, make):
+        """make(index tensor) for every scale of level k that runs on the packed kernels, None for the others"""
+        return [make(ix) if (USE_PACKED and sc.on_packed) else None for ix, sc in zip(lev["idx"], self.sa[k].scales)]
 
     @torch.no_grad()
     def geometry_group(self, xyz_list, on_batch_done=None, group_sa=True):
@@ -662,9 +697,8 @@ class FastPointRCNN:
                 n_early += 1
         arena.done()
         if same and n_early < len(geo["sa"]):
-            gpacks = [[ext.ball_pack_groups_wrapper(ix, geo["l_xyz"][k], lev["new_xyz"], sizes[0])
-                       if (USE_PACKED and (sc[2].packed is not None or sc[2].wide is not None or sc[3] == 0)) else None
-                       for ix, sc in zip(lev["idx"], self.sa[k][1])] for k, lev in enumerate(geo["sa"])]
+            gpacks = [self._row_lists(k, lev, lambda ix: ext.ball_pack_groups_wrapper(ix, geo["l_xyz"][k], lev["new_xyz"], sizes[0]))
+                      for k, lev in enumerate(geo["sa"])]
         out, lo = [], 0
         for bi, b in enumerate(sizes):
             hi = lo + b
@@ -711,22 +745,18 @@ class FastPointRCNN:
         and the model's weights only -- so does the whole backbone -- and are computed WITH the geometry, on the geometry's stream
         (the pipelined runner: a side stream that has slack, off the feature stream's critical path).  Stored as
         geo["sa"][k]["out"]; `_backbone` starts behind them.  Same kernels, same arguments as in `_backbone`: same bits."""
-        if not (USE_PACKED and USE_XYZ_MLP and self.sa and self.sa[0][1] and
-                all(sc[3] == 0 for sc in self.sa[0][1])):
+        if not (USE_PACKED and USE_XYZ_MLP and self.sa and self.sa[0].scales and all(sc.cin == 0 for sc in self.sa[0].scales)):
             return
         l_xyz, prev = geo["l_xyz"], None
         B = l_xyz[0].shape[0]
         for k in range(min(EARLY_LEVELS, len(self.sa))):
-            npoint, scales = self.sa[k]
-            lev = geo["sa"][k]
-            packs = lev.get("pack") or [None] * len(scales)
-            pre = bool(all(sc[2].packed is not None or sc[2].wide is not None or sc[3] == 0 for sc in scales))
-            if not pre or any(pk is None for pk in packs):
+            level, lev = self.sa[k], geo["sa"][k]
+            packs = lev.get("pack") or [None] * len(level.scales)
+            if not level.on_packed or any(pk is None for pk in packs):
                 return                                          # a level off the packed kernels: it (and what follows) stays in _backbone
-            width = sum(sc[2].layers[-1][0].shape[1] for sc in scales)
-            oshape = (B, npoint, _round128(width) if PAD128 else width)
+            oshape = (B, level.npoint, level.padded_width)
             out = arena.take(oshape) if arena is not None else torch.zeros(oshape, dtype=torch.float32, device=l_xyz[0].device)
-            self._sa_level(scales, lev, l_xyz[k], prev, out, True)
+            self._sa_level(level, lev, l_xyz[k], prev, out, True)
             lev["out"] = prev = out
         # ... and, with every SA level done, the coarsest EARLY_FP feature-propagation modules (a few thousand rows each: launches
         # that leave most of the chip idle on the feature stream, and depend on xyz only like everything else here)
@@ -815,7 +845,7 @@ class FastPointRCNN:
         ext.maxpool_pm_wrapper(y, ns, out, out_col)
 
     @staticmethod
-    def _sa_level_wide(xyz, new_xyz, feats, scales, idxs, packs, out, zeroed):
+    def _sa_level_wide(xyz, new_xyz, feats, level, idxs, packs, out, zeroed):
         """All scales of one MSG level whose layers are wider than the register-resident fused kernels take (RPN SA3 / SA4),
         STAGE BY STAGE with the scales side by side in one launch per stage: per-point parts, gather + affine over the packed
         rows, layer 2, layer 3 + segmented max.  On sparse levels every one of these launches is latency-bound (a handful of
@@ -824,66 +854,53 @@ class FastPointRCNN:
         B, N, _ = xyz.shape
         M = new_xyz.shape[1]
         dev = xyz.device
-        wides = [sc[2].wide for sc in scales]                  # (wf, wx, b1, w2, b2, w3, b3)
+        wides = [sc.mlp.wide for sc in level.scales]
         flat = feats.view(B * N, feats.shape[2])
-        Ps = [torch.empty((B * N, w[0].shape[1]), dtype=torch.float32, device=dev) for w in wides]
-        ext.packed_layer_batch_wrapper([(flat, w[0], w[2], False, P, None) for w, P in zip(wides, Ps)])
+        Ps = [torch.empty((B * N, w.wf.shape[1]), dtype=torch.float32, device=dev) for w in wides]
+        ext.packed_layer_batch_wrapper([(flat, w.wf, w.b1, False, P, None) for w, P in zip(wides, Ps)])
         pks = [pk if pk is not None else ext.ball_pack_wrapper(idx, xyz, new_xyz) for pk, idx in zip(packs, idxs)]
-        cols, col = [], 0
-        for sc in scales:
-            cols.append(col)
-            col += sc[2].layers[-1][0].shape[1]
         # (not csrc/sa_wide.hip here: it walks a unit's column blocks one after the other, which is the right trade when there are
         # hundreds of units -- the RCNN's GroupAll level -- and the wrong one for the handful of live tiles of these levels: 1.16 vs
         # 1.13 ms for the RPN stage)
-        a1s = [torch.empty((pk.max_tiles * 64, w[0].shape[1]), dtype=torch.float32, device=dev) for pk, w in zip(pks, wides)]
-        ext.packed_gather_affine_batch_wrapper([(new_xyz, xyz, P.view(B, N, -1), w[1], pk, a1) for P, w, pk, a1 in zip(Ps, wides, pks, a1s)])
-        y2s = [torch.empty((pk.max_tiles * 64, w[3].shape[1]), dtype=torch.float32, device=dev) for pk, w in zip(pks, wides)]
-        ext.packed_layer_batch_wrapper([(a1, w[3], w[4], True, y2, pk) for a1, w, y2, pk in zip(a1s, wides, y2s, pks)])
-        ext.packed_layer_segmax_batch_wrapper([(y2, w[5], w[6], pk, B, M, out, c, zeroed) for y2, w, pk, c in zip(y2s, wides, pks, cols)])
+        a1s = [torch.empty((pk.max_tiles * 64, w.wf.shape[1]), dtype=torch.float32, device=dev) for pk, w in zip(pks, wides)]
+        ext.packed_gather_affine_batch_wrapper([(new_xyz, xyz, P.view(B, N, -1), w.wx, pk, a1) for P, w, pk, a1 in zip(Ps, wides, pks, a1s)])
+        y2s = [torch.empty((pk.max_tiles * 64, w.w2.shape[1]), dtype=torch.float32, device=dev) for pk, w in zip(pks, wides)]
+        ext.packed_layer_batch_wrapper([(a1, w.w2, w.b2, True, y2, pk) for a1, w, y2, pk in zip(a1s, wides, y2s, pks)])
+        ext.packed_layer_segmax_batch_wrapper([(y2, w.w3, w.b3, pk, B, M, out, c, zeroed) for y2, w, pk, c in zip(y2s, wides, pks, level.columns)])
 
-    def _sa_level(self, scales, lev, cur_xyz, cur_feat, out, pre):
+    def _sa_level(self, level, lev, cur_xyz, cur_feat, out, pre):
         """all scales of one MSG level into out (pre: out is zeroed, the packed kernels pool through atomicMax)"""
+        scales = level.scales
         packs = lev.get("pack") or [None] * len(scales)
-        if (USE_SCALE_BATCH and USE_PACKED and 2 <= len(scales) <= 4 and all(sc[2].wide is not None for sc in scales) and
-                has_entry(pu.pointnet2, "packed_layer_batch_wrapper")):
-            self._sa_level_wide(cur_xyz, lev["new_xyz"], cur_feat, scales, lev["idx"], packs, out, pre)
+        ext = pu.pointnet2
+        if (USE_SCALE_BATCH and USE_PACKED and 2 <= len(scales) <= 4 and all(sc.mlp.wide is not None for sc in scales) and
+                has_entry(ext, "packed_layer_batch_wrapper")):
+            self._sa_level_wide(cur_xyz, lev["new_xyz"], cur_feat, level, lev["idx"], packs, out, pre)
         elif (USE_SCALE_BATCH and USE_PACKED and len(scales) == 2 and cur_feat is not None and cur_feat.shape[2] % 128 == 0 and
-              all(sc[2].packed is not None and sc[2].packed[5].shape[1] == 128 and sc[2].packed[0].shape[0] == cur_feat.shape[2] for sc in scales) and
-              all(pk is not None for pk in packs) and has_entry(pu.pointnet2, "sa_packed_mlp_batch_wrapper")
-              and has_entry(pu.pointnet2, "packed_layer_batch_wrapper")):
-            # both 128-wide scales of the level side by side (round 5): their per-point parts in one layer launch, their fused
+              all(sc.mlp.packed is not None and sc.mlp.packed.w3.shape[1] == 128 and sc.mlp.packed.wf.shape[0] == cur_feat.shape[2] for sc in scales) and
+              all(pk is not None for pk in packs) and has_entry(ext, "sa_packed_mlp_batch_wrapper")
+              and has_entry(ext, "packed_layer_batch_wrapper")):
+            # both 128-wide scales of the level side by side: their per-point parts in one layer launch, their fused
             # gather -> layer 2 -> layer 3 -> pool kernels in one launch -- 2 launches for the level instead of 4; same kernels, same bits
-            ext = pu.pointnet2
             B, N, _ = cur_xyz.shape
             flat = cur_feat.view(B * N, cur_feat.shape[2])
-            if (USE_SA_NARROW and all(sc[2].packed_widths[0] == 64 and sc[2].packed_widths[1] in (64, 96) for sc in scales)
-                    and getattr(ext, "IS_HIP_EXTENSION", False)):
+            if USE_SA_NARROW and level.pcat is not None and getattr(ext, "IS_HIP_EXTENSION", False):
                 # both scales' first layers are 64 wide under their padding to 128 (RPN SA2): their per-point parts side by side in ONE
-                # 128-wide product (a column's chain does not depend on its neighbours: same bits), half the flops and bytes of two
-                # padded ones; the narrow kernel reads its 64 columns out of the shared rows
-                m0 = scales[0][2]
-                if getattr(m0, "_pcat", None) is None or m0._pcat[2] is not scales[1][2].packed[0]:
-                    m0._pcat = (torch.cat([sc[2].packed[0][:, :64] for sc in scales], 1).contiguous(),
-                                torch.cat([sc[2].packed[2][:64] for sc in scales]).contiguous(), scales[1][2].packed[0])
+                # 128-wide product (`_narrow_pair_weights`), half the flops and bytes of two padded ones; the narrow kernel reads its 64
+                # columns out of the shared rows
                 Pcat = torch.empty((B * N, 128), dtype=torch.float32, device=cur_xyz.device)
-                ext.packed_layer_wrapper(flat, m0._pcat[0], m0._pcat[1], False, Pcat)
+                wcat, bcat = level.pcat
+                ext.packed_layer_wrapper(flat, wcat, bcat, False, Pcat)
                 Ps = [Pcat.view(B, N, 128)[:, :, 64 * k:64 * k + 64] for k in range(2)]
             else:
                 Ps = [torch.empty((B * N, 128), dtype=torch.float32, device=cur_xyz.device) for _ in scales]
-                ext.packed_layer_batch_wrapper([(flat, sc[2].packed[0], sc[2].packed[2], False, P, None) for sc, P in zip(scales, Ps)])
+                ext.packed_layer_batch_wrapper([(flat, sc.mlp.packed.wf, sc.mlp.packed.b1, False, P, None) for sc, P in zip(scales, Ps)])
                 Ps = [P.view(B, N, 128) for P in Ps]
-            probs, col = [], 0
-            for (radius, ns, mlp, cin), pack, P in zip(scales, packs, Ps):
-                wf, wx, b1, w2, b2, w3, b3 = mlp.packed
-                probs.append((lev["new_xyz"], cur_xyz, P, wx, pack, w2, b2, w3, b3, out, col, pre, mlp.packed_widths))
-                col += mlp.layers[-1][0].shape[1]
-            ext.sa_packed_mlp_batch_wrapper(probs)
+            ext.sa_packed_mlp_batch_wrapper([(lev["new_xyz"], cur_xyz, P, m.packed.wx, pack, m.packed.w2, m.packed.b2, m.packed.w3, m.packed.b3,
+                                              out, col, pre, m.packed_widths) for m, pack, P, col in zip((sc.mlp for sc in scales), packs, Ps, level.columns)])
         else:
-            col = 0
-            for (radius, ns, mlp, cin), idx, pack in zip(scales, lev["idx"], packs):
-                self._sa_scale(cur_xyz, lev["new_xyz"], cur_feat, idx, mlp, cin, out, col, pack=pack, zeroed=pre)
-                col += mlp.layers[-1][0].shape[1]
+            for sc, idx, pack, col in zip(scales, lev["idx"], packs, level.columns):
+                self._sa_scale(cur_xyz, lev["new_xyz"], cur_feat, idx, sc.mlp, sc.cin, out, col, pack=pack, zeroed=pre)
 
     def _backbone(self, xyz, geo, fuse_tail=False, feats0=None):
         """-> the (B, N, 128) point features; fuse_tail: -> (features, None), or (None, inputs of the fused last stretch).
@@ -892,31 +909,26 @@ class FastPointRCNN:
         # the packed kernels deliver through atomicMax into zeros: ONE fill for all levels of the backbone (all scales, the padding
         # columns) instead of one per level -- a 5 us launch each on the feature stream
         B = xyz.shape[0]
-        shapes, pres = [], []
-        for npoint, scales in self.sa:
-            width = sum(s[2].layers[-1][0].shape[1] for s in scales)
-            shapes.append((B, npoint, _round128(width) if PAD128 else width))   # consumers (next level's per-point part, FP skip) read 128s
-            pres.append(bool(USE_PACKED and all(sc[2].packed is not None or sc[2].wide is not None or sc[3] == 0 for sc in scales)))
+        shapes = [(B, level.npoint, level.padded_width) for level in self.sa]
+        pres = [bool(USE_PACKED and level.on_packed) for level in self.sa]
         # levels that came with the geometry (the coordinates-only level 0, `_xyz_level`)
         early = [lev.get("out") if (lev.get("out") is not None and tuple(lev["out"].shape) == sh) else None for lev, sh in zip(geo["sa"], shapes)]
         sizes = [sh[0] * sh[1] * sh[2] if (pr and e is None) else 0 for sh, pr, e in zip(shapes, pres, early)]
         arena = torch.zeros((sum(sizes),), dtype=torch.float32, device=xyz.device) if sum(sizes) else None
         offs = [sum(sizes[:k]) for k in range(len(sizes))]
-        for k, ((npoint, scales), lev) in enumerate(zip(self.sa, geo["sa"])):
+        for k, (level, lev) in enumerate(zip(self.sa, geo["sa"])):
             if early[k] is not None:
                 l_feat.append(early[k])
                 continue
             cur_xyz, cur_feat = l_xyz[len(l_feat) - 1], l_feat[-1]
-            width = sum(s[2].layers[-1][0].shape[1] for s in scales)
-            wpad = shapes[k][2]
+            width = sum(sc.mlp.out_width for sc in level.scales)
             pre = pres[k]
             out = (arena[offs[k]:offs[k] + sizes[k]].view(shapes[k]) if pre
                    else torch.empty(shapes[k], dtype=torch.float32, device=xyz.device))
-            if wpad > width and not pre:
+            if level.padded_width > width and not pre:
                 out[:, :, width:] = 0
-            self._sa_level(scales, lev, cur_xyz, cur_feat, out, pre)
+            self._sa_level(level, lev, cur_xyz, cur_feat, out, pre)
             l_feat.append(out)
-        ext = pu.pointnet2
         for i in range(-1, -(len(self.fp) + 1), -1):          # coarse -> fine
             k = len(self.fp) + i                               # FP module index == fine level
             if geo.get("fp_out", {}).get(k) is not None:       # came with the geometry (`_xyz_level`)
@@ -943,8 +955,6 @@ class FastPointRCNN:
             # interpolated G added in its epilogue
             m = known_feat.shape[1]
             N1 = wt.shape[1]
-            if getattr(self, "_zero_bias", None) is None or self._zero_bias.numel() < N1 or self._zero_bias.device != wt.device:
-                self._zero_bias = torch.zeros((max(N1, 1024),), dtype=torch.float32, device=wt.device)
             G = point_layer(known_feat.view(B * m, c2), wt[:c2], self._zero_bias[:N1], False).view(B, m, N1)
             y1 = torch.empty((B * n, N1), dtype=torch.float32, device=known_feat.device)
             ext.packed_layer_interp_wrapper(skip.view(B * n, c1), wt[c2:], b1, relu1, y1, G, idx, weight)
@@ -979,7 +989,6 @@ class FastPointRCNN:
         """Backbone + RPN heads: everything up to (not including) the proposal layer.  ``want_reg`` = False (the runners): where the
         fused tail can decode the boxes itself the state carries "rpn_boxes" (B, N, 7) and "rpn_reg" is None; True: the regression
         rows are always produced (forward(): the dict of the reference's PointRCNN.forward)."""
-        cfg = self.cfg
         self.check_weights()
         if pts_input.shape[-1] != 3 + self.in_feat:
             raise ValueError("pts_input has %d channels, the backbone was built for 3 + %d" % (pts_input.shape[-1], self.in_feat))
@@ -997,6 +1006,7 @@ class FastPointRCNN:
         B, N, _ = xyz.shape
         with self._strictly():
             feats, tail = self._backbone(xyz, geo, fuse_tail=True, feats0=feats0)
+        rpn_boxes = None
         if tail is not None:
             # interpolation + FP module 0 + both heads: one kernel, a 64-point tile never leaves LDS (csrc/rpn_tail.hip)
             known_feat, idx, weight = tail
@@ -1005,7 +1015,6 @@ class FastPointRCNN:
             rpn_cls = torch.empty((B, N, 1), dtype=torch.float32, device=xyz.device)
             dec = None if want_reg or self.in_feat else self._tail_decode_cfg(N)
             rpn_reg = torch.empty((B, N, tw["n_reg"]), dtype=torch.float32, device=xyz.device) if dec is None else None
-            rpn_boxes = None
             if USE_FP_LINEAR and has_entry(pu.pointnet2, "rpn_tail_lin_wrapper"):
                 # FP layer 1 over the coarse points (a quarter of the rows), interpolated inside the fused kernel
                 m = known_feat.shape[1]
@@ -1025,7 +1034,6 @@ class FastPointRCNN:
             rpn_reg = self.rpn_reg(flat).view(B, N, -1)
             if feats.shape[2] != self.fp[0].n_out:            # narrow configurations: drop the zero padding again
                 feats = feats[:, :, :self.fp[0].n_out].contiguous()
-            rpn_boxes = None
         out = {"rpn_cls": rpn_cls, "rpn_reg": rpn_reg, "rpn_boxes": rpn_boxes, "backbone_xyz": xyz, "rpn_features": feats, "groups": geo.get("groups")}
         out["rpn_scores_raw"] = rpn_cls[:, :, 0].contiguous()     # the proposal layer's and the segmentation decision's input
         return out
@@ -1097,16 +1105,16 @@ class FastPointRCNN:
     def _point_mlp_ok(self):
         """Shapes csrc/rcnn_point_mlp.hip is written for: xyz_up 5(8) -> 128 -> 128, merge 256 -> 128, SA1 through the
         fused MFMA kernel with a 128 -> 128 per-point part."""
-        if getattr(self, "_pm_ok", None) is None:
+        if self._pm_ok is None:
             ok = len(self.xyz_up.layers) == 2 and len(self.merge_down.layers) == 1 and len(self.rcnn_sa) > 0
             if ok:
                 (wu1, _, r1), (wu2, _, r2) = self.xyz_up.layers
                 (wm, _, r3), = self.merge_down.layers
-                mlp1, ns1 = self.rcnn_sa[0][3], self.rcnn_sa[0][2]
+                sa1, mlp1 = self.rcnn_sa[0], self.rcnn_sa[0].mlp
                 ok = (tuple(wu1.shape) == (8, 128) and tuple(wu2.shape) == (128, 128) and tuple(wm.shape) == (256, 128)
                       and r1 and r2 and r3 and mlp1.split is not None and tuple(mlp1.split[0].shape) == (128, 128)
-                      and len(mlp1.layers) == 3 and self.rcnn_sa[0][0] is not None
-                      and pu.pointnet2.sa_mlp_fused_supported(128, mlp1.layers[1][0].shape[1], mlp1.layers[2][0].shape[1], ns1))
+                      and len(mlp1.layers) == 3 and sa1.npoint is not None
+                      and pu.pointnet2.sa_mlp_fused_supported(128, mlp1.layers[1][0].shape[1], mlp1.layers[2][0].shape[1], sa1.nsample))
             self._pm_ok = bool(ok)
         return self._pm_ok
 
@@ -1119,62 +1127,150 @@ class FastPointRCNN:
         `_sa_scale`'s condition for that branch, known before the level's features exist (they are the level below's output)"""
         ext = pu.pointnet2
         if not (USE_PACKED and mlp.packed is None and mlp.wide is not None and USE_WIDE_FUSED
-                and has_entry(ext, "sa_wide_fused3_wrapper") and getattr(mlp, "wide_cat", None) is not None):
+                and has_entry(ext, "sa_wide_fused3_wrapper") and mlp.wide_cat is not None):
             return False
-        wf, wx, b1, w2, b2, w3, b3 = mlp.wide
-        c_below = below.layers[-1][0].shape[1]
-        return bool(c_below == wf.shape[0] and ext.sa_wide_fused3_supported(wf.shape[0], wf.shape[1], w2.shape[1], w3.shape[1]))
+        w = mlp.wide
+        return bool(below.out_width == w.wf.shape[0] and ext.sa_wide_fused3_supported(w.wf.shape[0], w.wf.shape[1], w.w2.shape[1], w.w3.shape[1]))
+
+    def _pool_canonical(self, xyz, feats, seg_mask, pts_depth, rois, depth_norm, groups):
+        """enlarge + pool + canonical transform + aligned row layout [x',y',z',mask,depth,0,0,0 | feats] in ONE kernel
+        -> (pooled (B,M,P,8+C), distinct points per RoI or None, the rows' coordinates as dense clouds, entrance rows, feature rows)"""
+        R = self.cfg.RCNN
+        B, M, P, W = rois.shape[0], rois.shape[1], R.NUM_POINTS, 8 + feats.shape[2]
+        pooled = torch.empty((B, M, P, W), dtype=torch.float32, device=xyz.device)
+        empty = torch.empty((B, M), dtype=torch.int32, device=xyz.device)
+        dedup = USE_POOL_DEDUP and USE_PACKED and USE_RCNN_POINT_MLP and P % 64 == 0 and self._point_mlp_ok()
+        pooled_cnt = torch.empty((B, M), dtype=torch.int32, device=xyz.device) if dedup else None
+        # ... and the rows' coordinates once more as dense clouds (what sampling and ball queries read; was a strided copy)
+        xyz_dense = torch.empty((B, M, P, 3), dtype=torch.float32, device=xyz.device)
+        depth_norm = depth_norm if depth_norm is not None else (pts_depth / 70.0 - 0.5).contiguous()
+        roipool3d_utils.roipool3d_cuda.forward_canonical(xyz, rois.contiguous(), feats, seg_mask.contiguous(), depth_norm, R.POOL_EXTRA_WIDTH,
+                                                         pooled, empty, pooled_cnt, groups, xyz_dense)
+        rows = pooled.view(B * M * P, W)
+        return pooled, pooled_cnt, xyz_dense, rows[:, 0:8], rows[:, 8:]          # (strided views: columns 5..7 are zero)
+
+    def _pool_torch(self, xyz, feats, seg_mask, pts_depth, rois, nin):
+        """the same rows by the reference's sequence of torch operations (rcnn_net.py:127-160) -> as `_pool_canonical`"""
+        R = self.cfg.RCNN
+        extra = [seg_mask.unsqueeze(2)]
+        if R.USE_DEPTH:
+            extra.append((pts_depth / 70.0 - 0.5).unsqueeze(2))
+        pts_feature = torch.cat(extra + [feats], dim=2)                   # (B,N,2+128), already point-major
+        pooled, _ = roipool3d_utils.roipool3d_gpu(xyz, pts_feature, rois, R.POOL_EXTRA_WIDTH, sampled_pt_num=R.NUM_POINTS)
+        B, M, P, W = pooled.shape
+        pooled[:, :, :, 0:3] -= rois[:, :, 0:3].unsqueeze(2)
+        flat = pooled.view(B * M, P, W)
+        flat[:, :, 0:3] = kitti_utils.rotate_pc_along_y_torch(flat[:, :, 0:3], rois.reshape(-1, 7)[:, 6])
+        rows = flat.view(B * M * P, W)
+        a = rows.new_zeros((rows.shape[0], _round4(nin)))
+        a[:, :nin] = rows[:, :nin]
+        return pooled, None, None, a, rows[:, nin:]
+
+    def _roi_geometry_fused(self, cur_xyz, pooled_cnt, zhdr):
+        """both sampled levels' geometry and row lists for every RoI cloud in ONE launch (csrc/roi_geometry.hip) -> (per level (new_xyz, idx,
+        rep, pack), the GroupAll level's row list or None, the level-1 centre rows or None); (None, None, None): the levels are not covered"""
+        # a wave per RoI (rcnn_roi_geometry_kernel) instead of FPS, ball query, representative map -- twice -- as six latency-bound launches; and
+        # both levels' row lists written by the wave that holds the hit lists (no pack launches for these levels).  The index tensors themselves
+        # are not written on the HIP path: the packed kernels read the lists, `idx` is asked for its shape; the lists' rows carry their cloud:
+        # no padded last tile per RoI cloud.
+        ext, sa = pu.pointnet2, self.rcnn_sa
+        if not (len(sa) >= 2 and sa[0].npoint is not None and sa[1].npoint is not None
+                and has_entry(ext, "rcnn_roi_geometry_packs_wrapper") and USE_PACKED and sa[0].mlp.on_packed and sa[1].mlp.on_packed
+                and ext.rcnn_roi_geometry_supported(cur_xyz.shape[1], sa[0].npoint, sa[0].nsample, sa[1].npoint, sa[1].nsample)):
+            return None, None, None
+        hd = zhdr() + zhdr()
+        rc = sa[0].mlp.packed is not None and sa[1].mlp.packed is not None      # the consumers that read lists whose rows carry their cloud
+        # ... and, in that form, the list of the GroupAll level above them (one group per RoI: no clouds merged to fill tiles)
+        ga = bool(rc and hd and len(sa) == 3 and sa[2].npoint is None and self._groupall_fused3_ok(sa[2].mlp, sa[1].mlp))
+        # ... and the level-1 centres that are their own representatives as a row list: level 2's per-point layer over those rows only
+        cr = bool(rc and hd and has_entry(ext, "rows_gemm128_rows_wrapper") and tuple(sa[1].mlp.packed.wf.shape) == (128, 128))
+        # the wrapper's protocol is positional (test proxies forward *args only): headers, write-idx flag, row-cloud flag, then the extras
+        extra = ()
+        if hd:
+            extra = hd + (False, rc) + ((zhdr()[0], True) if ga else (None, False)) + ((zhdr()[0], True) if cr else ())
+        new1, idx1, rep1, new2, idx2, rep2, pack1, pack2, *rest = ext.rcnn_roi_geometry_packs_wrapper(
+            cur_xyz, pooled_cnt.view(-1), sa[0].npoint, sa[0].radius, sa[0].nsample, sa[1].npoint, sa[1].radius, sa[1].nsample, *extra)
+        listed, crows = next((x for x in rest if hasattr(x, "rowinfo")), None), next((x for x in rest if isinstance(x, tuple)), None)
+        return ((new1, idx1, rep1, pack1), (new2, idx2, rep2, pack2)), listed, crows
+
+    def _roi_level_geometry(self, level, cur_xyz, limit, rep_in, first, centre_dedup):
+        """sampling, ball query, representative map and row list of one sampled RCNN level, launch by launch
+        -> (new_xyz, idx, rep, pack).  limit: the distinct points per cloud (level 0 of deduplicated pooling), else None"""
+        ext = pu.pointnet2
+        npoint, radius, ns, mlp, _ = level
+        Bc, n = cur_xyz.shape[0], cur_xyz.shape[1]
+        sel, new_xyz = self._sample(cur_xyz, npoint, False, roi_clouds=True)
+        if limit is not None and has_entry(ext, "ball_query_limit_wrapper"):
+            # pooled rows k >= count are copies of row k % count: scanning the distinct rows finds every ball's points
+            # (the row list below drops the copies anyway); a RoI holds ~60 of its 512 rows at this scene size
+            idx = torch.empty((Bc, npoint, ns), dtype=torch.int32, device=cur_xyz.device)     # every slot is written
+            ext.ball_query_limit_wrapper(Bc, n, npoint, radius, ns, new_xyz, cur_xyz, limit, idx)
+        else:
+            idx = pu.ball_query(radius, ns, cur_xyz, new_xyz)
+        # which of THIS level's centres are copies of one another (= the next level's point map): a centre that copies an
+        # earlier one gets no rows of its own -- the next level never lists it, so its output is never read
+        rep = ext.dup_rep_wrapper(sel, n, limit if first else None, None if first else rep_in) if (centre_dedup and (first or rep_in is not None)) else None
+        pack = None
+        if limit is not None:
+            pack = ext.ball_pack_wrapper(idx, cur_xyz, new_xyz, limit, None, rep)   # copies of pooled points are dropped too
+        elif USE_PACKED and mlp.on_packed and has_entry(ext, "ball_pack_wrapper"):
+            pack = (ext.ball_pack_wrapper(idx, cur_xyz, new_xyz, None, rep_in, rep) if (rep_in is not None and ns <= 64)
+                    else ext.ball_pack_wrapper(idx, cur_xyz, new_xyz))
+        return new_xyz, idx, rep, pack
+
+    def _groupall_geometry(self, cur_xyz, rep, zhdr, listed):
+        """the GroupAll level's geometry -> the entries of its level dict.  listed: the row list the fused launch wrote (every RoI one group,
+        centre 0, of its own 32 centres), or None: built here"""
+        ext, cache = pu.pointnet2, self._groupall
+        Bc, n = cur_xyz.shape[0], cur_xyz.shape[1]
+        if listed is not None:
+            key = ("origin", Bc, str(cur_xyz.device))
+            if key not in cache:
+                cache[key] = torch.zeros((Bc, 1, 3), dtype=torch.float32, device=cur_xyz.device)
+            return {"new_xyz": cache[key], "idx": listed.idx, "pack": listed, "f": 1}
+        # GroupAll (pointnet2_utils.py:267-288): ONE group holding all n points, no centre subtraction == a ball query answer 0..n-1 around
+        # the origin; same packed kernels as the other levels.  f clouds side by side form one "cloud" with f centres (no centre is
+        # subtracted, so cloud borders mean nothing here): n = 32 points per RoI would leave every 64-row MFMA tile half full of copies.
+        # The index tensor and the origins are constants of the shape (cached); the row list holds coordinates and is built per batch.
+        f = 1
+        while 2 * f * n <= 64 and Bc % (2 * f) == 0:
+            f *= 2
+        key = (Bc, n, f, str(cur_xyz.device))
+        if key not in cache:
+            ga_idx = torch.arange(f * n, dtype=torch.int32, device=cur_xyz.device).view(1, f, n).expand(Bc // f, f, n).contiguous()
+            cache[key] = (ga_idx, torch.zeros((Bc // f, f, 3), dtype=torch.float32, device=cur_xyz.device),
+                          (torch.arange(f, dtype=torch.int32, device=cur_xyz.device) * n).view(1, f, 1))
+        ga_idx, origin, shift = cache[key]
+        xyz_v = cur_xyz.view(Bc // f, f * n, 3)
+        # the f clouds' maps side by side, shifted to the merged cloud's numbering
+        rep_v = (rep.view(Bc // f, f, n) + shift).view(Bc // f, f * n) if (rep is not None and n <= 64) else None
+        return {"xyz": xyz_v, "new_xyz": origin, "idx": ga_idx, "f": f, "pack": ext.ball_pack_wrapper(ga_idx, xyz_v, origin, None, rep_v, None, *zhdr())}
+
+    def _rcnn_arena(self, levels, zarena):
+        """the pooled outputs of the levels that pool through atomicMax, out of the stage's one zero fill -> (arena or None, sizes)"""
+        sizes = [lev["xyz"].shape[0] * (level.npoint if level.npoint is not None else lev["f"]) * level.mlp.out_width
+                 if (lev["pack"] is not None and USE_PACKED and level.mlp.on_packed) else 0 for level, lev in zip(self.rcnn_sa, levels)]
+        return ({"zero": zarena, "parts": [zarena.take((n_,)) if n_ else None for n_ in sizes]} if sum(sizes) else None), sizes
 
     def _rcnn_geometry(self, xyz, feats, seg_mask, pts_depth, rois, depth_norm=None, groups=None):
         """Everything of the RCNN stage (rcnn_net.py:127-185) that needs no MLP result: RoI pooling into the canonical row layout,
         then per SA level sampling, ball query and the distinct-row lists.  All of it hangs on the RoIs and on coordinates only
         (the pooled FEATURES are copied, never computed on), so the pipelined runner launches it on the proposal stream right
-        behind the proposal layer -- a chain of ten latency-bound launches, 0.3 ms when it sat on the feature stream in front of
-        the MFMA kernels (profiles/r02_bench_step_kernel_stats.md).  -> state for `_rcnn_features`."""
+        behind the proposal layer, off the feature stream (a chain of ten latency-bound launches).  -> state for `_rcnn_features`."""
         R = self.cfg.RCNN
         if not (R.ROI_SAMPLE_JIT and R.USE_RPN_FEATURES and not R.USE_INTENSITY):
             raise NotImplementedError("fast path covers the default.yaml RCNN input configuration")
         nin = self.model.rcnn_net.rcnn_input_channel                           # xyz + mask + depth = 5
-        rp = roipool3d_utils.roipool3d_cuda
         ext = pu.pointnet2
-        C = feats.shape[2]
-        pooled_cnt = None
-        if (USE_ROIPOOL_CANONICAL and has_entry(rp, "forward_canonical") and R.USE_DEPTH and nin == 5 and C % 4 == 0):
-            # enlarge + pool + canonical transform + aligned row layout [x',y',z',mask,depth,0,0,0 | feats] in ONE kernel
-            B, M = rois.shape[0], rois.shape[1]
-            P, W = R.NUM_POINTS, 8 + C
-            pooled = torch.empty((B, M, P, W), dtype=torch.float32, device=xyz.device)
-            empty = torch.empty((B, M), dtype=torch.int32, device=xyz.device)
-            if USE_POOL_DEDUP and USE_PACKED and USE_RCNN_POINT_MLP and P % 64 == 0 and self._point_mlp_ok():
-                pooled_cnt = torch.empty((B, M), dtype=torch.int32, device=xyz.device)
-            # ... and the rows' coordinates once more as dense clouds (what sampling and ball queries read; was a strided copy)
-            xyz_dense = torch.empty((B, M, P, 3), dtype=torch.float32, device=xyz.device)
-            rp.forward_canonical(xyz, rois.contiguous(), feats, seg_mask.contiguous(),
-                                 depth_norm if depth_norm is not None else (pts_depth / 70.0 - 0.5).contiguous(),
-                                 R.POOL_EXTRA_WIDTH, pooled, empty, pooled_cnt, groups, xyz_dense)
-            flat = pooled.view(B * M, P, W)
-            rows = flat.view(B * M * P, W)
-            a = rows[:, 0:8]                                                   # strided view: columns 5..7 are zero
-            rpn_part = rows[:, 8:]
+        if USE_ROIPOOL_CANONICAL and has_entry(roipool3d_utils.roipool3d_cuda, "forward_canonical") and R.USE_DEPTH and nin == 5 and feats.shape[2] % 4 == 0:
+            pooled, pooled_cnt, xyz_dense, a, rpn_part = self._pool_canonical(xyz, feats, seg_mask, pts_depth, rois, depth_norm, groups)
         else:
-            extra = [seg_mask.unsqueeze(2)]
-            if R.USE_DEPTH:
-                extra.append((pts_depth / 70.0 - 0.5).unsqueeze(2))
-            pts_feature = torch.cat(extra + [feats], dim=2)                   # (B,N,2+128), already point-major
-            pooled, _ = roipool3d_utils.roipool3d_gpu(xyz, pts_feature, rois, R.POOL_EXTRA_WIDTH, sampled_pt_num=R.NUM_POINTS)
-            B, M, P, W = pooled.shape
-            xyz_dense = None
-            pooled[:, :, :, 0:3] -= rois[:, :, 0:3].unsqueeze(2)
-            flat = pooled.view(B * M, P, W)
-            flat[:, :, 0:3] = kitti_utils.rotate_pc_along_y_torch(flat[:, :, 0:3], rois.reshape(-1, 7)[:, 6])
-            rows = flat.view(B * M * P, W)
-            a = rows.new_zeros((rows.shape[0], _round4(nin)))
-            a[:, :nin] = rows[:, :nin]
-            rpn_part = rows[:, nin:]
+            pooled, pooled_cnt, xyz_dense, a, rpn_part = self._pool_torch(xyz, feats, seg_mask, pts_depth, rois, nin)
+        B, M, P, W = pooled.shape
+        rows = pooled.view(B * M * P, W)
         point_mlp = bool(USE_RCNN_POINT_MLP and W == 136 and rows.shape[0] % 64 == 0 and self._point_mlp_ok())
         use_rows = bool(point_mlp and pooled_cnt is not None and has_entry(ext, "pooled_rows_wrapper"))
-        cur_xyz = xyz_dense.view(B * M, P, 3) if xyz_dense is not None else flat[:, :, 0:3].contiguous()
-        levels = []
+        cur_xyz = xyz_dense.view(B * M, P, 3) if xyz_dense is not None else pooled.view(B * M, P, W)[:, :, 0:3].contiguous()
         # one zero fill for this stage: the headers of its three row lists and the pooled outputs of its levels (see ZeroArena)
         zarena = ZeroArena(("rcnn", B, M, P, str(rows.device)), rows.device)
         zhdr = (lambda: (zarena.take((4,), torch.int32),)) if getattr(ext, "IS_HIP_EXTENSION", False) else (lambda: ())   # positional (7th) argument
@@ -1183,120 +1279,27 @@ class FastPointRCNN:
         # of one another.  Level 0: pooled point k >= count is a copy of k % count (`limit`); deeper: the centres the sampling
         # picked from copies of one source are copies of one another -- coordinates, ball and therefore features (dup_rep).  The
         # deeper levels drop the rows of every point that is not the first of its kind, and such a centre gets no rows of its own
-        # either (prcnn_ball_pack_rep; round 3: 7.5x fewer SA2 rows on LiDAR-shaped scenes, bit-identical results).
-        centre_dedup = bool(pooled_cnt is not None and point_mlp and has_entry(ext, "dup_rep_wrapper"))
-        rep = None
-        # The two sampled levels' geometry for every RoI cloud in ONE launch (a wave per RoI: csrc/roi_geometry.hip rcnn_roi_geometry_kernel)
-        # instead of FPS, ball query, representative map -- twice -- as six latency-bound launches; and both levels' row lists written by
-        # the wave that holds the hit lists (no pack launches for these levels)
-        fused_geo = None
-        sa = self.rcnn_sa
-        if (centre_dedup and len(sa) >= 2 and sa[0][0] is not None and sa[1][0] is not None
-                and has_entry(ext, "rcnn_roi_geometry_packs_wrapper") and USE_PACKED
-                and all(m_[3].packed is not None or m_[3].wide is not None for m_ in sa[:2])
-                and ext.rcnn_roi_geometry_supported(cur_xyz.shape[1], sa[0][0], sa[0][2], sa[1][0], sa[1][2])):
-            # (the index tensors themselves are not written on the HIP path: the packed kernels read the lists, `idx` is asked for its shape;
-            #  the lists' rows carry their cloud: no padded last tile per RoI cloud)
-            hd = zhdr() + zhdr()
-            rc = all(m_[3].packed is not None for m_ in sa[:2])        # the consumers that read lists whose rows carry their cloud
-            # ... and, in that form, the list of the GroupAll level above them (one group per RoI: no clouds merged to fill tiles)
-            ga = bool(rc and hd and len(sa) == 3 and sa[2][0] is None and self._groupall_fused3_ok(sa[2][3], sa[1][3]))
-            # ... and the level-1 centres that are their own representatives as a row list: level 2's per-point layer over those rows only
-            cr = bool(rc and hd and has_entry(ext, "rows_gemm128_rows_wrapper") and sa[1][3].packed is not None
-                      and tuple(sa[1][3].packed[0].shape) == (128, 128))
-            extra = ()
-            if hd:
-                extra = hd + (False, rc) + ((zhdr()[0], True) if ga else (None, False)) + ((zhdr()[0], True) if cr else ())
-            fused_geo = ext.rcnn_roi_geometry_packs_wrapper(cur_xyz, pooled_cnt.view(-1), sa[0][0], sa[0][1], sa[0][2], sa[1][0], sa[1][1],
-                                                            sa[1][2], *extra)
-        fused_p3 = next((x for x in (fused_geo or ())[8:] if hasattr(x, "rowinfo")), None)
-        fused_crows = next((x for x in (fused_geo or ())[8:] if isinstance(x, tuple)), None)
-        for k, (npoint, radius, ns, mlp, cin) in enumerate(self.rcnn_sa):
+        # either (prcnn_ball_pack_rep: 7.5x fewer SA2 rows on LiDAR-shaped scenes, bit-identical results).
+        dedup = pooled_cnt is not None and point_mlp
+        centre_dedup = bool(dedup and has_entry(ext, "dup_rep_wrapper"))
+        fused_levels, fused_listed, fused_crows = self._roi_geometry_fused(cur_xyz, pooled_cnt, zhdr) if centre_dedup else (None, None, None)
+        levels, rep = [], None
+        for k, level in enumerate(self.rcnn_sa):
             lev = {"xyz": cur_xyz, "new_xyz": None, "idx": None, "pack": None}
             if k == 1 and fused_crows is not None:
                 lev["crows"] = fused_crows
-            if npoint is not None and fused_geo is not None and k < 2:
-                new_xyz, idx, rep = fused_geo[3 * k:3 * k + 3]
-                lev["pack"] = fused_geo[6 + k]
-                lev["new_xyz"], lev["idx"] = new_xyz, idx
-                cur_xyz = new_xyz
-            elif npoint is not None:
-                Bc, n = cur_xyz.shape[0], cur_xyz.shape[1]
-                if n <= 1024 and has_entry(ext, "fps_new_xyz_wrapper"):
-                    sel, new_xyz = ext.fps_new_xyz_wrapper(cur_xyz, npoint)    # sampling + the centres' coordinates, one launch
+            if level.npoint is not None:
+                if fused_levels is not None and k < 2:
+                    lev["new_xyz"], lev["idx"], rep, lev["pack"] = fused_levels[k]
                 else:
-                    sel = pu.furthest_point_sample(cur_xyz, npoint)
-                    new_xyz = torch.gather(cur_xyz, 1, sel.long().unsqueeze(-1).expand(-1, -1, 3)).contiguous()
-                dedup = k == 0 and pooled_cnt is not None and point_mlp
-                if dedup and has_entry(ext, "ball_query_limit_wrapper"):
-                    # pooled rows k >= count are copies of row k % count: scanning the distinct rows finds every ball's points
-                    # (the row list below drops the copies anyway); a RoI holds ~60 of its 512 rows at this scene size
-                    idx = torch.empty((Bc, npoint, ns), dtype=torch.int32, device=cur_xyz.device)     # every slot is written
-                    ext.ball_query_limit_wrapper(Bc, n, npoint, radius, ns, new_xyz, cur_xyz, pooled_cnt.view(-1), idx)
-                else:
-                    idx = pu.ball_query(radius, ns, cur_xyz, new_xyz)
-                # which of THIS level's centres are copies of one another (= the next level's point map): a centre that copies an
-                # earlier one gets no rows of its own -- the next level never lists it, so its output is never read
-                rep_in = rep
-                if centre_dedup and (k == 0 or rep is not None):
-                    rep = ext.dup_rep_wrapper(sel, n, pooled_cnt.view(-1) if k == 0 else None, rep_in if k > 0 else None)
-                else:
-                    rep = None
-                if dedup:
-                    lev["pack"] = ext.ball_pack_wrapper(idx, cur_xyz, new_xyz, pooled_cnt.view(-1), None, rep)   # copies of pooled points are dropped too
-                elif USE_PACKED and (mlp.packed is not None or mlp.wide is not None) and has_entry(ext, "ball_pack_wrapper"):
-                    lev["pack"] = (ext.ball_pack_wrapper(idx, cur_xyz, new_xyz, None, rep_in, rep) if (rep_in is not None and ns <= 64)
-                                   else ext.ball_pack_wrapper(idx, cur_xyz, new_xyz))
-                lev["new_xyz"], lev["idx"] = new_xyz, idx
-                cur_xyz = new_xyz
-            elif fused_p3 is not None:
-                # GroupAll over the list the fused launch wrote: every RoI one group (centre 0) of its own 32 centres
-                Bc, n = cur_xyz.shape[0], cur_xyz.shape[1]
-                cache = self.__dict__.setdefault("_groupall", {})
-                key = ("origin", Bc, str(cur_xyz.device))
-                if key not in cache:
-                    cache[key] = torch.zeros((Bc, 1, 3), dtype=torch.float32, device=cur_xyz.device)
-                lev.update({"new_xyz": cache[key], "idx": fused_p3.idx, "pack": fused_p3, "f": 1})
-                cur_xyz = None
-            elif USE_PACKED and (mlp.packed is not None or mlp.wide is not None):
-                # GroupAll (pointnet2_utils.py:267-288): ONE group holding all n points, no centre subtraction == a ball
-                # query answer 0..n-1 around the origin; same packed kernels as the other levels
-                # f clouds side by side form one "cloud" with f centres (no centre is subtracted, so cloud borders mean nothing
-                # here): n = 32 points per RoI would leave every 64-row MFMA tile half full of copies.  The index tensor and the
-                # origins are constants of the shape (cached); the row list holds coordinates and is built per batch.
-                Bc, n = cur_xyz.shape[0], cur_xyz.shape[1]
-                f = 1
-                while 2 * f * n <= 64 and Bc % (2 * f) == 0:
-                    f *= 2
-                key = (Bc, n, f, str(cur_xyz.device))
-                # (one entry per shape, never replaced: a captured hipGraph of another batch size may hold these addresses)
-                cache = self.__dict__.setdefault("_groupall", {})
-                if key not in cache:
-                    ga_idx = torch.arange(f * n, dtype=torch.int32, device=cur_xyz.device).view(1, f, n).expand(Bc // f, f, n).contiguous()
-                    cache[key] = (key, ga_idx, torch.zeros((Bc // f, f, 3), dtype=torch.float32, device=cur_xyz.device),
-                                  (torch.arange(f, dtype=torch.int32, device=cur_xyz.device) * n).view(1, f, 1))
-                _, ga_idx, origin, shift = cache[key]
-                xyz_v = cur_xyz.view(Bc // f, f * n, 3)
-                rep_v = None
-                if rep is not None and n <= 64:          # the f clouds' maps side by side, shifted to the merged cloud's numbering
-                    rep_v = (rep.view(Bc // f, f, n) + shift).view(Bc // f, f * n)
-                lev.update({"xyz": xyz_v, "new_xyz": origin, "idx": ga_idx,
-                            "pack": ext.ball_pack_wrapper(ga_idx, xyz_v, origin, None, rep_v, None, *zhdr()) if rep_v is not None else ext.ball_pack_wrapper(ga_idx, xyz_v, origin, None, None, None, *zhdr()),
-                            "f": f})
+                    limit = pooled_cnt.view(-1) if (k == 0 and dedup) else None
+                    lev["new_xyz"], lev["idx"], rep, lev["pack"] = self._roi_level_geometry(level, cur_xyz, limit, rep, k == 0, centre_dedup)
+                cur_xyz = lev["new_xyz"]
+            elif fused_listed is not None or (USE_PACKED and level.mlp.on_packed):
+                lev.update(self._groupall_geometry(cur_xyz, rep, zhdr, fused_listed))
                 cur_xyz = None
             levels.append(lev)
-        shapes = []
-        for (npoint, radius, ns, mlp, cin), lev in zip(self.rcnn_sa, levels):
-            cout = mlp.layers[-1][0].shape[1]
-            if lev["pack"] is not None and USE_PACKED and (mlp.packed is not None or mlp.wide is not None):
-                rows_out = lev["xyz"].shape[0] * (npoint if npoint is not None else lev["f"])
-                shapes.append(rows_out * cout)
-            else:
-                shapes.append(0)
-        arena = None
-        if sum(shapes):
-            parts = [zarena.take((n_,)) if n_ else None for n_ in shapes]
-            arena = {"zero": zarena, "parts": parts}
+        arena, shapes = self._rcnn_arena(levels, zarena)
         zarena.done()
         return {"B": B, "M": M, "P": P, "W": W, "rows": rows, "a": a, "rpn_part": rpn_part, "pooled": pooled, "pooled_cnt": pooled_cnt,
                 "point_mlp": point_mlp, "rowlist": rowlist, "levels": levels, "arena": arena, "arena_shapes": shapes}
@@ -1306,13 +1309,12 @@ class FastPointRCNN:
         B, M, P = rg["B"], rg["M"], rg["P"]
         rows = rg["rows"]
         P_pre = None
-        sa1 = self.rcnn_sa[0]
         ext = pu.pointnet2
         if rg["point_mlp"]:
             # xyz_up (2 layers) + concat + merge_down + the per-point part of SA1's layer 1: tiled MFMA layer kernels
             (wu1, bu1, _), (wu2, bu2, _) = self.xyz_up.layers
             (wm, bm, _), = self.merge_down.layers
-            wf, _, b1 = sa1[3].split
+            wf, _, b1 = self.rcnn_sa[0].mlp.split
             P_pre = torch.empty((rows.shape[0], 128), dtype=torch.float32, device=rows.device)
             if rg.get("rowlist") is not None:
                 ext.rcnn_point_mlp_rows_wrapper(rows, 8, wu1, bu1, wu2, bu2, wm, bm, wf, b1, P_pre, rg["rowlist"])     # only P, only the distinct rows
@@ -1329,65 +1331,66 @@ class FastPointRCNN:
         shapes, arena = rg["arena_shapes"], rg["arena"]
         if arena is not None:
             if rg.get("arena_used"):           # a second pass over the same geometry (another set of weights, a probe): the atomicMax pools
-                for part in arena["parts"]:    # must not start from the first pass's maxima (ADVICE r4) -- the first pass stays fill-free
+                for part in arena["parts"]:    # must not start from the first pass's maxima -- the first pass stays fill-free
                     if part is not None:
                         part.zero_()
             rg["arena_used"] = True
-        for k, ((npoint, radius, ns, mlp, cin), lev) in enumerate(zip(self.rcnn_sa, rg["levels"])):
+        for k, (level, lev) in enumerate(zip(self.rcnn_sa, rg["levels"])):
+            npoint, mlp, cin = level.npoint, level.mlp, level.cin
             cur_xyz, cur_feat = lev["xyz"], l_feat[-1]
-            cout = mlp.layers[-1][0].shape[1]
             first = len(l_feat) == 1
             pre = shapes[k] > 0
+            f = lev.get("f", 1)                                                 # GroupAll over f RoIs per "cloud" (see _groupall_geometry)
+            Bc = cur_xyz.shape[0] * f
+            oshape = (Bc, npoint if npoint is not None else 1, mlp.out_width)
+            out = arena["parts"][k].view(oshape) if pre else torch.empty(oshape, dtype=torch.float32, device=cur_xyz.device)
             if npoint is not None:
-                Bc = cur_xyz.shape[0]
-                out = (arena["parts"][k].view(Bc, npoint, cout) if pre
-                       else torch.empty((Bc, npoint, cout), dtype=torch.float32, device=cur_xyz.device))
                 P_lev = P_pre if first else None
                 if lev.get("crows") is not None and not first and mlp.packed is not None and cur_feat.shape[2] == 128:
                     # the level's per-point part P = f W1 + b1 over the rows its lists name (the centres that are their own representatives)
                     P_lev = torch.empty((Bc * cur_xyz.shape[1], 128), dtype=torch.float32, device=cur_xyz.device)
-                    ext.rows_gemm128_rows_wrapper(cur_feat.view(-1, 128), mlp.packed[0], mlp.packed[2], False, P_lev, lev["crows"])
+                    ext.rows_gemm128_rows_wrapper(cur_feat.view(-1, 128), mlp.packed.wf, mlp.packed.b1, False, P_lev, lev["crows"])
                     P_lev = P_lev.view(Bc, cur_xyz.shape[1], 128)
-                self._sa_scale(cur_xyz, lev["new_xyz"], cur_feat, lev["idx"], mlp, cin, out, 0, P_pre=P_lev, pack=lev["pack"],
-                               zeroed=pre)
-            elif lev["pack"] is not None:                                       # GroupAll over f RoIs per "cloud" (see _rcnn_geometry)
-                f = lev["f"]
-                Bc = cur_xyz.shape[0] * f
+                self._sa_scale(cur_xyz, lev["new_xyz"], cur_feat, lev["idx"], mlp, cin, out, 0, P_pre=P_lev, pack=lev["pack"], zeroed=pre)
+            elif lev["pack"] is not None:
                 feat_v = cur_feat.view(Bc // f, cur_xyz.shape[1], cur_feat.shape[2])
-                out = (arena["parts"][k].view(Bc, 1, cout) if pre
-                       else torch.empty((Bc, 1, cout), dtype=torch.float32, device=cur_xyz.device))
-                self._sa_scale(cur_xyz, lev["new_xyz"], feat_v, lev["idx"], mlp, cin, out.view(Bc // f, f, cout), 0, pack=lev["pack"], dense=True,
-                               zeroed=pre)
+                self._sa_scale(cur_xyz, lev["new_xyz"], feat_v, lev["idx"], mlp, cin, out.view(Bc // f, f, mlp.out_width), 0, pack=lev["pack"],
+                               dense=True, zeroed=pre)
             else:                                                               # GroupAll: one group of n points
-                Bc, n = cur_xyz.shape[0], cur_xyz.shape[1]
-                c4 = _round4(cin)
+                n, c4 = cur_xyz.shape[1], _round4(cin)
                 g = cur_feat.new_zeros((Bc, n, c4 + 4))
                 g[:, :, :cin] = cur_feat
                 g[:, :, c4:c4 + 3] = cur_xyz
-                y = mlp(g.view(Bc * n, c4 + 4))
-                out = torch.empty((Bc, 1, cout), dtype=torch.float32, device=cur_xyz.device)
-                ext.maxpool_pm_wrapper(y, n, out, 0)
+                ext.maxpool_pm_wrapper(mlp(g.view(Bc * n, c4 + 4)), n, out, 0)
             l_feat.append(out)
-        top = l_feat[-1].view(l_feat[-1].shape[0], -1)                         # (B*M, 512)
+        return self._rcnn_heads(l_feat[-1].view(l_feat[-1].shape[0], -1))       # (B*M, 512)
+
+    def _rcnn_heads(self, top):
+        """the classification and regression heads over the RoI features"""
         kp = self.rcnn_cls.layers[0][0].shape[0]
         if top.shape[1] != kp:                                                  # narrow configurations under PAD128
             top = torch.nn.functional.pad(top, (0, kp - top.shape[1]))
-        if self.rcnn_head1 is not None and top.stride(1) == 1:
-            wt, b, n1 = self.rcnn_head1
-            h = point_layer(top, wt, b, True)
-            hc, hr = h[:, :n1], h[:, n1:]
-            lc, lr = self.rcnn_cls.layers, self.rcnn_reg.layers
-            if (USE_POINT_LAYER and USE_PACKED and len(lc) >= 3 and len(lr) >= 3 and has_entry(ext, "packed_layer_batch_wrapper")
-                    and all(w_.shape[0] % 128 == 0 and w_.shape[1] % 128 == 0 for w_ in (lc[1][0], lr[1][0]))
-                    and hc.shape[1] == lc[1][0].shape[0] and hr.shape[1] == lr[1][0].shape[0] and hc.stride(0) % 4 == 0
-                    and hc.data_ptr() % 16 == 0 and hr.data_ptr() % 16 == 0):
-                # the second layers of the two branches side by side in ONE launch (800 rows: each is a 20-us launch of a few dozen
-                # workgroups on the feature stream); same kernel, same arguments per problem: same bits
-                yc = torch.empty((hc.shape[0], lc[1][0].shape[1]), dtype=torch.float32, device=h.device)
-                yr = torch.empty((hr.shape[0], lr[1][0].shape[1]), dtype=torch.float32, device=h.device)
-                ext.packed_layer_batch_wrapper([(hc, lc[1][0], lc[1][1], lc[1][2], yc, None), (hr, lr[1][0], lr[1][1], lr[1][2], yr, None)])
-                return {"rcnn_cls": self.rcnn_cls(yc, start=2), "rcnn_reg": self.rcnn_reg(yr, start=2)}
-            return {"rcnn_cls": self.rcnn_cls(hc, start=1), "rcnn_reg": self.rcnn_reg(hr, start=1)}
-        return {"rcnn_cls": self.rcnn_cls(top), "rcnn_reg": self.rcnn_reg(top)}
+        if self.rcnn_head1 is None or top.stride(1) != 1:
+            return {"rcnn_cls": self.rcnn_cls(top), "rcnn_reg": self.rcnn_reg(top)}
+        wt, b, n1 = self.rcnn_head1                                             # both first layers as ONE layer of twice the width
+        h = point_layer(top, wt, b, True)
+        hc, hr, start = self._rcnn_heads_second(h[:, :n1], h[:, n1:])
+        return {"rcnn_cls": self.rcnn_cls(hc, start=start), "rcnn_reg": self.rcnn_reg(hr, start=start)}
+
+    def _rcnn_heads_second(self, hc, hr):
+        """the second layers of the two branches side by side in ONE launch (800 rows: each is a 20-us launch of a few dozen workgroups on the
+        feature stream); same kernel, same arguments per problem: same bits.  -> (yc, yr, 2), or (hc, hr, 1) where the shapes do not fit"""
+        ext = pu.pointnet2
+        lc, lr = self.rcnn_cls.layers, self.rcnn_reg.layers
+        if not (USE_POINT_LAYER and USE_PACKED and len(lc) >= 3 and len(lr) >= 3 and has_entry(ext, "packed_layer_batch_wrapper")
+                and all(w_.shape[0] % 128 == 0 and w_.shape[1] % 128 == 0 for w_ in (lc[1][0], lr[1][0]))
+                and hc.shape[1] == lc[1][0].shape[0] and hr.shape[1] == lr[1][0].shape[0] and hc.stride(0) % 4 == 0
+                and hc.data_ptr() % 16 == 0 and hr.data_ptr() % 16 == 0):
+            return hc, hr, 1
+        (wc, bc, relu_c), (wr, br, relu_r) = lc[1], lr[1]
+        yc = torch.empty((hc.shape[0], wc.shape[1]), dtype=torch.float32, device=hc.device)
+        yr = torch.empty((hr.shape[0], wr.shape[1]), dtype=torch.float32, device=hr.device)
+        ext.packed_layer_batch_wrapper([(hc, wc, bc, relu_c, yc, None), (hr, wr, br, relu_r, yr, None)])
+        return yc, yr, 2
 
     __call__ = forward
