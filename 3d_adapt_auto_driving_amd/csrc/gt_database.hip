@@ -33,19 +33,8 @@ __device__ __forceinline__ float4 gt_load_rect(const prcnn_gt_batch &b, const Sc
     float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
     if (c.valid) {
         const float4 p = *(const float4 *)(b.velo + 4 * (c.p0 + c.idx));
-        const float *m = b.calib + 12 * c.s;
         float v[3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            if (c.n == 1) {                      // a (1, 4) . (4, 3) product is a gemv call: two pairs, then their sum
-                v[j] = gemv_row(p.x, p.y, p.z, m[j], m[3 + j], m[6 + j], m[9 + j]);
-                continue;
-            }
-            float a = __fmul_rn(p.x, m[j]);
-            a = __fmaf_rn(p.y, m[3 + j], a);
-            a = __fmaf_rn(p.z, m[6 + j], a);
-            v[j] = __fadd_rn(a, m[9 + j]);
-        }
+        lidar_to_rect_m(b.calib + 12 * c.s, p, c.n == 1, v);   // a (1, 4) . (4, 3) product is a gemv call: two pairs, then their sum
         r = make_float4(v[0], v[1], v[2], p.w);
     }
     return r;

@@ -47,6 +47,23 @@ __device__ __forceinline__ float gemv_row(float x, float y, float z, float m0, f
 {
     return __fadd_rn(__fmaf_rn(x, m0, __fmul_rn(y, m1)), __fmaf_rn(z, m2, m3));
 }
+// kitti_io.Calibration.lidar_to_rect of one raw point with the host's M = np.dot(V2C.T, R0.T), (4, 3) row-major (csrc/gt_database.hip,
+// csrc/road_planes.hip): product, two fused multiply-adds, one add; ``single``: the cloud has ONE point (the gemv form above)
+__device__ __forceinline__ void lidar_to_rect_m(const float *m, const float4 p, bool single, float v[3])
+{
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        if (single) {
+            v[j] = gemv_row(p.x, p.y, p.z, m[j], m[3 + j], m[6 + j], m[9 + j]);
+            continue;
+        }
+        float a = __fmul_rn(p.x, m[j]);
+        a = __fmaf_rn(p.y, m[3 + j], a);
+        a = __fmaf_rn(p.z, m[6 + j], a);
+        v[j] = __fadd_rn(a, m[9 + j]);
+    }
+}
+
 // [p 1] . P2^T, a transposed operand (rect_to_img): the same two pairs without fused operations
 __device__ __forceinline__ float gemv_row_t(float x, float y, float z, float m0, float m1, float m2, float m3)
 {

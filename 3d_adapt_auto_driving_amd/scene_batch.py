@@ -1,4 +1,4 @@
-"""What the ragged-scene data modules share on the host (gt_database.py, stat_norm.py, aug_scene.py, train_input.py; the device side is
+"""What the ragged-scene data modules share on the host (gt_database.py, stat_norm.py, aug_scene.py, train_input.py, road_planes.py; the device side is
 csrc/scene_tiles.hpp and csrc/placement.hpp): a batch of scenes packed back to back with its offsets and 64-point tiles, the
 valid-point filter of the reference's loaders in numpy, and the small box / database / label helpers of object placement.
 """

@@ -919,6 +919,22 @@ int prcnn_optim_update(const unsigned long long *param_addr, const unsigned long
                        const int *chunk_tensor, const long long *chunk_start, int n_tensors, int n_chunks, double lr, double beta1,
                        double beta2, double eps, double wd, const double *work, void *stream);
 
+/* Road-plane estimation for a batch of ragged LiDAR sweeps (csrc/road_planes.hip, road_planes.py): candidates in
+ * the x / z range compacted in point order, RANSAC over host-drawn triples, two least-squares refits, the final inlier count and rms,
+ * all in ONE call with no host read inside.  Device pointers.  pt_off / tile_off (n_scenes + 1) i32 and velo (sum n, 4) f32 as in
+ * prcnn_gt_batch, calib (n_scenes, 12) f32 = np.dot(V2C.T, R0.T); draws (n_scenes, iters, 3) f64 in [0, 1); the range x0 <= x <= x1,
+ * z0 <= z <= z1 in the rect frame; cos_tilt = cos(max tilt).  Work: tile_cnt (sum tiles) i32; cand_n (n_scenes) i32 = M; cand
+ * (sum n, 4) f32 = rect x, y, z, 0 of a scene's candidates from row pt_off[scene]; hyp (n_scenes, iters, PRCNN_RP_HYP) f64 = unit
+ * normal, d, the first point, accepted (1 / 0); part (n_scenes, G, iters) i32 with G = max(1, ceil(max_tiles / PRCNN_RP_GROUP_TILES));
+ * scores (n_scenes, iters) i32 (0 where rejected); p0 (n_scenes, 4) f64; mom (n_scenes, PRCNN_RP_MOMENT_GROUPS, PRCNN_RP_MOM) f64.
+ * out (n_scenes, PRCNN_RP_OUT) f64 = a, b, c, d, rms, M, best hypothesis (-1: fallback), its score, inliers of the final plane,
+ * fallback (0 none, 1 fewer than 3 candidates, 2 no hypothesis accepted, 3 best score below min_inliers): the block the host reads. */
+enum { PRCNN_RP_GROUP_TILES = 16, PRCNN_RP_HYP = 8, PRCNN_RP_MOMENT_GROUPS = 32, PRCNN_RP_MOM = 10, PRCNN_RP_OUT = 10 };
+int prcnn_road_planes(int n_scenes, int max_tiles, int iters, const int *pt_off, const int *tile_off, const float *velo,
+                      const float *calib, const double *draws, double x0, double x1, double z0, double z1, double thresh,
+                      double cos_tilt, int min_inliers, double default_height, int *tile_cnt, int *cand_n, float *cand,
+                      double *hyp, int *part, int *scores, double *p0, double *mom, double *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
