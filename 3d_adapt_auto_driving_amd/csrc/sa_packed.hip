@@ -872,7 +872,9 @@ using namespace prcnn;
 //   rowdxyz  [b * tiles_cap * 64] float4, xyz[point] - new_xyz[centre] of the same rows (w = 0)
 //   tilecloud[b * tiles_cap] i32, cloud of tile t
 //   hdr      [4] u32: [0] = number of tiles, [1] = number of distinct rows (both written by this call)
-// with tiles_cap = ceil(m * nsample / 64) tiles per cloud at most.  Needs m, n <= 65536.
+// with tiles_cap = ceil(m * nsample / 64) tiles per cloud at most.  Needs m <= 15360 centres and n <= 65536 points per cloud (both
+// refused otherwise; rowinfo keeps the point in 16 bits).  tests/row_lists.py restates the list in numpy: the definition every
+// producer is compared with row for row (tests/test_gpu_row_lists.py).
 // limit (b) i32, optional: points k >= limit[cloud] are copies of point k % limit[cloud] (see ball_pack_kernel).
 static int ball_pack_launch(int b, int group, int n, int m, int nsample, const int *idx, const int *limit, const float *xyz,
                             const float *new_xyz, unsigned int *rowinfo, float *rowdxyz, int *tilecloud, unsigned int *hdr, void *stream,

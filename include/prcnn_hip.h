@@ -197,6 +197,8 @@ int prcnn_sa_mlp_fused(int b, int n, int m, int nsample, int c1, int c2, int c3,
  *   hdr      u32 [4]: [0] tiles, [1] distinct rows (device-resident; no host sync)
  *   limit    i32 [b], optional: points k >= limit[cloud] of a cloud are copies of point k % limit[cloud] (the wrap-around
  *            fill of RoI pooling, roipool3d_kernel.cu:152-159); their rows are duplicates as well and are dropped
+ * Every prcnn_ball_pack* entry takes m <= 15360 centres and n <= 65536 points per cloud (rowinfo keeps the point in 16 bits) and
+ * refuses anything larger.
  * prcnn_sa_packed_mlp: layers as prcnn_sa_mlp_fused (c1 = c2 = 128; narrower levels zero-padded by the caller), c3 in
  * {128, 256}; zeroes out[(b*m)][out_col..out_col+c3) and accumulates the per-centre maxima with atomicMax (values are
  * >= 0 after ReLU).  Bit-identical to prcnn_sa_mlp_fused on the same idx.  max_tiles = b * ceil(m*nsample/64). */

@@ -643,15 +643,13 @@ def _pack_rows_by_cloud(pk, b):
     return ntiles, nrows, out
 
 
-@pytest.mark.parametrize("ns1,ns2", [(64, 64), (16, 48)])
-def test_rcnn_roi_geometry_packs_equal_ball_pack(ext, ns1, ns2):
-    """prcnn_rcnn_roi_geometry_packs: the six geometry outputs of prcnn_rcnn_roi_geometry and, out of the same launch, the two row lists
-    exactly as prcnn_ball_pack_ex writes them from idx1 (limit, crep = rep1) and idx2 (rep = rep1, crep = rep2): per cloud the same rows
-    in the same order in the same tiles, relative coordinates bit for bit, the padding rows of a cloud's last tile included."""
+def roi_pack_clouds(ns1):
+    """RoI clouds of the row-list tests (also tests/test_gpu_row_lists.py): (counts of distinct points, xyz (b, 512, 3)) -- the counts that
+    cross the kernel's slot boundaries plus 30 random ones, every fifth cloud on a lattice (ties, coinciding points), one cloud whose
+    points all coincide; the points beyond a cloud's count are wrap-around copies"""
     rng = np.random.default_rng(5 + ns1)
     counts = [1, 2, 7, 33, 60, 64, 65, 100, 127, 128, 129, 200, 300, 511, 512, 512, 50, 90] + [int(c) for c in rng.integers(1, 513, size=30)]
-    b = len(counts)
-    xyz = np.zeros((b, 512, 3), np.float32)
+    xyz = np.zeros((len(counts), 512, 3), np.float32)
     for i, c in enumerate(counts):
         base = (rng.standard_normal((c, 3)) * [1.2, 0.5, 0.6]).astype(np.float32)
         if i % 5 == 0:
@@ -659,6 +657,16 @@ def test_rcnn_roi_geometry_packs_equal_ball_pack(ext, ns1, ns2):
         if i == 16:
             base[:] = base[0]
         xyz[i] = base[np.arange(512) % c]
+    return counts, xyz
+
+
+@pytest.mark.parametrize("ns1,ns2", [(64, 64), (16, 48)])
+def test_rcnn_roi_geometry_packs_equal_ball_pack(ext, ns1, ns2):
+    """prcnn_rcnn_roi_geometry_packs: the six geometry outputs of prcnn_rcnn_roi_geometry and, out of the same launch, the two row lists
+    exactly as prcnn_ball_pack_ex writes them from idx1 (limit, crep = rep1) and idx2 (rep = rep1, crep = rep2): per cloud the same rows
+    in the same order in the same tiles, relative coordinates bit for bit, the padding rows of a cloud's last tile included."""
+    counts, xyz = roi_pack_clouds(ns1)
+    b = len(counts)
     limit = torch.tensor(counts, dtype=torch.int32, device=DEV)
     P = ext.pointnet2
     X = T(xyz)

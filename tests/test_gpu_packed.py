@@ -11,6 +11,7 @@ import torch
 from oracle import ext_cpu
 from conftest import pkg
 from helpers import scenes
+from row_lists import ball_like as ball_like_idx     # the generator shared with the row-list tests
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -18,21 +19,6 @@ DEV = "cuda:0"
 
 def T(a):
     return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def ball_like_idx(rng, b, m, n, ns, mean_cnt):
-    """index rows shaped like a ball query's output: cnt distinct increasing indices, then copies of the first"""
-    idx = np.empty((b, m, ns), np.int32)
-    cnt = np.clip(rng.geometric(1.0 / mean_cnt, (b, m)), 1, ns)
-    cnt[0, 0], cnt[-1, -1] = ns, 1
-    if m > 2:
-        cnt[0, 1] = 1
-    for i in range(b):
-        for c in range(m):
-            k = np.sort(rng.choice(n, cnt[i, c], replace=False))
-            idx[i, c, :cnt[i, c]] = k
-            idx[i, c, cnt[i, c]:] = k[0]
-    return idx, cnt
 
 
 def mlp_params(rng, c3):
