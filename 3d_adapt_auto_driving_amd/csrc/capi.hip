@@ -1,4 +1,4 @@
-// capi.hip -- error reporting and version of libprcnn_hip.so (see include/prcnn_hip.h).
+// capi.hip -- error reporting, version, per-stream scratch and tile-ticket ring of libprcnn_hip.so (see include/prcnn_hip.h).
 #include <cstring>
 #include "common.hpp"
 #include <stdarg.h>
@@ -142,6 +142,31 @@ char *scratch_for(hipStream_t st, size_t bytes, int slot, bool *fresh)
     return s->ptr;
 }
 
+// ---- tile tickets ---------------------------------------------------------------------------
+// A ring of 128 records of 16 words per (device, stream) ([0] draw counter, [1] workgroups done, [2..9] per-XCD draw counters of the
+// kernels that partition their tiles by XCD, common.hpp XcdTickets) (slot 6 of the scratch cache), zeroed when the stream's ring is
+// created (scratch_for's `fresh` flag).  One launch uses one record and leaves it at zero (common.hpp ticket_release: the launch's last
+// workgroup resets it), so nothing is filled in front of a launch -- eagerly or inside a captured hipGraph, whose replays find the
+// record clean as well.  (Round 1 zeroed one word per launch: a 5 us fill kernel in front of each ticketed launch; round 2 one memset
+// per 256 launches and, under capture, a memset node per launch.)  Launches of other streams never touch the ring.
+constexpr unsigned TICKET_RING = 128;
+static std::mutex g_ticket_mu;
+static std::map<std::pair<int, hipStream_t>, unsigned int> g_ticket_next;
+unsigned int *next_ticket(hipStream_t st)
+{
+    bool fresh = false;
+    unsigned int *ring = reinterpret_cast<unsigned int *>(scratch_for(st, 16 * TICKET_RING * sizeof(unsigned int), 6, &fresh));
+    if (!ring) return nullptr;                 // (a first use under capture ends here: the stream needs its warm-up)
+    unsigned int k;
+    {
+        std::lock_guard<std::mutex> lock(g_ticket_mu);
+        k = g_ticket_next[std::make_pair(current_device(), st)]++;
+    }
+    // zeroed whenever the ring's memory is new to this (device, stream) -- first use, or an entry of the scratch table that changed
+    // owner -- not keyed on the launch counter (a ring re-created after an eviction was never zeroed)
+    if (fresh && hipMemsetAsync(ring, 0, 16 * TICKET_RING * sizeof(unsigned int), st) != hipSuccess) return nullptr;
+    return ring + 16 * (k % TICKET_RING);
+}
 
 }  // namespace prcnn
 

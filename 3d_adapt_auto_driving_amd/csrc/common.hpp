@@ -9,6 +9,7 @@
 namespace prcnn {
 
 constexpr int WAVE = 64;
+typedef float f32x16 __attribute__((ext_vector_type(16)));      // the C/D operand of v_mfma_f32_32x32x2_f32: 16 accumulator rows per lane
 
 void set_error(const char *fmt, ...);
 int check_launch(const char *what);
@@ -43,6 +44,18 @@ __device__ __forceinline__ void ticket_release(unsigned int *ticket)
         atomicExch(ticket + 1, 0u);
     }
 }
+// The same for a launch that draws from TWO counters (words 0 and 2 of its record: the two problems of sa_packed_mlp128_kernel)
+__device__ __forceinline__ void ticket_release3(unsigned int *rec)
+{
+    if (atomicAdd(rec + 1, 1u) == gridDim.x * gridDim.y * gridDim.z - 1u) {
+        atomicExch(rec, 0u);
+        atomicExch(rec + 2, 0u);
+        atomicExch(rec + 1, 0u);
+    }
+}
+// The next 16-word ticket record of the stream's ring, at zero (capi.hip, next to scratch_for): one per ticketed launch.  nullptr: the
+// ring could not be set up (the caller reports it in its own words).
+unsigned int *next_ticket(hipStream_t st);
 
 // The same with one draw counter per XCD (words [2..9] of the launch's 16-word ticket record): a workgroup draws from the counter of
 // its own XCD first -- block b runs on XCD b % 8 (observed placement; a different one costs locality, never correctness) -- so that

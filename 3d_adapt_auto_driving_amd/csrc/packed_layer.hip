@@ -22,8 +22,6 @@
 
 namespace prcnn {
 
-unsigned int *next_ticket(hipStream_t st);    // sa_mlp_fused.hip: a zeroed, self-resetting 16-word ticket record of the stream's ring
-
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int PL_ROWS = 64;
 constexpr int PL_LD = 128 + 4;

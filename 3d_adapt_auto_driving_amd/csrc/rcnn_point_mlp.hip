@@ -19,8 +19,6 @@
 
 namespace prcnn {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int PM_C = 128;
 constexpr int PM_ROWS = 64;
 constexpr int PM_LD = PM_C + 4;
@@ -218,8 +216,6 @@ __global__ __launch_bounds__(256, 2) void rows_layer_list_kernel(const float *__
         }
     }
 }
-
-unsigned int *next_ticket(hipStream_t st);    // sa_mlp_fused.hip
 
 // ---- the whole entrance chain over a tile that stays in LDS (round 2, after the stage stamps of csrc/rpn_tail.hip) -----------
 // Per 64-row tile: builder (first xyz_up layer, K = 5, VALU; the tile's 128 RPN features go to the second LDS tile) ->

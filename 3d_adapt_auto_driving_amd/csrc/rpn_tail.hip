@@ -27,7 +27,6 @@
 
 namespace prcnn {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int RT_ROWS = 64;
@@ -536,8 +535,6 @@ __global__ __launch_bounds__(256, 1) void rpn_tail_lin_kernel(const RpnTailArgs 
 }  // namespace prcnn
 
 namespace prcnn {
-unsigned int *next_ticket(hipStream_t st);    // sa_mlp_fused.hip
-
 __global__ __launch_bounds__(256) void fmod_two_pi_selftest_kernel(long n, const float *__restrict__ a, float *__restrict__ mine,
                                                                    float *__restrict__ lib)
 {

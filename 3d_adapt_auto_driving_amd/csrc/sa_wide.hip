@@ -1,6 +1,6 @@
 // sa_wide.hip -- one scale of a set-abstraction level whose layers are wider than the register-resident fused kernels take
 // (RPN SA3 / SA4: 128-196-256, 256-256-512, 256-384-512, pointrcnn/lib/config.py:58-61; the RCNN's GroupAll level 256-256-512,
-// rcnn_net.py:64-92), over the DISTINCT grouped rows (csrc/sa_packed.hip ball_pack), in ONE kernel:
+// rcnn_net.py:64-92), over the DISTINCT grouped rows (csrc/ball_pack.hip), in ONE kernel:
 //
 //   rows of a half tile (32 packed rows)  ->  layer 1 = relu(P[point] + wxyz . (xyz[point] - centre))      (builder, VALU)
 //                                          ->  layer 2 (C1 -> C2)  ->  layer 3 (C2 -> C3) + max over each centre's rows
@@ -158,10 +158,6 @@ __global__ __launch_bounds__(256, 2) void sa_wide_fused_kernel(const SaWideArgs 
 }  // namespace prcnn
 
 using namespace prcnn;
-
-namespace prcnn {
-unsigned int *next_ticket(hipStream_t st);    // sa_mlp_fused.hip
-}
 
 extern "C" int prcnn_sa_wide_fused_supported(int c1, int c2, int c3)
 {

@@ -2,11 +2,10 @@
 // 64-MFMA panel stage of a 32-row unit and the segmented max of a unit's accumulator block.
 // Names the stage macro expects in scope: j / h (lane & 31, lane >> 5), acc (f32x16), SW_LD.
 #pragma once
-#include <hip/hip_runtime.h>
+#include "common.hpp"
 
 namespace prcnn {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int SW_R = 32;            // rows per unit

@@ -184,10 +184,6 @@ __global__ __launch_bounds__(256, 2) void sa_wide3_kernel(const SaWide3Args a)
 
 using namespace prcnn;
 
-namespace prcnn {
-unsigned int *next_ticket(hipStream_t st);    // sa_mlp_fused.hip
-}
-
 static size_t sa_wide3_lds(int c0, int c1, int c2, int c3)
 {
     const int kp0 = c0 / 128, kp1 = c1 / 128, kp2 = c2 / 128;

@@ -92,7 +92,7 @@ __global__ __launch_bounds__(256) void sa_xyz_mlp_kernel(
     }
 }
 
-// ---- the same level over the DISTINCT rows only (prcnn_ball_pack lists; see sa_packed.hip).  lane = one packed row; the
+// ---- the same level over the DISTINCT rows only (prcnn_ball_pack lists; see ball_pack.hip).  lane = one packed row; the
 // wave's 64 rows are one tile of the list.  The relu'd outputs go through LDS so that the pool runs with lane = channel:
 // a serial pass over the tile's rows keeps a running max per channel and flushes it with ONE coalesced atomicMax per centre
 // (outputs are >= 0; the output slice is zeroed by the caller of the kernel).  Per-row arithmetic is identical to

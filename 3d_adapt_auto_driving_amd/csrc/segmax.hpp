@@ -1,10 +1,8 @@
-// segmax.hpp -- segmented max over the rows of a 64-row MFMA accumulator tile (shared by sa_packed.hip and packed_layer.hip).
+// segmax.hpp -- segmented max over the rows of a 64-row MFMA accumulator tile (shared by sa_packed.hip and packed_layer.hip; f32x16: common.hpp).
 #pragma once
 #include "common.hpp"
 
 namespace prcnn {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // Rows held by lane half h of the 32x32 MFMA accumulators, in increasing row order: q = 0..31 ->
 // accumulator q >> 4, register q & 15, row = 32 (q >> 4) + (r & 3) + 8 (r >> 2) + 4 h.

@@ -4,7 +4,7 @@ The image has rocprofv3's --att front end but not its decoder library, so a real
 substitute that answered "where does the time between the MFMAs go".  Two steps:
 
   python profiles/stage_stamps.py build          (in the build container: hipcc)
-      text-instruments COPIES of csrc/rpn_tail.hip and csrc/packed_layer.hip (a STAMP(k) after every barrier / panel stage /
+      text-instruments COPIES of csrc/rpn_tail.hip, csrc/packed_layer.hip and csrc/sa_packed.hip (a STAMP(k) after every barrier / panel stage /
       epilogue; the product sources are not touched), compiles them and links profiles/_exp/libprcnn_hip_stamps.so from the
       product's other objects (profiles/_exp/ is git-ignored but travels with gpurun)
   python profiles/stage_stamps.py tail [grid]    (on the GPU box)   per-stage cycles of rpn_tail_kernel, B = 8 shape
@@ -21,11 +21,13 @@ CSRC = os.path.join(ROOT, "3d_adapt_auto_driving_amd", "csrc")
 EXP = os.path.join(ROOT, "profiles", "_exp")
 LIB = os.path.join(EXP, "libprcnn_hip_stamps.so")
 FLAGS = "--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math".split()
+SP_STAMPS = 16          # stamp slots per wave of sa_packed_mlp128_kernel
 
 
 def _abs_includes(s):
     return (s.replace('#include "common.hpp"', '#include <cstdlib>\n#include "%s/common.hpp"' % CSRC)
              .replace('#include "segmax.hpp"', '#include "%s/segmax.hpp"' % CSRC)
+             .replace('#include "sa_tile.hpp"', '#include "%s/sa_tile.hpp"' % CSRC)
              .replace('#include "mfma_stream.hpp"', '#include "%s/mfma_stream.hpp"' % CSRC)
              .replace('#include "../../include/prcnn_hip.h"', '#include "%s/include/prcnn_hip.h"' % ROOT))
 
@@ -79,29 +81,28 @@ def instrument_layer():
 
 
 def instrument_packed():
+    """a stamp after every stage line of sa_packed_mlp128_kernel's tile loop (each stage is one line there); the names are the lines"""
     s = _abs_includes(open(os.path.join(CSRC, "sa_packed.hip")).read())
     a = s.index("void sa_packed_mlp128_kernel(")
-    b = s.index("// ------------------------------------------------------------------------------------------------ C3 = 256")
-    k = s[a:b]
-    def put(old, new):
-        nonlocal k
-        assert old in k, old[:60]
-        k = k.replace(old, new, 1)
-    put("    for (int served = 0; served < tiles_per_wg && t < tiles; ++served) {\n", "    for (int served = 0; served < tiles_per_wg && t < tiles; ++served) {\n        STAMP(0)\n")
-    put("        __syncthreads();\n        const long t_next = slot[(served + 1) & 1];", "        STAMP(1)\n        __syncthreads();\n        STAMP(2)\n        const long t_next = slot[(served + 1) & 1];")
-    put("#pragma unroll\n            for (int r = 0; r < 16; ++r) {\n                const int row = (r & 3) + 8 * (r >> 2) + 4 * h;\n                Y1[row * PK_LD + 32 * w + j] = fmaxf(acc0[r] + bias2, 0.f);",
-        "            STAMP(3)\n#pragma unroll\n            for (int r = 0; r < 16; ++r) {\n                const int row = (r & 3) + 8 * (r >> 2) + 4 * h;\n                Y1[row * PK_LD + 32 * w + j] = fmaxf(acc0[r] + bias2, 0.f);")
-    put("        if (tid < PK_ROWS && t_next < tiles) dxyz_s[(served + 1) & 1][tid] = dnext;   // ordered before", "        STAMP(4)\n        if (tid < PK_ROWS && t_next < tiles) dxyz_s[(served + 1) & 1][tid] = dnext;   // ordered before")
-    put("   // in flight during layer 3\n        }\n        __syncthreads();\n", "   // in flight during layer 3\n        }\n        __syncthreads();\n        STAMP(5)\n")
-    put("            const int myc = cc[lane], prevc = cc[lane ? lane - 1 : 0];\n            const unsigned long long start = __ballot(lane == 0 || myc != prevc);\n            pk_segmented_max(acc0, acc1, cc, start, h, out, out_stride, out_col + 32 * w + j, bias3);\n        }",
-        "            STAMP(6)\n            const int myc = cc[lane], prevc = cc[lane ? lane - 1 : 0];\n            const unsigned long long start = __ballot(lane == 0 || myc != prevc);\n            pk_segmented_max(acc0, acc1, cc, start, h, out, out_stride, out_col + 32 * w + j, bias3);\n            STAMP(7)\n        }")
-    s = s[:a] + k + s[b:]
-    s = s.replace("constexpr int PK_ROWS = 64;", "__device__ unsigned long long g_sp_trace[1024 * 4 * 8];\n"
-                  "#define STAMP(k) if ((threadIdx.x & 63) == 0 && served == 1 && blockIdx.x < 1024) g_sp_trace[(blockIdx.x * 4 + (threadIdx.x >> 6)) * 8 + (k)] = __builtin_amdgcn_s_memtime();\n"
-                  "constexpr int PK_ROWS = 64;", 1)
+    lo = s.index("    for (int served = 0; served < tiles_per_wg && t < tiles; ++served) {", a)
+    hi = s.index("        t = t_next;", lo)
+    lines = s[lo:hi].split("\n")
+    out, names, k = [lines[0], "        STAMP(0)"], ["start"], 1
+    for ln in lines[1:]:
+        out.append(ln)
+        st = ln.strip()
+        if st.startswith(("__syncthreads();", "sa_pk_build<", "if (t_next < tiles) sa_fetch_rows<", "SA_PANEL2(", "SA_STORE_RELU2(", "sa_pk_pool128(")):
+            out.append("        STAMP(%d)" % k); names.append(st.split(";")[0].split("   //")[0][:44]); k += 1
+    assert 8 <= k <= SP_STAMPS, k
+    s = s[:lo] + "\n".join(out) + s[hi:]
+    anchor = "constexpr int PK_TILES_PER_WG = 8;"
+    assert anchor in s
+    s = s.replace(anchor, "__device__ unsigned long long g_sp_trace[1024 * 4 * %d];\n"
+                  "#define STAMP(k) if ((threadIdx.x & 63) == 0 && served == 1 && blockIdx.x < 1024) g_sp_trace[(blockIdx.x * 4 + (threadIdx.x >> 6)) * %d + (k)] = __builtin_amdgcn_s_memtime();\n"
+                  % (SP_STAMPS, SP_STAMPS) + anchor, 1)
     s += ('\nextern "C" int prcnn_debug_sp_trace(unsigned long long *dst)\n{\n    return (int)hipMemcpyFromSymbol(dst, '
-          'HIP_SYMBOL(prcnn::g_sp_trace), sizeof(unsigned long long) * 1024 * 4 * 8);\n}\n')
-    return s
+          'HIP_SYMBOL(prcnn::g_sp_trace), sizeof(unsigned long long) * 1024 * 4 * %d);\n}\n' % SP_STAMPS)
+    return s, names
 
 
 def build():
@@ -111,11 +112,13 @@ def build():
     open(os.path.join(EXP, "trace_names.txt"), "w").write("\n".join(names))
     objs, done = [], []
     sources = [("rpn_tail", tail)]
-    for name, fn in (("packed_layer", instrument_layer), ("sa_packed", instrument_packed)):
-        try:
-            sources.append((name, fn()))
-        except AssertionError:
-            print("(%s: the source no longer has the round-2 anchors of this tool -- linked uninstrumented)" % name)
+    try:
+        sources.append(("packed_layer", instrument_layer()))
+    except AssertionError:
+        print("(packed_layer: the source no longer has the round-2 anchors of this tool -- linked uninstrumented)")
+    packed, pnames = instrument_packed()
+    sources.append(("sa_packed", packed))
+    open(os.path.join(EXP, "packed_names.txt"), "w").write("\n".join(pnames))
     for name, src in sources:
         done.append(name + ".o")
         path = os.path.join(EXP, name + "_stamps.hip")
@@ -216,16 +219,17 @@ def read_packed(mean):
     pk = X.ball_pack_wrapper(idx, xyz, new_xyz)
     for _ in range(3): X.sa_packed_mlp_wrapper(new_xyz, xyz, P, wx, pk, w2, b2, w3, b3, out, 0)
     torch.cuda.synchronize()
-    buf = np.zeros(1024 * 4 * 8, np.uint64)
+    names = open(os.path.join(EXP, "packed_names.txt")).read().split("\n")
+    K = len(names)
+    buf = np.zeros(1024 * 4 * SP_STAMPS, np.uint64)
     L.prcnn_debug_sp_trace.argtypes = [ctypes.c_void_p]; assert L.prcnn_debug_sp_trace(buf.ctypes.data) == 0
-    tr = buf.reshape(1024, 4, 8).astype(np.int64); ok = tr[:, :, 0] > 0
+    tr = buf.reshape(1024, 4, SP_STAMPS).astype(np.int64)[:, :, :K]; ok = tr[:, :, 0] > 0
     d = np.diff(tr, axis=2)
     print("sa_packed_mlp128_kernel, 800 clouds x 128 centres, ~%.1f distinct rows per centre: %d tiles; second tile of every workgroup, s_memtime cycles per wave\n" % (mean + 1, int(pk.hdr[0])))
-    print("| span | median | p10 | p90 |\n|---|---|---|---|")
-    for k, nm in enumerate(["builder (P rows + affine -> LDS)", "barrier", "next tile's row list + layer 2 MFMAs", "epilogue -> Y1", "prefetch of the next P rows + barrier",
-                            "layer 3 MFMAs", "segmented max + atomics"]):
-        _row(nm, d[:, :, k][ok])
-    _row("tile total", (tr[:, :, 7] - tr[:, :, 0])[ok])
+    print("| up to | median | p10 | p90 |\n|---|---|---|---|")
+    for k in range(K - 1):
+        _row(names[k + 1], d[:, :, k][ok])
+    _row("tile total", (tr[:, :, K - 1] - tr[:, :, 0])[ok])
 
 
 if __name__ == "__main__":

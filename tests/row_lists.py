@@ -1,4 +1,4 @@
-"""The row list of a ball query, as numpy: the DEFINITION every producer is compared with row for row (csrc/sa_packed.hip
+"""The row list of a ball query, as numpy: the DEFINITION every producer is compared with row for row (csrc/ball_pack.hip
 ball_pack_kernel, ball_pack_count_kernel / ball_pack_write_kernel, csrc/roi_geometry.hip roi_pack_out), and seeded generators of
 inputs that satisfy the contracts those kernels rely on.  numpy only: no GPU, no import of the package.
 
@@ -21,7 +21,7 @@ import collections
 import numpy as np
 
 ROWS = 64            # rows per tile
-CHUNK = 64           # centres per workgroup of the two-launch kernels (csrc/sa_packed.hip PK_CH): where tiles meet chunk boundaries
+CHUNK = 64           # centres per workgroup of the two-launch kernels (csrc/ball_pack.hip PK_CH): where tiles meet chunk boundaries
 TWO_LAUNCH_M = 512   # !rep && m >= 512 takes the two-launch kernels
 
 MUTANTS = ("pad_with_last_row", "ignore_limit", "rep_as_prefix", "ignore_crep")
