@@ -14,7 +14,7 @@
 //   layers         v_mfma_f32_32x32x2_f32 over 128-deep panels, k = s on lanes 0-31 and s + 64 on lanes 32-63, panels in
 //                  sequence, then + bias, then ReLU                           (csrc/packed_layer.hip)
 //   score          32 lanes per row, lane l sums k = l, l+32, l+64, l+96 as one fma chain, xor butterfly 16..1, + bias
-//                                                                              (csrc/packed_layer.hip rows_dot_kernel)
+//                                                                              (csrc/packed_valu.hip rows_dot_kernel)
 //
 // One workgroup = 4 waves = a 64-row tile at a time, persistent over tiles (drawn from a ticket counter), ONE workgroup per CU.  Wave w owns
 // output columns 32w .. 32w+31 of every layer; its 128 x 32 weight slice of the NEXT layer is fetched into registers while the

@@ -6,7 +6,7 @@
 // (and 32 + j) of the A operand and column j of the B operand; h picks the k half: at step s the instruction's two k values are s and
 // s + 64.  A lane's four consecutive steps are 16 contiguous bytes of its row: one ds_read_b128 per four MFMAs and row half.
 // C/D layout: column = j, row = (r & 3) + 8 (r >> 2) + 4 h for accumulator register r.
-// The panels, the weight load and the epilogues are macros that expect j and h in scope, like PL_GROUP_MFMA_* (packed_layer.hip) and
+// The panels, the weight load and the epilogues are macros that expect j and h in scope, like PL_STAGE_SIDE (layer_tile.hpp) and
 // RT_STAGE* (mfma_stream.hpp): sa_packed_mlp128_kernel sits at the register ceiling, and its register allocation moves with the form
 // of these blocks (the epilogue as a function: 248 -> 256 VGPRs and 28 bytes of scratch; the weight load as a function: another
 // schedule of the whole kernel).  Their COL argument is pasted unparenthesised on purpose: the address sums then associate as in the

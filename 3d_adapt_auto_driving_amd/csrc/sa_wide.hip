@@ -5,7 +5,7 @@
 //   rows of a half tile (32 packed rows)  ->  layer 1 = relu(P[point] + wxyz . (xyz[point] - centre))      (builder, VALU)
 //                                          ->  layer 2 (C1 -> C2)  ->  layer 3 (C2 -> C3) + max over each centre's rows
 //
-// It replaces three launches per scale (packed_gather_affine, packed_layer, packed_layer_segmax: csrc/packed_layer.hip) whose
+// It replaces three launches per scale (packed_gather_affine: csrc/packed_valu.hip; packed_layer, packed_layer_segmax: csrc/packed_layer.hip) whose
 // activations went through HBM and which, on sparse levels, were each a latency-bound launch for a handful of live tiles.
 // The 32 rows stay in LDS from the builder to the pooling (A1: C1 columns, Y1: C2 columns, 128-column panels of 132-float rows);
 // every (output column block, K panel) pair is one 64-MFMA stage of a wave (32 rows x 32 columns, one accumulator), and each

@@ -711,7 +711,7 @@ def packed_layer_segmax_batch_wrapper(problems):
 
 
 def rows_dot_wrapper(a, wt, bias, out):
-    """out (R, n) = a (R, K) @ wt (K, n) + bias for n <= 4 (a classification head's last layer) -- csrc/packed_layer.hip."""
+    """out (R, n) = a (R, K) @ wt (K, n) + bias for n <= 4 (a classification head's last layer) -- csrc/packed_valu.hip."""
     _chk(torch.float32, wt, bias)
     if a.dim() != 2 or a.stride(1) != 1 or out.stride(1) != 1 or not a.is_cuda:
         raise RuntimeError("pointnet2_cuda: rows_dot expects 2-D float32 CUDA matrices with unit column stride")

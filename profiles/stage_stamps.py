@@ -27,6 +27,7 @@ SP_STAMPS = 16          # stamp slots per wave of sa_packed_mlp128_kernel
 def _abs_includes(s):
     return (s.replace('#include "common.hpp"', '#include <cstdlib>\n#include "%s/common.hpp"' % CSRC)
              .replace('#include "segmax.hpp"', '#include "%s/segmax.hpp"' % CSRC)
+             .replace('#include "layer_tile.hpp"', '#include "%s/layer_tile.hpp"' % CSRC)
              .replace('#include "sa_tile.hpp"', '#include "%s/sa_tile.hpp"' % CSRC)
              .replace('#include "mfma_stream.hpp"', '#include "%s/mfma_stream.hpp"' % CSRC)
              .replace('#include "../../include/prcnn_hip.h"', '#include "%s/include/prcnn_hip.h"' % ROOT))
@@ -58,25 +59,26 @@ def instrument_tail(lin=False):
 
 
 def instrument_layer():
+    """stamps in packed_layer_pipe_kernel: 0 in front of the first loads, then one in front of every panel's drain, behind its barrier and
+    behind its stage; 62 / 63 around the epilogue (the direct one or the staged one)"""
     s = _abs_includes(open(os.path.join(CSRC, "packed_layer.hip")).read())
-    s = s.replace("constexpr int PL_ROWS = 64;", "__device__ unsigned long long g_pl_trace[1024 * 4 * 64];\n"
-                  "#define STAMP(k) if (!SEGMAX && lane == 0 && (blockIdx.x + gridDim.x * blockIdx.y) < 1024) "
-                  "g_pl_trace[((blockIdx.x + gridDim.x * blockIdx.y) * 4 + w) * 64 + (k)] = __builtin_amdgcn_s_memtime();\n"
-                  "constexpr int PL_ROWS = 64;")
-    # (first occurrence only: the 32-row kernel below repeats these lines)
-    s = s.replace("    float wa[64], wb[64];\n    {\n        PL_LOAD_W(wa, 0)", "    float wa[64], wb[64];\n    STAMP(0)\n    {\n        PL_LOAD_W(wa, 0)", 1)
-    s = s.replace("    const int np = K >> 7;\n    for (int p = 0; p < np; ++p) {\n        PL_VM_DRAIN",
-                  "    const int np = K >> 7;\n    int sk = 1;\n    for (int p = 0; p < np; ++p) {\n        STAMP(sk++)\n        PL_VM_DRAIN", 1)
-    s = s.replace("        lds_barrier();                                     // ... and published; the other tile is free\n",
-                  "        lds_barrier();                                     // ... and published; the other tile is free\n        STAMP(sk++)\n")
-    s = s.replace("            PL_STAGE_PREFETCH(T, TN, wa, wb, (p + 1) * 128)\n", "            PL_STAGE_PREFETCH(T, TN, wa, wb, (p + 1) * 128)\n            STAMP(sk++)\n")
-    s = s.replace("            PL_STAGE(T, wa)\n        }\n    }\n", "            PL_STAGE(T, wa)\n            STAMP(sk++)\n        }\n    }\n    STAMP(62)\n")
-    tail = "    pl_epilogue<SEGMAX>(acc0, acc1, tiles, ctr, t, rows, n0, bias, do_relu, out, ldo, rowinfo, tilecloud, m, out_col, n_store);\n}"
-    assert tail in s
-    s = s.replace(tail, tail[:-1] + "    STAMP(63)\n}")
+    lo = s.index("template <bool SEGMAX>\n__global__ __launch_bounds__(256, 2) void packed_layer_pipe_kernel(")
+    hi = s.index("// ---- K >= 256 layers, PERSISTENT", lo)
+    k = s[lo:hi]
+    for old, new in (("    float wa[64], wb[64];\n", "    float wa[64], wb[64];\n    STAMP(0)\n"),
+                     ("    for (int p = 0; p < np; ++p) {\n        PL_VM_DRAIN", "    int sk = 1;\n    for (int p = 0; p < np; ++p) {\n        STAMP(sk++)\n        PL_VM_DRAIN"),
+                     ("the other tile is free\n", "the other tile is free\n        STAMP(sk++)\n"),
+                     ("            PL_STAGE_PREFETCH(T, TN, wa, wb, (p + 1) * 128)\n", "            PL_STAGE_PREFETCH(T, TN, wa, wb, (p + 1) * 128)\n            STAMP(sk++)\n"),
+                     ("            PL_STAGE(T, wa)\n        }\n    }\n", "            PL_STAGE(T, wa)\n            STAMP(sk++)\n        }\n    }\n    STAMP(62)\n"),
+                     ("            return;\n", "            STAMP(63)\n            return;\n"),
+                     ("    pl_epilogue<SEGMAX>(acc0, acc1, tiles, ctr, t, rows, n0, pb);\n}", "    pl_epilogue<SEGMAX>(acc0, acc1, tiles, ctr, t, rows, n0, pb);\n    STAMP(63)\n}")):
+        assert k.count(old) == 1, old
+        k = k.replace(old, new)
+    s = (s[:lo] + "__device__ unsigned long long g_pl_trace[1024 * 4 * 64];\n"
+         "#define STAMP(k) if (!SEGMAX && lane == 0 && (blockIdx.x + gridDim.x * blockIdx.y) < 1024) "
+         "g_pl_trace[((blockIdx.x + gridDim.x * blockIdx.y) * 4 + w) * 64 + (k)] = __builtin_amdgcn_s_memtime();\n" + k + s[hi:])
     s += ('\nextern "C" int prcnn_debug_pl_trace(unsigned long long *dst)\n{\n    return (int)hipMemcpyFromSymbol(dst, '
           'HIP_SYMBOL(prcnn::g_pl_trace), sizeof(unsigned long long) * 1024 * 4 * 64);\n}\n')
-    assert s.count("STAMP(") >= 8
     return s
 
 
@@ -112,10 +114,7 @@ def build():
     open(os.path.join(EXP, "trace_names.txt"), "w").write("\n".join(names))
     objs, done = [], []
     sources = [("rpn_tail", tail)]
-    try:
-        sources.append(("packed_layer", instrument_layer()))
-    except AssertionError:
-        print("(packed_layer: the source no longer has the round-2 anchors of this tool -- linked uninstrumented)")
+    sources.append(("packed_layer", instrument_layer()))
     packed, pnames = instrument_packed()
     sources.append(("sa_packed", packed))
     open(os.path.join(EXP, "packed_names.txt"), "w").write("\n".join(pnames))

@@ -343,6 +343,61 @@ def test_packed_layer_host_row_count_ragged(ext):
         assert torch.equal(out[:R].cpu(), want)
 
 
+_PL_CASES = {}
+
+
+def _pl_case(R, K, N, relu):
+    """one layer problem and its oracle result at full width, computed once per shape and shared (left unchanged) by the cases below"""
+    key = (R, K, N, relu)
+    if key not in _PL_CASES:
+        rng = np.random.default_rng(R + K + N)
+        a = T(rng.standard_normal((R, K)).astype(np.float32))
+        w = T((rng.standard_normal((K, N)) / np.sqrt(K)).astype(np.float32))
+        bias = T(rng.standard_normal(N).astype(np.float32))
+        want = ext_cpu.pointnet2_cpu.packed_layer_batch_wrapper([(a.cpu(), w.cpu(), bias.cpu(), relu, torch.empty((R, N)), None)])[0]
+        _PL_CASES[key] = (a, w, bias, want)
+    return _PL_CASES[key]
+
+
+# (rows, K, N, n_store, relu) and the form the shape reaches by the rule of csrc/packed_layer.hip (thresholds 512 / 512 / 256)
+PL_NARROW = [(130, 128, 256, 130, True),      # one-panel: 3 tiles x 2 column blocks; the second block is partial, ldo = 130: scalar stores
+             (70, 256, 128, 46, False),       # pipe32: K >= 256 and 2 items < 256
+             (16400, 256, 128, 76, True),     # pipe: 257 items, and n_store != N keeps it off persist; staged store
+             (32800, 128, 128, 76, False)]    # stream: K = 128 and 513 items >= 512; staged branch
+PL_BATCHES = {
+    "one-panel x2": [(130, 128, 256, 256, True), (700, 128, 128, 128, False)],          # grid (11, 2, 2): the surplus workgroups exit
+    "pipe32 x2": [(70, 256, 128, 46, False), (200, 512, 256, 256, True)],
+    "one-panel + pipe32 + stream": [(130, 128, 256, 256, True), (70, 256, 128, 128, False), (32800, 128, 128, 128, False)],  # one by one
+}
+
+
+def _pl_run_and_check(ext, cases):
+    probs, outs = [], []
+    for R, K, N, n_store, relu in cases:
+        a, w, bias, want = _pl_case(R, K, N, relu)
+        out = torch.full((R + 1, n_store), float("nan"), device=DEV)         # host-count mode; one row more than needed
+        probs.append((a, w, bias, relu, out[:R], None))
+        outs.append((out, want[:, :n_store]))
+    ext.pointnet2.packed_layer_batch_wrapper(probs)
+    for (R, K, N, n_store, relu), (out, want) in zip(cases, outs):
+        assert torch.isnan(out[R]).all(), (R, K, N, n_store)                # nothing written past the last row
+        assert torch.equal(out[:R].cpu(), want), (R, K, N, n_store, float((out[:R].cpu() - want).abs().max()))
+
+
+@pytest.mark.parametrize("case", PL_NARROW, ids=lambda c: "%dx%dx%d_store%d" % c[:4])
+def test_packed_layer_narrow_store_on_every_staged_form(ext, case):
+    """n_store < N through every form that has a staged row store (16-byte stores where the row layout allows them, else the
+    n_store-limited scalar tail), `out` exactly n_store wide: the oracle's bits, and nothing past the last row."""
+    _pl_run_and_check(ext, [case])
+
+
+@pytest.mark.parametrize("name", list(PL_BATCHES))
+def test_packed_layer_batches_same_form_and_mixed(ext, name):
+    """prcnn_packed_layer_batch: problems on the same batchable form share one launch sized for the largest (different tile counts,
+    column blocks, K and n_store); a mixed batch is launched one by one.  Every output == the oracle, bit for bit."""
+    _pl_run_and_check(ext, PL_BATCHES[name])
+
+
 def test_packed_layer_interp_persistent_forms(ext):
     """prcnn_packed_layer_interp (FP layer 1 over the skip features + the interpolated coarse product in the epilogue) at sizes that take
     the persistent kernels of round 4 -- K = 128: weights resident, rows streamed (625 tiles x 2 column blocks); K >= 256: the panel
