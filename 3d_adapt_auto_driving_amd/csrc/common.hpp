@@ -106,6 +106,13 @@ __device__ __forceinline__ void lds_barrier()
 
 // Workgroups of a persistent (ticket-drawing) MFMA launch: PRCNN_MFMA_GRID, default in capi.hip
 int mfma_grid_cap();
+// ONE launch of rows_layer_kernel<npanel, pro, relu> (rows_layer.hip) over `tiles` 64-row tiles, for the units that chain 128-wide layers
+// out of it: out = act(A0 @ w0 [+ A1 @ w1] + bias), A0 = src0 rows (128 floats at column col0, row stride ld0) or with pro = 1
+// relu(in5 @ wu1 + bu1) of columns 0..4 of src0 (npanel 1 and relu only); npanel = 2 adds A1 = src1 rows.  tilemap / ntiles (both or
+// none): the launch serves tiles tilemap[0 .. *ntiles).  Draws the launch's ticket from the stream's ring; `what` names it in an error.
+int rows_layer_launch(int npanel, int pro, bool relu, long tiles, const float *src0, int ld0, int col0, const float *src1, int ld1, int col1,
+                      const float *wu1, const float *bu1, const float *w0, const float *w1, const float *bias, float *out, const int *tilemap,
+                      const unsigned int *ntiles, hipStream_t st, const char *what);
 
 static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 

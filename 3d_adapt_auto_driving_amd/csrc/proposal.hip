@@ -15,6 +15,7 @@
 // No host synchronisation anywhere.
 #include "common.hpp"
 #include "rbox_iou.hpp"
+#include "rpn_decode.hpp"
 #include <stdlib.h>
 #include <math.h>
 
@@ -37,7 +38,7 @@ __device__ __forceinline__ int argmax_row(const float *p, int n)
     int best = 0;
     float bv = p[0];
     for (int i = 1; i < n; ++i)                    // first maximum; a NaN counts as the largest value (torch.argmax)
-        if (p[i] > bv || (p[i] != p[i] && bv == bv)) { bv = p[i]; best = i; }
+        if (RD_ARGMAX_TAKES(p[i], bv)) { bv = p[i]; best = i; }
     return best;
 }
 
@@ -60,13 +61,12 @@ __global__ __launch_bounds__(256) void rpn_decode_kernel(long total, DecodeCfg c
     const float *p = xyz + i * 3;
     const int nb = c.nbin;
     const int xb = argmax_row(r, nb), zb = argmax_row(r + nb, nb);
-    const float half_bin = c.loc_bin_size / 2;
-    float px = __fsub_rn(__fadd_rn(__fmul_rn((float)xb, c.loc_bin_size), half_bin), c.loc_scope);
-    float pz = __fsub_rn(__fadd_rn(__fmul_rn((float)zb, c.loc_bin_size), half_bin), c.loc_scope);
+    float px = rd_bin_centre(xb, c.loc_bin_size, c.loc_scope);
+    float pz = rd_bin_centre(zb, c.loc_bin_size, c.loc_scope);
     int cur = 2 * nb;
     if (c.xz_fine) {
-        px = __fadd_rn(px, __fmul_rn(r[2 * nb + xb], c.loc_bin_size));
-        pz = __fadd_rn(pz, __fmul_rn(r[3 * nb + zb], c.loc_bin_size));
+        px = rd_add_residual(px, r[2 * nb + xb], c.loc_bin_size);
+        pz = rd_add_residual(pz, r[3 * nb + zb], c.loc_bin_size);
         cur = 4 * nb;
     }
     float py = __fadd_rn(p[1], r[cur]);
@@ -79,9 +79,9 @@ __global__ __launch_bounds__(256) void rpn_decode_kernel(long total, DecodeCfg c
     float ry = torch_remainder(__fadd_rn(__fmul_rn((float)rb, apc), __fmul_rn(res_norm, apc_half)), two_pi);
     if (ry > pi) ry = __fsub_rn(ry, two_pi);
     cur += 2 * c.num_head_bin;
-    const float h = __fadd_rn(__fmul_rn(r[cur], c.anchor[0]), c.anchor[0]);
-    const float w = __fadd_rn(__fmul_rn(r[cur + 1], c.anchor[1]), c.anchor[1]);
-    const float l = __fadd_rn(__fmul_rn(r[cur + 2], c.anchor[2]), c.anchor[2]);
+    const float h = rd_anchor_size(r[cur], c.anchor[0]);
+    const float w = rd_anchor_size(r[cur + 1], c.anchor[1]);
+    const float l = rd_anchor_size(r[cur + 2], c.anchor[2]);
     float *o = boxes + i * 7;
     o[0] = __fadd_rn(px, p[0]);
     o[1] = __fadd_rn(py, h / 2);
@@ -301,17 +301,13 @@ __device__ __forceinline__ void rcnn_decode_box(const RcnnCfg &c, const float *_
 {
     const int nb = c.nbin;
     const int xb = argmax_row(r, nb), zb = argmax_row(r + nb, nb);
-    const float half_bin = c.loc_bin_size / 2;
-    float px = __fsub_rn(__fadd_rn(__fmul_rn((float)xb, c.loc_bin_size), half_bin), c.loc_scope);
-    float pz = __fsub_rn(__fadd_rn(__fmul_rn((float)zb, c.loc_bin_size), half_bin), c.loc_scope);
-    px = __fadd_rn(px, __fmul_rn(r[2 * nb + xb], c.loc_bin_size));      // get_xz_fine = True
-    pz = __fadd_rn(pz, __fmul_rn(r[3 * nb + zb], c.loc_bin_size));
+    const float px = rd_add_residual(rd_bin_centre(xb, c.loc_bin_size, c.loc_scope), r[2 * nb + xb], c.loc_bin_size);      // get_xz_fine = True
+    const float pz = rd_add_residual(rd_bin_centre(zb, c.loc_bin_size, c.loc_scope), r[3 * nb + zb], c.loc_bin_size);
     int cur = 4 * nb;
     float py;
     if (c.y_by_bin) {
         const int yb = argmax_row(r + cur, c.nbin_y);
-        const float y_res = __fmul_rn(r[cur + c.nbin_y + yb], c.loc_y_bin_size);
-        py = __fadd_rn(__fsub_rn(__fadd_rn(__fmul_rn((float)yb, c.loc_y_bin_size), c.loc_y_bin_size / 2), c.loc_y_scope), y_res);
+        py = rd_add_residual(rd_bin_centre(yb, c.loc_y_bin_size, c.loc_y_scope), r[cur + c.nbin_y + yb], c.loc_y_bin_size);
         py = __fadd_rn(py, roi[1]);
         cur += 2 * c.nbin_y;
     } else {
@@ -325,9 +321,9 @@ __device__ __forceinline__ void rcnn_decode_box(const RcnnCfg &c, const float *_
     const float apc_half = (float)(((M_PI / 2) / c.num_head_bin) / 2.0);
     float ry = __fsub_rn(__fadd_rn(__fadd_rn(__fmul_rn((float)rb, apc), apc_half), __fmul_rn(res_norm, apc_half)), (float)(M_PI / 4));
     cur += 2 * c.num_head_bin;
-    const float h = __fadd_rn(__fmul_rn(r[cur], c.anchor[0]), c.anchor[0]);
-    const float w = __fadd_rn(__fmul_rn(r[cur + 1], c.anchor[1]), c.anchor[1]);
-    const float l = __fadd_rn(__fmul_rn(r[cur + 2], c.anchor[2]), c.anchor[2]);
+    const float h = rd_anchor_size(r[cur], c.anchor[0]);
+    const float w = rd_anchor_size(r[cur + 1], c.anchor[1]);
+    const float l = rd_anchor_size(r[cur + 2], c.anchor[2]);
     // rotate (px, pz) by -roi_ry back to the scene frame (rotate_pc_along_y_torch with -ry), add the RoI centre
     const float roi_ry = roi[6];
     const float cosa = cosf(-roi_ry), sina = sinf(-roi_ry);

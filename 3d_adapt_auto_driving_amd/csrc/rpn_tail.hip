@@ -19,18 +19,13 @@
 // One workgroup = 4 waves = a 64-row tile at a time, persistent over tiles (drawn from a ticket counter), ONE workgroup per CU.  Wave w owns
 // output columns 32w .. 32w+31 of every layer; its 128 x 32 weight slice of the NEXT layer is fetched into registers while the
 // MFMAs of the current one run (two register sets, six panel stages per tile, so the roles repeat tile after tile).
-#include <hip/hip_runtime.h>
-
-#include "common.hpp"
+#include <stdlib.h>
+#define RPN_DECODE_SELFTEST
 #include "mfma_stream.hpp"
-#include "../../include/prcnn_hip.h"
+#include "rpn_decode.hpp"
 
 namespace prcnn {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int RT_ROWS = 64;
-constexpr int RT_LD = 128 + 4;
 #ifndef RT_IROWS
 #define RT_IROWS 4                  // rows a wave interpolates per round (3 x RT_IROWS 1 KB gathers in flight per wave)
 #endif
@@ -55,54 +50,29 @@ struct RpnTailArgs {
     float loc_scope, loc_bin_size, anchor[3];
 };
 
-// fmodf(a, (float)(2 pi)) WITHOUT the library's loop (the decode below rides inside a hand-scheduled MFMA stage: no control flow).
-// The remainder of two floats is exact in f32's own format, so it can be taken in f64: three reduction steps modulo b 2^80, b 2^40
-// and b (b = the f32 value of 2 pi) -- each one q = trunc(r * (1 / B)), r = fma(-q, B, r): q < 2^46 is an exact integer that misses the
-// true quotient by at most one, the fma's true result is a multiple of B's last bit below 2 B and therefore exact, and every step
-// keeps r congruent to a modulo b -- then two corrective steps into [0, b), a's sign put back (a zero remainder takes it too, as
-// fmod's does).  inf -> NaN and NaN -> NaN as fmodf.  Checked against fmodf in tests/test_gpu_packed.py through the fused decode:
-// huge quotients up to 3e38, negatives, +-0, denormals, inf, NaN.
-__device__ __forceinline__ float fmod_two_pi(float a)
-{
-    constexpr double B0 = (double)(float)(2.0 * M_PI), B1 = B0 * 1099511627776.0 /* 2^40 */, B2 = B1 * 1099511627776.0;
-    constexpr double I0 = 1.0 / B0, I1 = 1.0 / B1, I2 = 1.0 / B2;
-    double r = __builtin_fabs((double)a);
-    r = __builtin_fma(-__builtin_trunc(r * I2), B2, r);
-    r = __builtin_fma(-__builtin_trunc(r * I1), B1, r);
-    r = __builtin_fma(-__builtin_trunc(r * I0), B0, r);
-    r = r < 0.0 ? r + B0 : r;
-    r = r < 0.0 ? r + B0 : r;
-    r = r >= B0 ? r - B0 : r;
-    r = r >= B0 ? r - B0 : r;
-    return __builtin_copysignf((float)r, a);
-}
-
-__global__ __launch_bounds__(256, 1) void rpn_tail_kernel(const RpnTailArgs a)
-{
-    // T0 / T1: the working tiles of the layer chain; X0 / X1: the two 128-column panels of the interpolated input tile.  The input
-    // of tile t+1 is built WHILE tile t is in its last four stages, a few instructions behind every k-group's first MFMAs
-    // (RT_STAGE_HOOK): as a phase of its own the interpolation was 6.6k of a 69k-cycle tile, and a second workgroup on the CU
-    // does not hide it (profiles/r02_stage_stamps.md) -- so ONE workgroup per CU, four tiles of LDS, up to 512 registers.
-    __shared__ float T0[RT_ROWS * RT_LD];
-    __shared__ float T1[RT_ROWS * RT_LD];
-    __shared__ float X0[RT_ROWS * RT_LD];
-    __shared__ float X1[RT_ROWS * RT_LD];
-    __shared__ unsigned int slot[2];
-    const int tid = threadIdx.x, lane = tid & 63, j = lane & 31, h = lane >> 5;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int chunk = tid & 31, r0 = tid >> 5;
-    const long tiles = (a.rows + RT_ROWS - 1) / RT_ROWS;
-    const unsigned int lane_off = ((unsigned int)(64 * h) * 128u + (unsigned int)(32 * w + j)) * 4u;
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)a.wcat, 0, 768 * 128 * 4, 0x00020000);
-    const float wd0 = a.wc2[j], wd1 = a.wc2[j + 32], wd2 = a.wc2[j + 64], wd3 = a.wc2[j + 96], bd = a.bc2[0];
-    const f32x4 *known4 = reinterpret_cast<const f32x4 *>(a.known);
-    const float bias1 = a.bcat[32 * w + j], bias2 = a.bcat[128 + 32 * w + j], biasc = a.bcat[256 + 32 * w + j],
-                biasr1 = a.bcat[384 + 32 * w + j], biasr2 = a.bcat[512 + 32 * w + j];
-
-    // neighbour indices / weights / cloud of the 16 rows this wave interpolates in tile `tt`: one coalesced load each
-    // (lane l < 48 holds element l of the 16 x 3 block, lane 3q the cloud of row q)
-    int nx_i, nx_cloud;
-    float nx_w;
+// ---- what the two kernels share ------------------------------------------------------------------------------------------------------
+// The prologue: T0 / T1: the working tiles of the layer chain; X0 / X1: the input panels (rpn_tail_kernel: the two 128-column panels of
+// the interpolated input tile; rpn_tail_lin_kernel: the running tile's and the next one's, alternating); the lane's ids; the weight
+// buffer of WROWS k-rows; the score layer's weights; the next tile's neighbour record.
+#define RT_TAIL_PROLOGUE(WROWS)                                                                           \
+    __shared__ float T0[RT_ROWS * RT_LD];                                                                 \
+    __shared__ float T1[RT_ROWS * RT_LD];                                                                 \
+    __shared__ float X0[RT_ROWS * RT_LD];                                                                 \
+    __shared__ float X1[RT_ROWS * RT_LD];                                                                 \
+    __shared__ unsigned int slot[2];                                                                      \
+    const int tid = threadIdx.x, lane = tid & 63, j = lane & 31, h = lane >> 5;                           \
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);                                               \
+    const int chunk = tid & 31, r0 = tid >> 5;                                                            \
+    const long tiles = (a.rows + RT_ROWS - 1) / RT_ROWS;                                                  \
+    const unsigned int lane_off = RT_LANE_OFF(32 * w + j);                                             \
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)a.wcat, 0, (WROWS) * 128 * 4, 0x00020000); \
+    const float wd0 = a.wc2[j], wd1 = a.wc2[j + 32], wd2 = a.wc2[j + 64], wd3 = a.wc2[j + 96], bd = a.bc2[0]; \
+    const f32x4 *known4 = reinterpret_cast<const f32x4 *>(a.known);                                       \
+    int nx_i, nx_cloud;                                                                                   \
+    float nx_w;                                                                                           \
+    f32x4 co[4];          /* a tile's rows on their way out, four at a time: LDS -> registers -> 512-byte rows */
+// neighbour indices / weights / cloud of the 16 rows this wave interpolates in tile `tt`: one coalesced load each
+// (lane l < 48 holds element l of the 16 x 3 block, lane 3q the cloud of row q)
 #define RT_FETCH_IDX(tt)                                                                                  \
     {                                                                                                     \
         long ge = (tt) * RT_ROWS + 16 * w + lane / 3;                                                     \
@@ -112,6 +82,60 @@ __global__ __launch_bounds__(256, 1) void rpn_tail_kernel(const RpnTailArgs a)
         nx_w = lane < 48 ? a.weight[el] : 0.f;                                                            \
         nx_cloud = (int)(ge / a.n);                                                                       \
     }
+// side work: rows of tile TT leave LDS tile T for `dst` (row stride ld), four in k-groups 1 -> 3, four in 4 -> 6
+#define RT_ROWS_OUT(g, TT, T, dst, ld, live)                                                              \
+    if ((g) == 1 || (g) == 4) {                                                                       \
+        _Pragma("unroll") for (int i = 0; i < 4; ++i) co[i] = *reinterpret_cast<const f32x4 *>((T) + (r0 + 8 * (i + ((g) == 4 ? 4 : 0))) * RT_LD + 4 * chunk); \
+    } else if ((g) == 3 || (g) == 6) {                                                                \
+        _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                               \
+            const unsigned int gr = (unsigned int)(TT) * RT_ROWS + r0 + 8 * (i + ((g) == 6 ? 4 : 0)); \
+            if ((live) && gr < (unsigned int)a.rows) *reinterpret_cast<f32x4 *>((dst) + (gr * (unsigned int)(ld) + 4u * chunk)) = co[i]; \
+        }                                                                                             \
+    }
+// side work: the score = cls layer 2, a 128-long dot product per row over the cls hidden rows in T0 (the stage reads T1): 8 rows per
+// half-wave pass, the 8 passes side by side -- 5 rounds of 8 independent lane exchanges instead of 8 dependent chains of 5 (same
+// additions per row, in the same order) -- one piece per k-group; keeps float sd[8] of the caller
+#define RT_SCORE(g)                                                                                       \
+        if ((g) == 4) {                                                                                   \
+            _Pragma("unroll") for (int p = 0; p < 8; ++p) {                                               \
+                const float *ar = T0 + (r0 + 8 * p) * RT_LD + j;                                          \
+                float v = fmaf(ar[0], wd0, 0.f);                                                          \
+                v = fmaf(ar[32], wd1, v);                                                                 \
+                v = fmaf(ar[64], wd2, v);                                                                 \
+                sd[p] = fmaf(ar[96], wd3, v);                                                             \
+            }                                                                                             \
+        } else if ((g) >= 5 && (g) <= 9) {                                                                \
+            float o[8];                                                                                   \
+            _Pragma("unroll") for (int p = 0; p < 8; ++p) o[p] = __shfl_xor(sd[p], 16 >> ((g) - 5), 32);  \
+            _Pragma("unroll") for (int p = 0; p < 8; ++p) sd[p] = __fadd_rn(sd[p], o[p]);                 \
+        } else if ((g) == 14) {                                                                           \
+            _Pragma("unroll") for (int p = 0; p < 8; ++p) {                                               \
+                const unsigned int gr = (unsigned int)t * RT_ROWS + r0 + 8 * p;                           \
+                if (j == 0 && gr < (unsigned int)a.rows) a.cls[gr] = __fadd_rn(sd[p], bd);                \
+            }                                                                                             \
+        }
+// the last tile's regression rows (tile tp, in T1): nobody's first stage carries them out
+#define RT_LAST_REG_ROWS                                                                                  \
+    if (4 * chunk < a.n_reg) {                                                                            \
+        _Pragma("unroll") for (int i = 0; i < 8; ++i) {                                                   \
+            const int row = r0 + 8 * i;                                                                   \
+            const unsigned int g = (unsigned int)tp * RT_ROWS + row;                                      \
+            if (g < (unsigned int)a.rows)                                                                 \
+                *reinterpret_cast<f32x4 *>(a.reg + (g * (unsigned int)a.n_reg + 4u * chunk)) =            \
+                    *reinterpret_cast<const f32x4 *>(T1 + row * RT_LD + 4 * chunk);                       \
+        }                                                                                                 \
+    }
+
+__global__ __launch_bounds__(256, 1) void rpn_tail_kernel(const RpnTailArgs a)
+{
+    // T0 / T1: the working tiles of the layer chain; X0 / X1: the two 128-column panels of the interpolated input tile.  The input
+    // of tile t+1 is built WHILE tile t is in its last four stages, a few instructions behind every k-group's first MFMAs
+    // (RT_STAGE_HOOK): as a phase of its own the interpolation was 6.6k of a 69k-cycle tile, and a second workgroup on the CU
+    // does not hide it (profiles/r02_stage_stamps.md) -- so ONE workgroup per CU, four tiles of LDS, up to 512 registers.
+    RT_TAIL_PROLOGUE(768)
+    const float bias1 = a.bcat[32 * w + j], bias2 = a.bcat[128 + 32 * w + j], biasc = a.bcat[256 + 32 * w + j],
+                biasr1 = a.bcat[384 + 32 * w + j], biasr2 = a.bcat[512 + 32 * w + j];
+
     // one round of the interpolation = RT_IROWS rows of this wave: a lane owns one float4 of the 256-wide row, so every
     // neighbour row is one coalesced 1 KB read; ISSUE sends the 3 x RT_IROWS gathers, ROW finishes one row into X0 | X1
     f32x4 f[RT_IROWS][3];
@@ -143,16 +167,6 @@ __global__ __launch_bounds__(256, 1) void rpn_tail_kernel(const RpnTailArgs a)
 #define RT_SIDE1(g) RT_SIDE(RT_IROWS, g)
 #define RT_SIDE2(g) RT_SIDE(2 * RT_IROWS, g)
 #define RT_SIDE3(g) RT_SIDE(3 * RT_IROWS, g)
-    f32x4 co[4];                                           // a tile's rows on their way out, four at a time: LDS -> registers -> 512-byte rows
-#define RT_ROWS_OUT(g, TT, T, dst, ld, live)                                                              \
-    if ((g) == 1 || (g) == 4) {                                                                       \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i) co[i] = *reinterpret_cast<const f32x4 *>((T) + (r0 + 8 * (i + ((g) == 4 ? 4 : 0))) * RT_LD + 4 * chunk); \
-    } else if ((g) == 3 || (g) == 6) {                                                                \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                               \
-            const unsigned int gr = (unsigned int)(TT) * RT_ROWS + r0 + 8 * (i + ((g) == 6 ? 4 : 0)); \
-            if ((live) && gr < (unsigned int)a.rows) *reinterpret_cast<f32x4 *>((dst) + (gr * (unsigned int)(ld) + 4u * chunk)) = co[i]; \
-        }                                                                                             \
-    }
     static_assert(RT_IROWS == 4, "four stages carry four rounds of four rows");
 
     // Tiles come from a ticket counter, not a static stride: the step runs this kernel next to other streams' kernels
@@ -203,30 +217,9 @@ __global__ __launch_bounds__(256, 1) void rpn_tail_kernel(const RpnTailArgs a)
         RT_EPILOGUE(T0, biasc, true)
         lds_barrier();
         // ---- reg layer 1 (wa) while reg layer 2 (wb) comes in.  Side: round 2 of the next input, and the score = cls layer 2, a
-        //      128-long dot product per row over the cls hidden rows in T0 (this stage reads T1): 8 rows per half-wave pass, the 8
-        //      passes side by side -- 5 rounds of 8 independent lane exchanges instead of 8 dependent chains of 5 (same additions
-        //      per row, in the same order) -- one piece per k-group
+        //      128-long dot product per row over the cls hidden rows in T0 (RT_SCORE)
         RT_VM_DRAIN
         float sd[8];
-#define RT_SCORE(g)                                                                                       \
-        if ((g) == 4) {                                                                                   \
-            _Pragma("unroll") for (int p = 0; p < 8; ++p) {                                               \
-                const float *ar = T0 + (r0 + 8 * p) * RT_LD + j;                                          \
-                float v = fmaf(ar[0], wd0, 0.f);                                                          \
-                v = fmaf(ar[32], wd1, v);                                                                 \
-                v = fmaf(ar[64], wd2, v);                                                                 \
-                sd[p] = fmaf(ar[96], wd3, v);                                                             \
-            }                                                                                             \
-        } else if ((g) >= 5 && (g) <= 9) {                                                                \
-            float o[8];                                                                                   \
-            _Pragma("unroll") for (int p = 0; p < 8; ++p) o[p] = __shfl_xor(sd[p], 16 >> ((g) - 5), 32);  \
-            _Pragma("unroll") for (int p = 0; p < 8; ++p) sd[p] = __fadd_rn(sd[p], o[p]);                 \
-        } else if ((g) == 14) {                                                                           \
-            _Pragma("unroll") for (int p = 0; p < 8; ++p) {                                               \
-                const unsigned int gr = (unsigned int)t * RT_ROWS + r0 + 8 * p;                           \
-                if (j == 0 && gr < (unsigned int)a.rows) a.cls[gr] = __fadd_rn(sd[p], bd);                \
-            }                                                                                             \
-        }
 #define RT_SIDE2S(g) RT_SIDE2(g) RT_SCORE(g)
         RT_STAGE_HOOK(T1, wa, wb, rs, 640, true, RT_SIDE2S)
         lds_barrier();                                         // every wave has read the cls hidden rows
@@ -240,18 +233,9 @@ __global__ __launch_bounds__(256, 1) void rpn_tail_kernel(const RpnTailArgs a)
         t = tn;                                                // (the barrier at the top of the loop publishes T1 and X0 | X1)
         last = true;
     }
-    if (last) {                                                // the last tile's regression rows
+    if (last) {
         lds_barrier();
-        if (4 * chunk < a.n_reg) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const int row = r0 + 8 * i;
-                const unsigned int g = (unsigned int)tp * RT_ROWS + row;
-                if (g < (unsigned int)a.rows)
-                    *reinterpret_cast<f32x4 *>(a.reg + (g * (unsigned int)a.n_reg + 4u * chunk)) =
-                        *reinterpret_cast<const f32x4 *>(T1 + row * RT_LD + 4 * chunk);
-            }
-        }
+        RT_LAST_REG_ROWS
     }
     if (tid == 0) ticket_release(a.ticket);          // the launch's last workgroup zeroes the counter for the word's next user
 }
@@ -267,47 +251,27 @@ __global__ __launch_bounds__(256, 1) void rpn_tail_kernel(const RpnTailArgs a)
 // A 128-wide row is 32 float4 lanes: a wave interpolates TWO rows per gather instruction (lanes 0-31 / 32-63), 8 such sets per tile;
 // the next tile's input is built behind the MFMAs of all four stages into the input panel the running tile does not use (X0 / X1
 // alternate).
-// DECODE (round 5): the regression head's 76 outputs of a row are decoded where they stand in LDS (tile T1) -- arg-max over the
-// 12 x bins / 12 z bins / 12 heading bins, residual look-ups, anchor sizes: decode_bbox_target of lib/utils/bbox_transform.py:24-121 with
-// get_xz_fine, then proposal_layer.py:31's y shift, in rpn_decode_kernel's f32 operation order (csrc/proposal.hip) -- and the 7-float box
-// leaves instead of the 304-byte row: the 80 MB `reg` tensor of a 16-scene launch and the kernel that read it back with one lane per
-// row (537 MB of HBM traffic for 85 MB of algorithmic bytes) are gone.  Four lanes per row (x | z | heading | y + sizes),
-// 16 rows per wave, spread over four k-groups of the NEXT tile's first stage like the row stores it replaces; no control flow.
-// The layout is the shipped one only (12 + 12 + 12 + 12 + 1 + 12 + 12 + 3 = 76 channels: every cfgs/*.yaml); other layouts keep `reg`.
-constexpr int RD_NB = 12;           // per_loc_bin_num = 2 * int(LOC_SCOPE / LOC_BIN_SIZE) = 2 * int(3.0 / 0.5), = NUM_HEAD_BIN
+// DECODE (round 5): the regression rows are decoded where they stand in LDS (csrc/rpn_decode.hpp, the RL_DEC_* blocks) and the 7-float
+// box leaves instead of the 304-byte row: the 80 MB `reg` tensor of a 16-scene launch and the kernel that read it back with one lane per
+// row (537 MB of HBM traffic for 85 MB of algorithmic bytes) are gone.
 // NARROW (round 5, 64 < n_reg <= 80: the 76 channels of the shipped configurations): the last stage computes 80 columns instead of a
 // zero-padded 128 -- until then 52 of its 128 columns (10 % of the kernel's MFMAs) multiplied padding.  Columns 0..63 = two 32-column
 // blocks x two 32-row blocks, ONE block per wave (v_mfma_f32_32x32x2_f32, the k order of every other layer: the same bits as
 // before); columns 64..79 = a 16-column block, 16 rows per wave, on v_mfma_f32_16x16x4_f32 -- bitwise a chain of fused multiply-adds
 // too (profiles/mfma16_probe.hip: 0 of 51 200 outputs differ), step s = 0..31 over k = s, 32 + s, 64 + s, 96 + s in that order
 // (oracle/mlp_oracle.c orc_rows_layer_mfma16).  96 MFMA issues of 64 / 32 cycles per wave instead of 128 of 64: 5120 cycles, not 8192.
-typedef float f32x4v __attribute__((ext_vector_type(4)));
 template <bool DECODE, bool NARROW>
 __global__ __launch_bounds__(256, 1) void rpn_tail_lin_kernel(const RpnTailArgs a)
 {
-    __shared__ float T0[RT_ROWS * RT_LD];
-    __shared__ float T1[RT_ROWS * RT_LD];
-    __shared__ float X0[RT_ROWS * RT_LD];
-    __shared__ float X1[RT_ROWS * RT_LD];
-    __shared__ unsigned int slot[2];
-    const int tid = threadIdx.x, lane = tid & 63, j = lane & 31, h = lane >> 5;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int chunk = tid & 31, r0 = tid >> 5;
-    const long tiles = (a.rows + RT_ROWS - 1) / RT_ROWS;
-    const unsigned int lane_off = ((unsigned int)(64 * h) * 128u + (unsigned int)(32 * w + j)) * 4u;
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)a.wcat, 0, 512 * 128 * 4, 0x00020000);
-    const float wd0 = a.wc2[j], wd1 = a.wc2[j + 32], wd2 = a.wc2[j + 64], wd3 = a.wc2[j + 96], bd = a.bc2[0];
-    const f32x4 *known4 = reinterpret_cast<const f32x4 *>(a.known);       // G (b, m, 128)
+    RT_TAIL_PROLOGUE(512)                                  // known4: G (b, m, 128)
     const f32x4 bias1v = *reinterpret_cast<const f32x4 *>(a.bcat + 4 * j);
     const float bias2 = a.bcat[128 + 32 * w + j], biasc = a.bcat[256 + 32 * w + j], biasr1 = a.bcat[384 + 32 * w + j],
                 biasr2 = a.bcat[512 + 32 * w + j];
     // NARROW last stage: wave w = 32 x 32 block (row block w & 1, column block w >> 1) + rows 16 w .. 16 w + 15 of the 16-column block
     const int nrb = w & 1, ncb = w >> 1;
-    const unsigned int lane_off_n = ((unsigned int)(64 * h) * 128u + (unsigned int)(32 * ncb + j)) * 4u;          // k = s + 64 h, column 32 ncb + j
+    const unsigned int lane_off_n = RT_LANE_OFF(32 * ncb + j);                                                 // k = s + 64 h, column 32 ncb + j
     const unsigned int lane_off_x = ((unsigned int)(32 * (lane >> 4)) * 128u + (unsigned int)(64 + (lane & 15))) * 4u;   // k = s + 32 (lane / 16), column 64 + lane % 16
     const float biasn = a.bcat[512 + 32 * ncb + j], biasx = a.bcat[512 + 64 + (lane & 15)];
-    int nx_i, nx_cloud;
-    float nx_w;
     f32x4 fl[2][3];
     // set s of a tile = rows 16 w + 2 s (lanes 0-31) and 16 w + 2 s + 1 (lanes 32-63) of this wave
 #define RL_ISSUE(sl, s)                                                                                   \
@@ -332,65 +296,7 @@ __global__ __launch_bounds__(256, 1) void rpn_tail_lin_kernel(const RpnTailArgs 
     if ((g) == (gi)) { RL_ISSUE(0, 2 * (r)) RL_ISSUE(1, 2 * (r) + 1) }                                    \
     else if ((g) == (gf)) { RL_ROW(0, 2 * (r), Xn) }                                                      \
     else if ((g) == (gf) + 1) { RL_ROW(1, 2 * (r) + 1, Xn) }
-    f32x4 co[4];
-    // ---- DECODE: lane = (row 16 w + lane / 4, part lane % 4); part 0: x, 1: z, 2: heading, 3: y + sizes
-    const int dpart = lane & 3;
-    const float *drow = T1 + (16 * w + (lane >> 2)) * RT_LD;
-    const int dstart = dpart == 0 ? 0 : dpart == 1 ? RD_NB : dpart == 2 ? 4 * RD_NB + 1 : 6 * RD_NB + 4 - RD_NB;   // 12 values from here: bins | bins | bins | .. h w l
-    const int dexb = dpart == 0 ? 2 * RD_NB : dpart == 1 ? 3 * RD_NB : dpart == 2 ? 5 * RD_NB + 1 : 4 * RD_NB;     // + bin: residual (part 3: the y offset)
-    const int dxo = dpart == 0 ? 0 : dpart == 1 ? 2 : dpart == 2 ? 0 : 1;                                          // which coordinate of the point
-    const int dbo = dpart == 0 ? 0 : dpart == 1 ? 2 : dpart == 2 ? 6 : 1;                                          // which slot of the box
-    float dv[RD_NB], dp = 0.f, dex = 0.f, dout = 0.f, dh = 0.f, dw = 0.f, dl = 0.f;
-    int dbi = 0;
-#define RL_DEC_READ(TT)                                                                                   \
-    {                                                                                                     \
-        _Pragma("unroll") for (int i = 0; i < RD_NB; ++i) dv[i] = drow[dstart + i];                        \
-        unsigned int gr_ = (unsigned int)(TT) * RT_ROWS + 16 * w + (lane >> 2);                           \
-        if (gr_ >= (unsigned int)a.rows) gr_ = (unsigned int)a.rows - 1u;                                  \
-        dp = a.xyz[gr_ * 3u + dxo];                                                                        \
-    }
-    // first maximum; a NaN counts as the largest value (torch.argmax; proposal.hip argmax_row)
-#define RL_DEC_ARGMAX                                                                                     \
-    {                                                                                                     \
-        float bv_ = dv[0];                                                                                \
-        dbi = 0;                                                                                          \
-        _Pragma("unroll") for (int i = 1; i < RD_NB; ++i) {                                                \
-            const bool tk_ = dv[i] > bv_ || (dv[i] != dv[i] && bv_ == bv_);                                \
-            bv_ = tk_ ? dv[i] : bv_;                                                                      \
-            dbi = tk_ ? i : dbi;                                                                          \
-        }                                                                                                 \
-        dex = drow[dexb + (dpart < 3 ? dbi : 0)];                                                          \
-    }
-#define RL_DEC_MATH                                                                                       \
-    {                                                                                                     \
-        const float fb_ = (float)dbi, bin_ = a.loc_bin_size;                                               \
-        float loc_ = __fsub_rn(__fadd_rn(__fmul_rn(fb_, bin_), bin_ / 2), a.loc_scope);                    \
-        loc_ = __fadd_rn(__fadd_rn(loc_, __fmul_rn(dex, bin_)), dp);                                       \
-        const float apc_ = (float)((2.0 * M_PI) / RD_NB), apch_ = (float)(((2.0 * M_PI) / RD_NB) / 2.0);   \
-        const float two_pi_ = (float)(2.0 * M_PI), pi_ = (float)M_PI;                                      \
-        float ry_ = fmod_two_pi(__fadd_rn(__fmul_rn(fb_, apc_), __fmul_rn(dex, apch_)));           \
-        ry_ = (ry_ != 0.f && ry_ < 0.f) ? __fadd_rn(ry_, two_pi_) : ry_;                                   \
-        ry_ = ry_ > pi_ ? __fsub_rn(ry_, two_pi_) : ry_;                                                   \
-        dh = __fadd_rn(__fmul_rn(dv[RD_NB - 3], a.anchor[0]), a.anchor[0]);                                \
-        dw = __fadd_rn(__fmul_rn(dv[RD_NB - 2], a.anchor[1]), a.anchor[1]);                                \
-        dl = __fadd_rn(__fmul_rn(dv[RD_NB - 1], a.anchor[2]), a.anchor[2]);                                \
-        const float y_ = __fadd_rn(__fadd_rn(dp, dex), dh / 2);                                            \
-        dout = dpart < 2 ? loc_ : dpart == 2 ? ry_ : y_;                                                   \
-    }
-#define RL_DEC_STORE(TT, live)                                                                            \
-    {                                                                                                     \
-        const unsigned int gr_ = (unsigned int)(TT) * RT_ROWS + 16 * w + (lane >> 2);                     \
-        if ((live) && gr_ < (unsigned int)a.rows) {                                                        \
-            float *o_ = a.boxes + gr_ * 7u;                                                                \
-            o_[dbo] = dout;                                                                                \
-            if (dpart == 3) { o_[3] = dh; o_[4] = dw; o_[5] = dl; }                                        \
-        }                                                                                                 \
-    }
-#define RL_DECODE(g, TT, live)                                                                            \
-    if ((g) == 1) RL_DEC_READ(TT)                                                                         \
-    else if ((g) == 3) RL_DEC_ARGMAX                                                                      \
-    else if ((g) == 5) RL_DEC_MATH                                                                        \
-    else if ((g) == 7) RL_DEC_STORE(TT, live)
+    RL_DEC_STATE
 
     // tiles by XCD: one eighth of the rows (one scene of a batch of 8) and its 2 MB of G per L2 instead of all 16.8 MB through every L2
     XcdTickets tk;
@@ -450,35 +356,15 @@ __global__ __launch_bounds__(256, 1) void rpn_tail_lin_kernel(const RpnTailArgs 
         RT_VM_DRAIN
 #define RL_H4(g) RL_SIDE(3, g, 2, 10)
         if (NARROW) {
+            // this wave's 32 x 32 block on the shared k-group text (one accumulator: rows 32 nrb ..); with the group's loads of the next
+            // tile's first stage (FP layer 2: this wave's usual slice) go two of the 16-column block's weights, consumed behind the stage
             float wx[32];
             f32x4 accx;
+#define RL_LOAD_WX(g)                                                                                     \
+            _Pragma("unroll") for (int q = 0; q < 2; ++q)                                                 \
+                wx[2 * (g) + q] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, lane_off_x, (unsigned int)(384 + 2 * (g) + q) * 512u, 0));
+            RT_STAGE_X(T0 + 32 * nrb * RT_LD, wb, wa, rs, 0, true, RL_H4, lane_off, RT_ONE_HALF, RL_LOAD_WX)
             {
-                const float *ap = T0 + (32 * nrb + j) * RT_LD + 64 * h;
-                f32x4 a0 = *reinterpret_cast<const f32x4 *>(ap);
-#pragma unroll
-                for (int g = 0; g < 16; ++g) {
-                    f32x4 n0 = a0;
-                    if (g < 15) n0 = *reinterpret_cast<const f32x4 *>(ap + 4 * (g + 1));
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (g == 0) {
-                        const f32x16 zero = {0};
-                        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.x, wb[0], zero, 0, 0, 0);
-                    } else {
-                        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.x, wb[4 * g + 0], acc0, 0, 0, 0);
-                    }
-#pragma unroll
-                    for (int q = 0; q < 4; ++q)          // the next tile's first stage (FP layer 2): this wave's usual slice
-                        wa[4 * g + q] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, lane_off, (unsigned int)(4 * g + q) * 512u, 0));
-#pragma unroll
-                    for (int q = 0; q < 2; ++q)          // the 16-column block's weights, consumed behind this loop
-                        wx[2 * g + q] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, lane_off_x, (unsigned int)(384 + 2 * g + q) * 512u, 0));
-                    __builtin_amdgcn_sched_barrier(0);
-                    RL_H4(g)
-                    acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.y, wb[4 * g + 1], acc0, 0, 0, 0);
-                    acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.z, wb[4 * g + 2], acc0, 0, 0, 0);
-                    acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.w, wb[4 * g + 3], acc0, 0, 0, 0);
-                    a0 = n0;
-                }
                 const float *xp = T0 + (16 * w + (lane & 15)) * RT_LD + 32 * (lane >> 4);
                 f32x4 x = *reinterpret_cast<const f32x4 *>(xp);
 #pragma unroll
@@ -486,7 +372,7 @@ __global__ __launch_bounds__(256, 1) void rpn_tail_lin_kernel(const RpnTailArgs 
                     f32x4 nx = x;
                     if (q < 7) nx = *reinterpret_cast<const f32x4 *>(xp + 4 * (q + 1));
                     if (q == 0) {
-                        const f32x4v zero4 = {0.f, 0.f, 0.f, 0.f};
+                        const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
                         accx = __builtin_amdgcn_mfma_f32_16x16x4f32(x.x, wx[0], zero4, 0, 0, 0);
                     } else {
                         accx = __builtin_amdgcn_mfma_f32_16x16x4f32(x.x, wx[4 * q + 0], accx, 0, 0, 0);
@@ -518,15 +404,8 @@ __global__ __launch_bounds__(256, 1) void rpn_tail_lin_kernel(const RpnTailArgs 
         lds_barrier();
         if (DECODE) {
             RL_DEC_READ(tp) RL_DEC_ARGMAX RL_DEC_MATH RL_DEC_STORE(tp, true)
-        } else if (4 * chunk < a.n_reg) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const int row = r0 + 8 * i;
-                const unsigned int g = (unsigned int)tp * RT_ROWS + row;
-                if (g < (unsigned int)a.rows)
-                    *reinterpret_cast<f32x4 *>(a.reg + (g * (unsigned int)a.n_reg + 4u * chunk)) =
-                        *reinterpret_cast<const f32x4 *>(T1 + row * RT_LD + 4 * chunk);
-            }
+        } else {
+            RT_LAST_REG_ROWS
         }
     }
     if (tid == 0) tk.release();                      // the launch's last workgroup zeroes the record for its next user
@@ -534,105 +413,84 @@ __global__ __launch_bounds__(256, 1) void rpn_tail_lin_kernel(const RpnTailArgs 
 
 }  // namespace prcnn
 
-namespace prcnn {
-__global__ __launch_bounds__(256) void fmod_two_pi_selftest_kernel(long n, const float *__restrict__ a, float *__restrict__ mine,
-                                                                   float *__restrict__ lib)
-{
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    mine[i] = fmod_two_pi(a[i]);
-    lib[i] = fmodf(a[i], (float)(2.0 * M_PI));
-}
-}
-
 using namespace prcnn;
 
-extern "C" int prcnn_rpn_tail(int b, int n, int m, const float *known, const int *idx, const float *weight, const float *wcat,
-                              const float *bcat, const float *wc2, const float *bc2, int n_reg, float *feats, float *cls,
-                              float *reg, void *stream)
-{
-    PRCNN_REQUIRE(b >= 0 && n >= 0 && m >= 1 && n_reg >= 4 && n_reg <= 128 && n_reg % 4 == 0,
-                  "rpn_tail: bad sizes (n_reg=%d must be a multiple of 4 in 4..128)", n_reg);
-    const long rows = (long)b * n;
-    if (rows == 0) return PRCNN_OK;
-    PRCNN_REQUIRE(rows <= (1L << 23), "rpn_tail: too many points (32-bit element offsets)");
-    PRCNN_REQUIRE(known && idx && weight && wcat && bcat && wc2 && bc2 && feats && cls && reg, "rpn_tail: null pointer");
-    PRCNN_REQUIRE((((uintptr_t)known | (uintptr_t)feats | (uintptr_t)wcat | (uintptr_t)reg) & 15) == 0,
-                  "rpn_tail: 16-byte alignment required");
-    RpnTailArgs a;
-    a.rows = rows; a.n = n; a.m = m; a.known = known; a.idx = idx; a.weight = weight;
-    a.wcat = wcat; a.bcat = bcat; a.wc2 = wc2; a.bc2 = bc2; a.feats = feats; a.cls = cls; a.reg = reg; a.n_reg = n_reg;
-    a.ticket = next_ticket((hipStream_t)stream);
-    if (!a.ticket) { set_error("rpn_tail: cannot set up the tile ticket"); return PRCNN_ELAUNCH; }
-    a.xcd_split = 0;
-    const long tiles = (rows + RT_ROWS - 1) / RT_ROWS;
-    const long cap = mfma_grid_cap() < 256 ? mfma_grid_cap() : 256;               // gfx950: 256 CUs, one resident workgroup each (135 KB of LDS)
-    const long grid = tiles < cap ? tiles : cap;
-    hipLaunchKernelGGL(rpn_tail_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a);
-    return check_launch("rpn_tail");
-}
-
-
-/* prcnn_rpn_tail with the FP module's first layer already applied at the coarse level (csrc/rpn_tail.hip rpn_tail_lin_kernel):
- * G (b,m,128) = coarse features @ the layer's weights (no bias); wcat (512,128) = [FP layer 2 | cls layer 1 | reg layer 1 | reg layer 2],
- * bcat (5,128) = the biases of FP layer 1 (added after the interpolation) and of those four.
- * boxes != NULL (prcnn_rpn_tail_lin_boxes): the regression rows are decoded in the kernel and `reg` is not written (may be NULL). */
-static int rpn_tail_lin_any(int b, int n, int m, const float *G, const int *idx, const float *weight, const float *wcat,
-                            const float *bcat, const float *wc2, const float *bc2, int n_reg, float *feats, float *cls,
-                            float *reg, const float *xyz, float *boxes, float loc_scope, float loc_bin_size, const float *anchor,
-                            void *stream, const char *who)
+// What the three entries share: validate, fill the kernel's arguments, size the grid, launch.  lin: the FP module's first layer is
+// already applied at the coarse level (`known` = G (b,m,128), wcat (512,128), rpn_tail_lin_kernel); else `known` = the coarse features
+// (b,m,256), wcat (768,128), rpn_tail_kernel.  boxes != NULL (lin only): the regression rows are decoded in the kernel and `reg` is not
+// written (may be NULL).
+static int rpn_tail_launch(const char *who, bool lin, int b, int n, int m, const float *known, const int *idx, const float *weight,
+                           const float *wcat, const float *bcat, const float *wc2, const float *bc2, int n_reg, float *feats, float *cls,
+                           float *reg, const float *xyz, float *boxes, float loc_scope, float loc_bin_size, const float *anchor, void *stream)
 {
     PRCNN_REQUIRE(b >= 0 && n >= 0 && m >= 1 && n_reg >= 4 && n_reg <= 128 && n_reg % 4 == 0,
                   "%s: bad sizes (n_reg=%d must be a multiple of 4 in 4..128)", who, n_reg);
     const long rows = (long)b * n;
     if (rows == 0) return PRCNN_OK;
     PRCNN_REQUIRE(rows <= (1L << 23), "%s: too many points (32-bit element offsets)", who);
-    PRCNN_REQUIRE(G && idx && weight && wcat && bcat && wc2 && bc2 && feats && cls && (reg || boxes), "%s: null pointer", who);
-    PRCNN_REQUIRE((((uintptr_t)G | (uintptr_t)feats | (uintptr_t)wcat | (uintptr_t)reg | (uintptr_t)bcat) & 15) == 0,
+    PRCNN_REQUIRE(known && idx && weight && wcat && bcat && wc2 && bc2 && feats && cls && (reg || boxes), "%s: null pointer", who);
+    // (lin: the bias of FP layer 1 is read as one float4 per lane)
+    PRCNN_REQUIRE((((uintptr_t)known | (uintptr_t)feats | (uintptr_t)wcat | (uintptr_t)reg | (lin ? (uintptr_t)bcat : 0)) & 15) == 0,
                   "%s: 16-byte alignment required", who);
     RpnTailArgs a;
-    a.rows = rows; a.n = n; a.m = m; a.known = G; a.idx = idx; a.weight = weight;
+    a.rows = rows; a.n = n; a.m = m; a.known = known; a.idx = idx; a.weight = weight;
     a.wcat = wcat; a.bcat = bcat; a.wc2 = wc2; a.bc2 = bc2; a.feats = feats; a.cls = cls; a.reg = reg; a.n_reg = n_reg;
     a.xyz = xyz; a.boxes = boxes; a.loc_scope = loc_scope; a.loc_bin_size = loc_bin_size;
     for (int i = 0; i < 3; ++i) a.anchor[i] = anchor ? anchor[i] : 0.f;
     a.ticket = next_ticket((hipStream_t)stream);
     if (!a.ticket) { set_error("%s: cannot set up the tile ticket", who); return PRCNN_ELAUNCH; }
-    const int xcd_split = 1;                               // (round 6: A/B switch PRCNN_TAIL_XCD removed)
     const long tiles = (rows + RT_ROWS - 1) / RT_ROWS;
-    // PRCNN_TAIL_GRID (tuning): workgroups of the fused tail.  Its waves hold a SIMD's whole register file, so while it runs on all 256 CUs no
-    // other stream's kernel makes progress; measured in round 6 (bench.py, alternating): 224 / 192 workgroups 8412 / 8443 scenes/s at K = 100
-    // against 8347-8361 with 256 (the tail itself a third longer at 192), 160: 8273; at K = 20 level within the windows' spread -- default kept
+    // gfx950: 256 CUs, one resident workgroup each (135 KB of LDS).  PRCNN_TAIL_GRID (tuning, lin): workgroups of the fused tail.  Its
+    // waves hold a SIMD's whole register file, so while it runs on all 256 CUs no other stream's kernel makes progress; measured in round 6
+    // (bench.py, alternating): 224 / 192 workgroups 8412 / 8443 scenes/s at K = 100 against 8347-8361 with 256 (the tail itself a third
+    // longer at 192), 160: 8273; at K = 20 level within the windows' spread -- default kept
     static const long tail_cap = getenv("PRCNN_TAIL_GRID") && atol(getenv("PRCNN_TAIL_GRID")) > 0 ? atol(getenv("PRCNN_TAIL_GRID")) : 256;
-    const long cap = mfma_grid_cap() < tail_cap ? mfma_grid_cap() : tail_cap;
+    const long most = lin ? tail_cap : 256;
+    const long cap = mfma_grid_cap() < most ? mfma_grid_cap() : most;
     const long grid = tiles < cap ? tiles : cap;
-    // a workgroup draws only from partition blockIdx.x & 7 (no stealing): every non-empty partition needs a workgroup of its own --
-    // with fewer than 8 workgroups for 8 or more tiles (PRCNN_MFMA_GRID < 8) the tiles come from one counter instead
-    a.xcd_split = xcd_split && (grid >= 8 || grid == tiles);
+    const dim3 gd((unsigned)grid), wg(256);
+    hipStream_t st = (hipStream_t)stream;
+    if (!lin) {
+        a.xcd_split = 0;
+        hipLaunchKernelGGL(rpn_tail_kernel, gd, wg, 0, st, a);
+        return check_launch(who);
+    }
+    // tiles by XCD (round 6: A/B switch PRCNN_TAIL_XCD removed): a workgroup draws only from partition blockIdx.x & 7 (no stealing), so
+    // every non-empty partition needs a workgroup of its own -- with fewer than 8 workgroups for 8 or more tiles (PRCNN_MFMA_GRID < 8)
+    // the tiles come from one counter instead
+    a.xcd_split = grid >= 8 || grid == tiles;
     // the narrow last stage (80 columns instead of 128) for 64 < n_reg <= 80; PRCNN_TAIL_NARROW=0: the padded stage everywhere (another
     // k order in columns 64.. -- a numerics switch: ~1e-7 relative)
     static const bool narrow_ok = !(getenv("PRCNN_TAIL_NARROW") && atoi(getenv("PRCNN_TAIL_NARROW")) == 0);
     const bool narrow = narrow_ok && n_reg > 64 && n_reg <= 80;
-    if (boxes && narrow) hipLaunchKernelGGL((rpn_tail_lin_kernel<true, true>), dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a);
-    else if (boxes) hipLaunchKernelGGL((rpn_tail_lin_kernel<true, false>), dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a);
-    else if (narrow) hipLaunchKernelGGL((rpn_tail_lin_kernel<false, true>), dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((rpn_tail_lin_kernel<false, false>), dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a);
+    if (boxes && narrow) hipLaunchKernelGGL((rpn_tail_lin_kernel<true, true>), gd, wg, 0, st, a);
+    else if (boxes) hipLaunchKernelGGL((rpn_tail_lin_kernel<true, false>), gd, wg, 0, st, a);
+    else if (narrow) hipLaunchKernelGGL((rpn_tail_lin_kernel<false, true>), gd, wg, 0, st, a);
+    else hipLaunchKernelGGL((rpn_tail_lin_kernel<false, false>), gd, wg, 0, st, a);
     return check_launch(who);
 }
 
+extern "C" int prcnn_rpn_tail(int b, int n, int m, const float *known, const int *idx, const float *weight, const float *wcat,
+                              const float *bcat, const float *wc2, const float *bc2, int n_reg, float *feats, float *cls,
+                              float *reg, void *stream)
+{
+    PRCNN_REQUIRE(reg || (long)b * n == 0, "rpn_tail: null pointer");
+    return rpn_tail_launch("rpn_tail", false, b, n, m, known, idx, weight, wcat, bcat, wc2, bc2, n_reg, feats, cls, reg, nullptr, nullptr, 0.f,
+                           0.f, nullptr, stream);
+}
+
+/* prcnn_rpn_tail with the FP module's first layer already applied at the coarse level (rpn_tail_lin_kernel):
+ * G (b,m,128) = coarse features @ the layer's weights (no bias); wcat (512,128) = [FP layer 2 | cls layer 1 | reg layer 1 | reg layer 2],
+ * bcat (5,128) = the biases of FP layer 1 (added after the interpolation) and of those four. */
 extern "C" int prcnn_rpn_tail_lin(int b, int n, int m, const float *G, const int *idx, const float *weight, const float *wcat,
                                   const float *bcat, const float *wc2, const float *bc2, int n_reg, float *feats, float *cls,
                                   float *reg, void *stream)
 {
     PRCNN_REQUIRE(reg || (long)b * n == 0, "rpn_tail_lin: null pointer");
-    return rpn_tail_lin_any(b, n, m, G, idx, weight, wcat, bcat, wc2, bc2, n_reg, feats, cls, reg, nullptr, nullptr, 0.f, 0.f, nullptr,
-                            stream, "rpn_tail_lin");
+    return rpn_tail_launch("rpn_tail_lin", true, b, n, m, G, idx, weight, wcat, bcat, wc2, bc2, n_reg, feats, cls, reg, nullptr, nullptr, 0.f,
+                           0.f, nullptr, stream);
 }
 
-/* prcnn_rpn_tail_lin with the proposal layer's decode inside (round 5): boxes (b*n,7) = decode_bbox_target(xyz, reg, get_xz_fine = True,
- * get_y_by_bin = False, get_ry_fine = False) with y += h / 2 (bbox_transform.py:24-121, proposal_layer.py:23-31) -- what rpn_decode_kernel
- * of csrc/proposal.hip computes from the stored rows, operation for operation -- and the regression rows themselves are not
- * written.  Served layout: LOC_SCOPE / LOC_BIN_SIZE = 6 bins per side (12 x bins, 12 z bins), NUM_HEAD_BIN = 12, LOC_XZ_FINE: the 76
- * channels of every shipped configuration (prcnn_rpn_tail_boxes_supported); anchor_size_host = (h, w, l) in host memory. */
 /* test hook: out_mine[i] = the branch-free fmod of the fused decode, out_lib[i] = fmodf(a[i], (float)(2 pi)) on the same device */
 extern "C" int prcnn_selftest_fmod_two_pi(long n, const float *a, float *out_mine, float *out_lib, void *stream)
 {
@@ -645,10 +503,14 @@ extern "C" int prcnn_selftest_fmod_two_pi(long n, const float *a, float *out_min
 
 extern "C" int prcnn_rpn_tail_boxes_supported(int channels, float loc_scope, float loc_bin_size, int num_head_bin, int xz_fine)
 {
-    return loc_bin_size > 0.f && (int)(loc_scope / loc_bin_size) * 2 == RD_NB && num_head_bin == RD_NB && xz_fine &&
-           channels == 6 * RD_NB + 4;
+    return rd_layout_served(channels, loc_scope, loc_bin_size, num_head_bin, xz_fine);
 }
 
+/* prcnn_rpn_tail_lin with the proposal layer's decode inside (round 5): boxes (b*n,7) = decode_bbox_target(xyz, reg, get_xz_fine = True,
+ * get_y_by_bin = False, get_ry_fine = False) with y += h / 2 (bbox_transform.py:24-121, proposal_layer.py:23-31) -- what rpn_decode_kernel
+ * of csrc/proposal.hip computes from the stored rows, operation for operation -- and the regression rows themselves are not
+ * written.  Served layout: LOC_SCOPE / LOC_BIN_SIZE = 6 bins per side (12 x bins, 12 z bins), NUM_HEAD_BIN = 12, LOC_XZ_FINE: the 76
+ * channels of every shipped configuration (prcnn_rpn_tail_boxes_supported); anchor_size_host = (h, w, l) in host memory. */
 extern "C" int prcnn_rpn_tail_lin_boxes(int b, int n, int m, const float *G, const int *idx, const float *weight, const float *wcat,
                                         const float *bcat, const float *wc2, const float *bc2, int n_reg, float loc_scope,
                                         float loc_bin_size, int num_head_bin, int xz_fine, const float *anchor_size_host,
@@ -658,6 +520,6 @@ extern "C" int prcnn_rpn_tail_lin_boxes(int b, int n, int m, const float *G, con
                   "rpn_tail_lin_boxes: regression layout (%d channels, scope %g / bin %g, %d heading bins, xz_fine %d) not served",
                   n_reg, loc_scope, loc_bin_size, num_head_bin, xz_fine);
     PRCNN_REQUIRE(anchor_size_host && ((xyz && boxes) || (long)b * n == 0), "rpn_tail_lin_boxes: null pointer");
-    return rpn_tail_lin_any(b, n, m, G, idx, weight, wcat, bcat, wc2, bc2, n_reg, feats, cls, nullptr, xyz, boxes, loc_scope, loc_bin_size,
-                            anchor_size_host, stream, "rpn_tail_lin_boxes");
+    return rpn_tail_launch("rpn_tail_lin_boxes", true, b, n, m, G, idx, weight, wcat, bcat, wc2, bc2, n_reg, feats, cls, nullptr, xyz, boxes,
+                           loc_scope, loc_bin_size, anchor_size_host, stream);
 }

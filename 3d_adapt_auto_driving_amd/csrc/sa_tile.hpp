@@ -1,5 +1,5 @@
 // sa_tile.hpp -- what the set-abstraction tile kernels share (csrc/sa_mlp_fused.hip: one centre per tile; csrc/sa_packed.hip: the
-// distinct rows of csrc/ball_pack.hip's lists): the tile's shape, the 128-deep MFMA panels over a weight panel held in registers, the
+// distinct rows of csrc/ball_pack.hip's lists; csrc/rows_layer.hip and csrc/rcnn_entrance.hip: the per-point layers in front of them): the tile's shape, the 128-deep MFMA panels over a weight panel held in registers, the
 // epilogues, the ticket draws and the row-descriptor codec of the packed lists.
 //
 // A tile is 64 rows x 128 channels in LDS, rows padded to 132 floats.  Lane (j, h) = (lane & 31, lane >> 5) of a wave supplies row j

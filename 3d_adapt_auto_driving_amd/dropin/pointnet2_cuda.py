@@ -855,7 +855,7 @@ def sa_xyz_mlp_packed_wrapper(new_xyz, xyz, pack, w1, b1, w2, b2, w3, b3, out, o
 
 
 def rcnn_point_mlp_wrapper(rows, fcol, wu1, bu1, wu2, bu2, wm, bm, wp, bp, xfeat, merged, p, tiles=None):
-    """RCNN entrance chain as tiled MFMA layer kernels (csrc/rcnn_point_mlp.hip): rows (R, ld) pooled rows
+    """RCNN entrance chain as tiled MFMA layer kernels (csrc/rcnn_entrance.hip): rows (R, ld) pooled rows
     [x',y',z',mask,depth,0,0,0 | 128 feats at column fcol] -> xfeat = xyz_up(in5), merged = relu([xfeat | feats] wm + bm),
     p = merged wp + bp, each (R,128).  tiles = (tilemap, hdr) from pooled_tiles_wrapper: only those 64-row tiles are computed."""
     _chk(torch.float32, rows, wu1, bu1, wu2, bu2, wm, bm, wp, bp, p)
@@ -886,7 +886,7 @@ def rows_gemm128_rows_wrapper(a, wt, bias, relu, out, rowlist):
 
 def rows_gemm128_wrapper(a, wt, bias, relu, out=None):
     """a (R, K) with K in (128, 256), row stride a.stride(0), unit column stride -> act(a @ wt + bias) (R, 128) on the tiled
-    MFMA layer kernel (csrc/rcnn_point_mlp.hip); R % 64 == 0, wt (K,128) k-major."""
+    MFMA layer kernel (csrc/rows_layer.hip); R % 64 == 0, wt (K,128) k-major."""
     if a.dim() != 2 or a.stride(1) != 1 or not a.is_cuda or a.dtype != torch.float32:
         raise RuntimeError("pointnet2_cuda: rows_gemm128 expects a 2-D float32 CUDA matrix with unit column stride")
     _chk(torch.float32, wt, bias)

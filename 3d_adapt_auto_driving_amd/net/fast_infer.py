@@ -34,7 +34,7 @@ from .. import iou3d_utils
 
 # The engine's switches: what each selects, and what its other setting is (A/B).  Measurements and history: DESIGN.md section 12.
 USE_ROIPOOL_CANONICAL = True   # RCNN input assembly through roipool3d_canonical_kernel; False: the torch-op sequence
-USE_RCNN_POINT_MLP = True      # RCNN entrance chain through csrc/rcnn_point_mlp.hip; False: library GEMMs + concat
+USE_RCNN_POINT_MLP = True      # RCNN entrance chain through csrc/rcnn_entrance.hip; False: library GEMMs + concat
 USE_XYZ_MLP = True             # coordinates-only SA scales through csrc/sa_xyz_mlp.hip; False: the grouped GEMM chain
 # SA levels over the DISTINCT grouped rows only (csrc/sa_packed.hip, same bits); PRCNN_NO_PACK=1: all nsample rows (csrc/sa_mlp_fused.hip)
 USE_PACKED = os.environ.get("PRCNN_NO_PACK") is None
@@ -144,7 +144,7 @@ def _lib_gemm_allowed():
 
 def gemm_bias_act(a, wt, bias, relu):
     """a (rows, K) @ wt (K, Cout) + bias, optional ReLU.  128-wide layers with K in (128, 256) run on the tiled MFMA layer
-    kernel of csrc/rcnn_point_mlp.hip when USE_ROWS_GEMM128 is set; everything else is a
+    kernel of csrc/rows_layer.hip when USE_ROWS_GEMM128 is set; everything else is a
     library GEMM with the epilogue fused when the backend offers it (hipBLASLt through torch._addmm_activation)."""
     if (USE_ROWS_GEMM128 and a.is_cuda and wt.shape[1] == 128 and wt.shape[0] in (128, 256) and a.shape[1] == wt.shape[0]
             and a.shape[0] % 64 == 0 and a.shape[0] >= 4096 and a.stride(1) == 1 and a.stride(0) % 4 == 0
@@ -1103,7 +1103,7 @@ class FastPointRCNN:
         return out
 
     def _point_mlp_ok(self):
-        """Shapes csrc/rcnn_point_mlp.hip is written for: xyz_up 5(8) -> 128 -> 128, merge 256 -> 128, SA1 through the
+        """Shapes csrc/rcnn_entrance.hip is written for: xyz_up 5(8) -> 128 -> 128, merge 256 -> 128, SA1 through the
         fused MFMA kernel with a 128 -> 128 per-point part."""
         if self._pm_ok is None:
             ok = len(self.xyz_up.layers) == 2 and len(self.merge_down.layers) == 1 and len(self.rcnn_sa) > 0

@@ -123,7 +123,7 @@ void orc_rows_dot(long rows, int K, int n, const float *A, long lda, const float
 void orc_sa_xyz_mlp(int b, int n, int m, int ns, int c1, int c2, int c3, const float *new_xyz, const float *xyz,
                     const int *idx, const float *w1, const float *b1, const float *w2, const float *b2, const float *w3,
                     const float *b3, float *out, int out_stride, int out_col);
-/* csrc/rcnn_point_mlp.hip */
+/* csrc/rows_layer.hip, csrc/rcnn_entrance.hip */
 void orc_rcnn_point_mlp(long r, int ld, int fcol, const float *rows, const float *wu1, const float *bu1, const float *wu2,
                         const float *bu2, const float *wm, const float *bm, const float *wp, const float *bp,
                         float *xfeat, float *merged, float *p);

@@ -13,7 +13,7 @@ steps = max(1, int(os.environ.get("PRCNN_PAIR", "2")) * sum(1 for r in half if "
 by = collections.defaultdict(lambda: [0, 0.0])
 for r in half:
     name = r["Kernel_Name"]
-    if not any(k in name for k in ("packed_layer", "sa_packed", "sa_wide", "rcnn_entrance", "rpn_tail", "rcnn_point")):
+    if not any(k in name for k in ("packed_layer", "sa_packed", "sa_wide", "rcnn_entrance", "rpn_tail", "rows_layer", "pooled_rows")):
         continue
     key = (name.replace("void ", "").replace("prcnn::", "").split("(")[0][:44], r.get("Stream_Id", "?"),
            "%sx%sx%s" % (r["Grid_Size_X"], r["Grid_Size_Y"], r["Grid_Size_Z"]), r["Workgroup_Size_X"])

@@ -1,4 +1,5 @@
-"""Microbench of csrc/rcnn_point_mlp.hip at the RCNN size of one batch (8 scenes x 100 RoIs x 512 points)."""
+"""Microbench of csrc/rcnn_entrance.hip and csrc/rows_layer.hip at the RCNN size of one batch (8 scenes x 100 RoIs x 512 points), and of
+the list layer at the engine's shape."""
 import importlib, os, sys, time
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
@@ -32,3 +33,12 @@ cnt = torch.from_numpy(np.random.default_rng(0).poisson(54, 800).clip(1, 512).as
 tiles = P.pooled_tiles_wrapper(cnt, 512)
 us = timed(lambda: P.rcnn_point_mlp_wrapper(rows, 8, wu1, b[0], wu2, b[1], wm, b[2], wp, b[3], None, None, p2, tiles))
 print("rcnn_entrance, live tiles of a step (~1.3 per RoI): %.1f us" % us)
+# the 128-wide layer over a row list (rows_layer_list_kernel) at the engine's shape: the per-point part of the RCNN's second SA level over
+# 1600 RoI clouds x 128 level-1 centres, of which a RoI lists the ~47 that are their own representatives (the uniform scene's share)
+clouds, per = 1600, 128
+cnt2 = torch.from_numpy(np.random.default_rng(1).poisson(47, clouds).clip(1, per).astype(np.int32)).to(dev)
+rowlist = P.pooled_rows_wrapper(cnt2, per)
+a2 = torch.randn((clouds * per, 128), device=dev, generator=g)
+o2 = torch.empty((clouds * per, 128), device=dev)
+us = timed(lambda: P.rows_gemm128_rows_wrapper(a2, wp, b[3], False, o2, rowlist), 50)
+print("rows_gemm128_rows, %d of %d rows listed: %.1f us" % (int(rowlist[1][1]), clouds * per, us))

@@ -30,6 +30,7 @@ def _abs_includes(s):
              .replace('#include "layer_tile.hpp"', '#include "%s/layer_tile.hpp"' % CSRC)
              .replace('#include "sa_tile.hpp"', '#include "%s/sa_tile.hpp"' % CSRC)
              .replace('#include "mfma_stream.hpp"', '#include "%s/mfma_stream.hpp"' % CSRC)
+             .replace('#include "rpn_decode.hpp"', '#include "%s/rpn_decode.hpp"' % CSRC)
              .replace('#include "../../include/prcnn_hip.h"', '#include "%s/include/prcnn_hip.h"' % ROOT))
 
 
@@ -49,7 +50,7 @@ def instrument_tail(lin=False):
     for ln in lines[1:]:
         out.append(ln)
         st = ln.strip()
-        if st.startswith(("lds_barrier();", "RT_STAGE(", "RT_STAGE_HOOK(", "RT_EPILOGUE(")):
+        if st.startswith(("lds_barrier();", "RT_STAGE(", "RT_STAGE_HOOK(", "RT_STAGE_HOOK_LO(", "RT_STAGE_X(", "RT_EPILOGUE(")):
             out.append("        STAMP(%d)" % k); names.append(st.split(";")[0][:44]); k += 1
     s = s[:lo] + "\n".join(out) + s[hi:]
     # (the launch size: PRCNN_MFMA_GRID, capped at one workgroup per CU since the kernel keeps four LDS tiles)

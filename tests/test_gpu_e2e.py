@@ -142,7 +142,7 @@ def test_roipool_canonical_kernel_equals_torch_sequence():
     dxyz = (pooled[..., 0:3] - ref_xyz).abs()
     print("canonical xyz: max |diff| %.3g, differing elements %d of %d" % (float(dxyz.max()), int((dxyz > 0).sum()), dxyz.numel()))
     assert float(dxyz.max()) < 2e-5                                            # |coordinates| <= ~50 m: a few ulp at most
-    # through the RCNN; and the MFMA entrance chain (csrc/rcnn_point_mlp.hip) vs the library GEMMs + concat
+    # through the RCNN; and the MFMA entrance chain (csrc/rcnn_entrance.hip) vs the library GEMMs + concat
     a = eng.rcnn_stage(st, rois)
     F.USE_RCNN_POINT_MLP = False
     try:

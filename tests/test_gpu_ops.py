@@ -1010,7 +1010,7 @@ def test_sa_xyz_mlp_fused_level(ext, oracle, c1, c2, c3, ns):
 
 
 def test_rcnn_point_mlp_kernels(ext):
-    """csrc/rcnn_point_mlp.hip (xyz_up x2 + concat + merge_down + SA1 per-point part as two MFMA kernels) vs the same
+    """csrc/rcnn_entrance.hip (xyz_up x2 + concat + merge_down + SA1 per-point part as two MFMA kernels) vs the same
     chain with library f32 GEMMs; NaN-initialised outputs (every tile served), bit-identical reruns, 3000 tiles."""
     rng = np.random.default_rng(71)
     R, ld = 64 * 3000, 136
@@ -1061,21 +1061,107 @@ def test_rcnn_point_mlp_kernels(ext):
         assert torch.equal(p3[listed], outs[0][1][listed]) and torch.isnan(p3[~listed]).all()
 
 
+def _entrance_case(R, seed=72):
+    """pooled rows (R, 136) with fcol = 8, the chain's weights, and the CPU stand-in's xfeat / merged / p (computed once per R)"""
+    if R not in _ENTRANCE_CASES:
+        from oracle import ext_cpu
+        rng = np.random.default_rng(seed + R)
+        rows = rng.standard_normal((R, 136)).astype(np.float32)
+        rows[:, 5:8] = 0
+        W = lambda *sh: torch.from_numpy((rng.standard_normal(sh) / np.sqrt(sh[0])).astype(np.float32))
+        wu1 = W(8, 128); wu1[5:] = 0
+        ws = [wu1, torch.from_numpy(rng.standard_normal(128).astype(np.float32) * 0.1)]
+        for k in (128, 256, 128):
+            ws += [W(k, 128), torch.from_numpy(rng.standard_normal(128).astype(np.float32) * 0.1)]
+        want = [torch.empty((R, 128)) for _ in range(3)]
+        ext_cpu.pointnet2_cpu.rcnn_point_mlp_wrapper(torch.from_numpy(rows), 8, *ws, *want)
+        _ENTRANCE_CASES[R] = (torch.from_numpy(rows), ws, want)
+    return _ENTRANCE_CASES[R]
+
+
+_ENTRANCE_CASES = {}
+
+
+@pytest.mark.parametrize("R", [64, 128, 192])
+def test_rcnn_entrance_chain_small_equals_the_cpu_stand_in(ext, R):
+    """The entrance chain on one, two and three tiles, every form bit for bit against oracle/ext_cpu.py rcnn_point_mlp_wrapper: the three
+    launches (xfeat, merged, p), the fused kernel, the fused kernel over a tile map made from counts and over row lists of 1, 65 and R
+    rows; NaN-initialised outputs: tiles and rows that are not listed stay NaN."""
+    rows, ws, (wx, wm, wp) = _entrance_case(R)
+    trow, tw = rows.to(DEV), [w.to(DEV) for w in ws]
+    nan = lambda: torch.full((R, 128), float("nan"), device=DEV)
+    xfeat, merged, p = nan(), nan(), nan()
+    ext.pointnet2.rcnn_point_mlp_wrapper(trow, 8, *tw, xfeat, merged, p)
+    assert torch.equal(xfeat.cpu(), wx) and torch.equal(merged.cpu(), wm) and torch.equal(p.cpu(), wp)
+    p1 = nan()
+    ext.pointnet2.rcnn_point_mlp_wrapper(trow, 8, *tw, None, None, p1)
+    assert torch.equal(p1.cpu(), wp)
+    # a tile map made from counts: one cloud of R rows of which the first 5 / 3 / 70 are distinct -> its first 1 / 1 / 2 tiles
+    cnt = torch.tensor([{64: 5, 128: 3, 192: 70}[R]], dtype=torch.int32, device=DEV)
+    tiles = ext.pointnet2.pooled_tiles_wrapper(cnt, R)
+    nlive = int(tiles[1][0])
+    assert nlive == (int(cnt[0]) + 63) // 64 and tiles[0][:nlive].tolist() == list(range(nlive))
+    p2 = nan()
+    ext.pointnet2.rcnn_point_mlp_wrapper(trow, 8, *tw, None, None, p2, tiles)
+    assert torch.equal(p2.cpu()[:64 * nlive], wp[:64 * nlive]) and torch.isnan(p2.cpu()[64 * nlive:]).all()
+    rng = np.random.default_rng(R)
+    for n in (1, 65, R):
+        if n > R:                                              # (65 listed rows need two tiles of rows)
+            continue
+        rowmap = torch.from_numpy(rng.permutation(R)[:n].astype(np.int32))
+        hdr = torch.tensor([0, n, 0, 0], dtype=torch.int32)
+        p3 = nan()
+        ext.pointnet2.rcnn_point_mlp_rows_wrapper(trow, 8, *tw, p3, (rowmap.to(DEV), hdr.to(DEV)))
+        listed = torch.zeros(R, dtype=torch.bool)
+        listed[rowmap.long()] = True
+        assert torch.equal(p3.cpu()[listed], wp[listed]) and torch.isnan(p3.cpu()[~listed]).all(), n
+
+
 @pytest.mark.parametrize("K,relu", [(128, True), (128, False), (256, True), (256, False)])
 def test_rows_gemm128_layer(ext, K, relu):
-    """The tiled MFMA layer kernel as a general 128-wide layer: contiguous and row-strided inputs vs torch f32."""
+    """The tiled MFMA layer kernel as a general 128-wide layer: contiguous and row-strided inputs vs torch f32, and bit for bit against
+    the CPU stand-in (oracle/ext_cpu.py rows_gemm128_wrapper).  R = 64: one tile, no next tile to prefetch."""
+    from oracle import ext_cpu
     rng = np.random.default_rng(K + int(relu))
-    R = 64 * 333
     wt = T((rng.standard_normal((K, 128)) / np.sqrt(K)).astype(np.float32))
     b = T(rng.standard_normal(128).astype(np.float32) * 0.1)
-    wide = T(rng.standard_normal((R, K + 8)).astype(np.float32))
-    for a in (wide[:, :K].contiguous(), wide[:, 4:4 + K] if False else wide[:, 8:8 + K]):   # contiguous; strided (ld = K+8, col 8)
+    for R in (64 * 333, 64):
+        wide = T(rng.standard_normal((R, K + 8)).astype(np.float32))
+        for a in (wide[:, :K].contiguous(), wide[:, 4:4 + K] if False else wide[:, 8:8 + K]):   # contiguous; strided (ld = K+8, col 8)
+            out = torch.full((R, 128), float("nan"), device=DEV)
+            ext.pointnet2.rows_gemm128_wrapper(a, wt, b, relu, out)
+            want = a @ wt + b
+            want = torch.relu(want) if relu else want
+            assert torch.isfinite(out).all()
+            assert (out - want).abs().max().item() <= 2e-5 * max(1.0, want.abs().max().item())
+            assert torch.equal(out.cpu(), ext_cpu.pointnet2_cpu.rows_gemm128_wrapper(a.cpu(), wt.cpu(), b.cpu(), relu)), R
+
+
+@pytest.mark.parametrize("n", [1, 64, 65, 64 * 512 + 1, 64 * 1024 + 1])
+def test_rows_gemm128_rows_list_layer_alone(ext, n):
+    """rows_gemm128_rows_wrapper over a hand-made list: n distinct rows of R = n + 100 in random order, hdr = [0, n, 0, 0], both ReLU
+    settings.  64 * 512 + 1 and 64 * 1024 + 1 are the smallest lists for which a workgroup serves a second and a third tile (512
+    workgroups at most, tiles strided by the grid): the next tile's prefetch and the row numbers fetched two tiles ahead, each with a
+    one-row last tile.  Listed rows equal the CPU stand-in's (oracle/ext_cpu.py rows_gemm128_wrapper over the gathered rows), all other
+    rows are still NaN."""
+    from oracle import ext_cpu
+    rng = np.random.default_rng(n)
+    R = n + 100
+    a = torch.from_numpy(rng.standard_normal((R, 128)).astype(np.float32))
+    wt = torch.from_numpy((rng.standard_normal((128, 128)) / np.sqrt(128)).astype(np.float32))
+    b = torch.from_numpy(rng.standard_normal(128).astype(np.float32) * 0.1)
+    rowmap = torch.from_numpy(rng.permutation(R)[:n].astype(np.int32))
+    rowlist = (rowmap.to(DEV), torch.tensor([0, n, 0, 0], dtype=torch.int32, device=DEV))
+    listed = torch.zeros(R, dtype=torch.bool)
+    listed[rowmap.long()] = True
+    gathered = a[rowmap.long()].contiguous()
+    for relu in (True, False):
         out = torch.full((R, 128), float("nan"), device=DEV)
-        ext.pointnet2.rows_gemm128_wrapper(a, wt, b, relu, out)
-        want = a @ wt + b
-        want = torch.relu(want) if relu else want
-        assert torch.isfinite(out).all()
-        assert (out - want).abs().max().item() <= 2e-5 * max(1.0, want.abs().max().item())
+        ext.pointnet2.rows_gemm128_rows_wrapper(a.to(DEV), wt.to(DEV), b.to(DEV), relu, out, rowlist)
+        want = ext_cpu.pointnet2_cpu.rows_gemm128_wrapper(gathered, wt, b, relu)
+        got = out.cpu()
+        assert torch.equal(got[rowmap.long()], want) and torch.isnan(got[~listed]).all(), relu
+        assert float(want.abs().max()) > 0
 
 
 def test_randomised_operator_sweep(ext, oracle):

@@ -462,7 +462,8 @@ def _rpn_tail_case(rng, b, n, m, n_reg):
     return known, idx, wgt, T(wcat), T(bcat), wc2, bc2
 
 
-@pytest.mark.parametrize("b,n,m,n_reg", [(1, 1, 3, 76), (2, 1000, 300, 76), (3, 64, 17, 128), (1, 4100, 700, 4)])
+@pytest.mark.parametrize("b,n,m,n_reg", [(1, 1, 3, 76), (2, 1000, 300, 76), (3, 64, 17, 128), (1, 4100, 700, 4),
+                                         (1, 130, 9, 64), (1, 130, 9, 68), (1, 130, 9, 80)])   # around the range 64 < n_reg <= 80 of rpn_tail_lin_kernel's narrow stage
 def test_rpn_tail_kernel_equals_the_chain_of_oracle_functions(ext, b, n, m, n_reg):
     """csrc/rpn_tail.hip (interpolation -> FP module 256-128-128 -> cls 128-128-1 and reg 128-128-n_reg, one kernel) vs the
     oracle's three_interpolate -> five MFMA-ordered layers -> GEMV, BIT FOR BIT: ragged row counts (not multiples of 64, fewer
@@ -481,7 +482,8 @@ def test_rpn_tail_kernel_equals_the_chain_of_oracle_functions(ext, b, n, m, n_re
     assert float(wf.abs().max()) > 0 and float(wr.abs().max()) > 0
 
 
-@pytest.mark.parametrize("b,n,m,n_reg", [(1, 1, 3, 76), (2, 1000, 300, 76), (3, 64, 17, 128), (1, 4100, 700, 4), (8, 16384, 4096, 76)])
+@pytest.mark.parametrize("b,n,m,n_reg", [(1, 1, 3, 76), (2, 1000, 300, 76), (3, 64, 17, 128), (1, 4100, 700, 4), (8, 16384, 4096, 76),
+                                         (1, 130, 9, 64), (1, 130, 9, 68), (1, 130, 9, 80)])   # the first width below the narrow last stage's range, its two edges
 def test_rpn_tail_lin_kernel_equals_its_oracle_restatement(ext, b, n, m, n_reg):
     """csrc/rpn_tail.hip rpn_tail_lin_kernel (FP layer 1 applied at the coarse level: the 128-wide product is interpolated, + bias,
     ReLU, then FP layer 2 and both heads in one kernel) vs oracle/ext_cpu.py rpn_tail_lin_wrapper, BIT FOR BIT: ragged sizes, several
