@@ -22,11 +22,16 @@ namespace prcnn {
 // the CU.  Four panel stages per tile, each one's 128 x 32 weight slice per wave streaming in behind the MFMAs of the stage
 // before it (mfma_stream.hpp); persistent workgroups draw the live tiles from a ticket counter.  Arithmetic per row = the three
 // rows_layer_kernel launches, bit for bit (same builder chain, same panel order, same epilogues).
+// SRC (over a row list only): the rows carry no features (ld = 8, csrc/roipool.hip's SRC form); list entry e takes them from row
+// featmap[e] of `feats`, the RPN's own (points, 128) feature matrix, a negative entry = a zero row (the one listed row of an empty box).
+// The same 16 bytes reach the same place of T1: from the first barrier on the two forms are one text.
+template <bool SRC>
 __global__ __launch_bounds__(256, 2) void rcnn_entrance_kernel(
     long tiles, const float *__restrict__ rows, int ld, int fcol, const float4 *__restrict__ wu1, const float4 *__restrict__ bu1,
     const float *__restrict__ wu2, const float *__restrict__ bu2, const float *__restrict__ wm, const float *__restrict__ bm,
     const float *__restrict__ wp, const float *__restrict__ bp, float *__restrict__ p_out, unsigned int *__restrict__ ticket,
-    const int *__restrict__ tilemap, const unsigned int *__restrict__ ntiles_dev, const int *__restrict__ rowmap)
+    const int *__restrict__ tilemap, const unsigned int *__restrict__ ntiles_dev, const int *__restrict__ rowmap,
+    const float *__restrict__ feats, const int *__restrict__ featmap)
 {
     // rowmap != NULL (round 5, prcnn_rcnn_point_mlp_rows): tile t = the rows rowmap[64 t .. 64 t + 63] of `rows` / `p_out` -- the
     // DISTINCT pooled rows of all RoIs back to back (prcnn_pooled_rows), ntiles_dev[1] of them; the last tile's missing entries repeat
@@ -56,8 +61,12 @@ __global__ __launch_bounds__(256, 2) void rcnn_entrance_kernel(
     f32x16 acc0, acc1;
     RT_LOAD_W(wa, rs_u2, 0)
     int ridx[8], nidx[8];                                      // this thread's 8 rows of the running tile / of the next one
+    int fidx[SRC ? 8 : 1], nfidx[SRC ? 8 : 1];                 // SRC: ... and their feature rows
 #pragma unroll
-    for (int i = 0; i < 8; ++i) ridx[i] = (rowmap && t < tiles) ? rowmap[min(t * RT_ROWS + r0 + 8 * i, nrows - 1)] : 0;
+    for (int i = 0; i < 8; ++i) {
+        ridx[i] = (rowmap && t < tiles) ? rowmap[min(t * RT_ROWS + r0 + 8 * i, nrows - 1)] : 0;
+        if constexpr (SRC) fidx[i] = t < tiles ? featmap[min(t * RT_ROWS + r0 + 8 * i, nrows - 1)] : -1;
+    }
     for (unsigned int served = 0; t < tiles; ++served) {
         if (!rowmap) {
             const long tt = tilemap ? (long)tilemap[t] : t;
@@ -73,7 +82,8 @@ __global__ __launch_bounds__(256, 2) void rcnn_entrance_kernel(
                 const float *row = rows + (long)ridx[i] * (long)ld;
                 q[i] = *reinterpret_cast<const float4 *>(row);
                 d[i] = row[4];
-                f[i] = *reinterpret_cast<const float4 *>(row + fcol + 4 * chunk);
+                if constexpr (SRC) f[i] = *reinterpret_cast<const float4 *>(feats + (long)max(fidx[i], 0) * PK_C + 4 * chunk);
+                else f[i] = *reinterpret_cast<const float4 *>(row + fcol + 4 * chunk);
             }
             // the next tile's ticket rides behind the loads (a persistent workgroup: it draws until the tickets run out, so this is
             // not sa_next_ticket, which stops at a workgroup's quota)
@@ -83,6 +93,8 @@ __global__ __launch_bounds__(256, 2) void rcnn_entrance_kernel(
                 float4 v;
                 v = relu4(pk_fma4(k1[4], d[i], pk_fma4(k1[3], q[i].w, pk_fma4(k1[2], q[i].z, pk_fma4(k1[1], q[i].y, pk_fma4(k1[0], q[i].x, b1))))));
                 *reinterpret_cast<float4 *>(T0 + (r0 + 8 * i) * RT_LD + 4 * chunk) = v;
+                if constexpr (SRC)                                 // (a select: whatever row 0 holds, a NaN included, is dropped)
+                    if (fidx[i] < 0) f[i] = make_float4(0.f, 0.f, 0.f, 0.f);
                 *reinterpret_cast<float4 *>(T1 + (r0 + 8 * i) * RT_LD + 4 * chunk) = f[i];
             }
         }
@@ -91,7 +103,10 @@ __global__ __launch_bounds__(256, 2) void rcnn_entrance_kernel(
         if (rowmap) {                                          // the next tile's row numbers: in flight behind the first stage
             const long tq = (long)__builtin_amdgcn_readfirstlane((int)slot[(served + 1) & 1]);
 #pragma unroll
-            for (int i = 0; i < 8; ++i) nidx[i] = tq < tiles ? rowmap[min(tq * RT_ROWS + r0 + 8 * i, nrows - 1)] : 0;
+            for (int i = 0; i < 8; ++i) {
+                nidx[i] = tq < tiles ? rowmap[min(tq * RT_ROWS + r0 + 8 * i, nrows - 1)] : 0;
+                if constexpr (SRC) nfidx[i] = tq < tiles ? featmap[min(tq * RT_ROWS + r0 + 8 * i, nrows - 1)] : -1;
+            }
         }
         // ---- xyz_up layer 2 (wa) while merge panel a (wb) comes in
         RT_STAGE(T0, wa, wb, rs_m, 0, true)
@@ -117,7 +132,10 @@ __global__ __launch_bounds__(256, 2) void rcnn_entrance_kernel(
         t = tn;
         if (rowmap) {
 #pragma unroll
-            for (int i = 0; i < 8; ++i) ridx[i] = nidx[i];
+            for (int i = 0; i < 8; ++i) {
+                ridx[i] = nidx[i];
+                if constexpr (SRC) fidx[i] = nfidx[i];
+            }
         }
     }
     if (tid == 0) ticket_release(ticket);          // the launch's last workgroup zeroes the counter for the word's next user
@@ -155,9 +173,10 @@ __global__ __launch_bounds__(1024) void pooled_tiles_kernel(int clouds, int rows
 
 // cnt[c] distinct rows of cloud c -> the list of those rows (row c * rows_per_cloud + j, j < max(cnt[c], 1)) of ALL clouds back to back:
 // rowmap[0 .. hdr[1]).  A wave per cloud draws its block from the list's row counter hdr[1] (zero on entry): the order of the clouds in
-// the list is the counter's, every row of the input is computed on its own.
+// the list is the counter's, every row of the input is computed on its own.  featmap (optional): src[row] of every listed row beside it,
+// the row of the feature matrix that csrc/roipool.hip's SRC form names for it.
 __global__ __launch_bounds__(256) void pooled_rows_kernel(int clouds, int rows_per_cloud, const int *__restrict__ cnt, int *__restrict__ rowmap,
-                                                          unsigned int *__restrict__ hdr)
+                                                          unsigned int *__restrict__ hdr, const int *__restrict__ src, int *__restrict__ featmap)
 {
     const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (c >= clouds) return;
@@ -165,7 +184,10 @@ __global__ __launch_bounds__(256) void pooled_rows_kernel(int clouds, int rows_p
     int base = 0;
     if (lane == 0) base = (int)atomicAdd(&hdr[1], (unsigned int)n);
     base = __builtin_amdgcn_readfirstlane(base);
-    for (int j = lane; j < n; j += 64) rowmap[base + j] = c * rows_per_cloud + j;
+    for (int j = lane; j < n; j += 64) {
+        rowmap[base + j] = c * rows_per_cloud + j;
+        if (featmap) featmap[base + j] = src[c * rows_per_cloud + j];
+    }
 }
 
 }  // namespace prcnn
@@ -173,14 +195,14 @@ __global__ __launch_bounds__(256) void pooled_rows_kernel(int clouds, int rows_p
 using namespace prcnn;
 
 // what prcnn_rcnn_point_mlp and prcnn_rcnn_point_mlp_rows ask of their common arguments; *run = false: nothing to do (r == 0).
-// fused: the chain runs in rcnn_entrance_kernel, whose weight slices come in as 16-byte aligned buffers.
+// fused: the chain runs in rcnn_entrance_kernel, whose weight slices come in as 16-byte aligned buffers.  fcol < 0: rows without features.
 static int entrance_check(const char *who, long r, int ld, int fcol, const float *rows, const float *wu1, const float *bu1, const float *wu2,
                           const float *bu2, const float *wm, const float *bm, const float *wp, const float *bp, const float *p, bool fused,
                           bool *run)
 {
     *run = false;
     PRCNN_REQUIRE(r >= 0 && r % RT_ROWS == 0, "%s: %ld rows is not a multiple of %d", who, r, RT_ROWS);
-    PRCNN_REQUIRE(ld >= 8 && ld % 4 == 0 && fcol >= 8 && fcol % 4 == 0 && fcol + PK_C <= ld, "%s: bad row layout ld=%d fcol=%d", who, ld, fcol);
+    PRCNN_REQUIRE(ld >= 8 && ld % 4 == 0 && (fcol < 0 || (fcol >= 8 && fcol % 4 == 0 && fcol + PK_C <= ld)), "%s: bad row layout ld=%d fcol=%d", who, ld, fcol);
     if (r == 0) return PRCNN_OK;
     PRCNN_REQUIRE(rows && wu1 && bu1 && wu2 && bu2 && wm && bm && wp && bp && p, "%s: null pointer", who);
     PRCNN_REQUIRE((((uintptr_t)rows | (uintptr_t)wu1 | (uintptr_t)bu1 | (uintptr_t)p) & 15) == 0 &&
@@ -189,17 +211,19 @@ static int entrance_check(const char *who, long r, int ld, int fcol, const float
     return PRCNN_OK;
 }
 
-// the fused chain over r / 64 tiles at most: whole tiles, the tiles of a tile map (tilemap, hdr[0]) or the rows of a list (rowmap, hdr[1])
+// the fused chain over r / 64 tiles at most: whole tiles, the tiles of a tile map (tilemap, hdr[0]) or the rows of a list (rowmap, hdr[1]);
+// featmap (with a list only): the listed rows' features come from rows featmap[e] of `feats`
 static int entrance_launch(const char *who, long r, int ld, int fcol, const float *rows, const float *wu1, const float *bu1, const float *wu2,
                            const float *bu2, const float *wm, const float *bm, const float *wp, const float *bp, float *p, const int *tilemap,
-                           const unsigned int *hdr, const int *rowmap, hipStream_t st)
+                           const unsigned int *hdr, const int *rowmap, const float *feats, const int *featmap, hipStream_t st)
 {
     const long tiles = r / RT_ROWS;                            // at most, where a list on the device says how many
     unsigned int *tk = next_ticket(st);
     if (!tk) { set_error("%s: cannot set up the tile ticket", who); return PRCNN_ELAUNCH; }
     const long grid = tiles < mfma_grid_cap() ? tiles : mfma_grid_cap();
-    hipLaunchKernelGGL(rcnn_entrance_kernel, dim3((unsigned)grid), dim3(256), 0, st, tiles, rows, ld, fcol, (const float4 *)wu1,
-                       (const float4 *)bu1, wu2, bu2, wm, bm, wp, bp, p, tk, tilemap, hdr, rowmap);
+    auto kernel = featmap ? rcnn_entrance_kernel<true> : rcnn_entrance_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(256), 0, st, tiles, rows, ld, fcol, (const float4 *)wu1, (const float4 *)bu1, wu2,
+                       bu2, wm, bm, wp, bp, p, tk, tilemap, hdr, rowmap, feats, featmap);
     return check_launch(who);
 }
 
@@ -221,7 +245,7 @@ extern "C" int prcnn_rcnn_point_mlp(long r, int ld, int fcol, const float *rows,
     PRCNN_REQUIRE((xfeat == nullptr) == (merged == nullptr), "rcnn_point_mlp: xfeat and merged are both given or both NULL");
     PRCNN_REQUIRE((((uintptr_t)xfeat | (uintptr_t)merged) & 15) == 0, "rcnn_point_mlp: 16-byte alignment required");
     hipStream_t st = (hipStream_t)stream;
-    if (!xfeat) return entrance_launch("rcnn_point_mlp(fused)", r, ld, fcol, rows, wu1, bu1, wu2, bu2, wm, bm, wp, bp, p, tilemap, ntiles, nullptr, st);
+    if (!xfeat) return entrance_launch("rcnn_point_mlp(fused)", r, ld, fcol, rows, wu1, bu1, wu2, bu2, wm, bm, wp, bp, p, tilemap, ntiles, nullptr, nullptr, nullptr, st);
     const long tiles = r / RT_ROWS;
     rc = rows_layer_launch(1, 1, true, tiles, rows, ld, 0, nullptr, 0, 0, wu1, bu1, wu2, nullptr, bu2, xfeat, tilemap, ntiles, st,
                            "rcnn_point_mlp(xyz_up)");
@@ -244,20 +268,46 @@ extern "C" int prcnn_rcnn_point_mlp_rows(long r, int ld, int fcol, const float *
     const int rc = entrance_check("rcnn_point_mlp_rows", r, ld, fcol, rows, wu1, bu1, wu2, bu2, wm, bm, wp, bp, p, true, &run);
     if (rc != PRCNN_OK || !run) return rc;
     PRCNN_REQUIRE(rowmap && hdr, "rcnn_point_mlp_rows: null pointer");
-    return entrance_launch("rcnn_point_mlp_rows", r, ld, fcol, rows, wu1, bu1, wu2, bu2, wm, bm, wp, bp, p, nullptr, hdr, rowmap, (hipStream_t)stream);
+    return entrance_launch("rcnn_point_mlp_rows", r, ld, fcol, rows, wu1, bu1, wu2, bu2, wm, bm, wp, bp, p, nullptr, hdr, rowmap, nullptr, nullptr,
+                           (hipStream_t)stream);
+}
+
+// ... over rows that carry no features (r, ld >= 8: [x',y',z',mask,depth, ...], prcnn_roipool3d_canonical_src): list entry e takes its 128
+// features from row featmap[e] of feats (any number of rows, 128 wide), zeros where featmap[e] < 0 (prcnn_pooled_rows_src).  Same chain, same bits.
+extern "C" int prcnn_rcnn_point_mlp_rows_src(long r, int ld, const float *rows, const float *feats, const float *wu1, const float *bu1,
+                                             const float *wu2, const float *bu2, const float *wm, const float *bm, const float *wp,
+                                             const float *bp, float *p, const int *rowmap, const int *featmap, const unsigned int *hdr,
+                                             void *stream)
+{
+    PRCNN_REQUIRE(r <= 0x7fffffffL, "rcnn_point_mlp_rows_src: %ld rows: the list holds 32-bit row numbers", r);
+    bool run;
+    const int rc = entrance_check("rcnn_point_mlp_rows_src", r, ld, -1, rows, wu1, bu1, wu2, bu2, wm, bm, wp, bp, p, true, &run);
+    if (rc != PRCNN_OK || !run) return rc;
+    PRCNN_REQUIRE(rowmap && featmap && hdr && feats, "rcnn_point_mlp_rows_src: null pointer");
+    PRCNN_REQUIRE(((uintptr_t)feats & 15) == 0, "rcnn_point_mlp_rows_src: 16-byte alignment required");
+    return entrance_launch("rcnn_point_mlp_rows_src", r, ld, 0, rows, wu1, bu1, wu2, bu2, wm, bm, wp, bp, p, nullptr, hdr, rowmap, feats, featmap,
+                           (hipStream_t)stream);
 }
 
 // cnt (clouds) i32 -> rowmap (clouds * rows_per_cloud entries at most), hdr[1] = number of listed rows (hdr (4 u32) zeroed here unless
 // hdr_is_zero): the distinct pooled rows of all clouds back to back, for prcnn_rcnn_point_mlp_rows.
-extern "C" int prcnn_pooled_rows(int clouds, int rows_per_cloud, const int *cnt, int *rowmap, unsigned int *hdr, int hdr_is_zero, void *stream)
+// src / featmap (optional, both or neither; prcnn_pooled_rows_src): src (clouds * rows_per_cloud) i32 -> featmap[e] = src[rowmap[e]] in the same pass.
+extern "C" int prcnn_pooled_rows_src(int clouds, int rows_per_cloud, const int *cnt, const int *src, int *rowmap, int *featmap, unsigned int *hdr,
+                                     int hdr_is_zero, void *stream)
 {
     PRCNN_REQUIRE(clouds >= 0 && rows_per_cloud > 0 && (long)clouds * rows_per_cloud <= 0x7fffffffL, "pooled_rows: bad sizes");
     PRCNN_REQUIRE(hdr && (clouds == 0 || (cnt && rowmap)), "pooled_rows: null pointer");
+    PRCNN_REQUIRE((src == nullptr) == (featmap == nullptr), "pooled_rows: src and featmap go together");
     hipStream_t st = (hipStream_t)stream;
     if (!hdr_is_zero && hipMemsetAsync(hdr, 0, 4 * sizeof(unsigned int), st) != hipSuccess) { set_error("pooled_rows: memset failed"); return PRCNN_ELAUNCH; }
     if (clouds == 0) return PRCNN_OK;
-    hipLaunchKernelGGL(pooled_rows_kernel, dim3((clouds + 3) / 4), dim3(256), 0, st, clouds, rows_per_cloud, cnt, rowmap, hdr);
+    hipLaunchKernelGGL(pooled_rows_kernel, dim3((clouds + 3) / 4), dim3(256), 0, st, clouds, rows_per_cloud, cnt, rowmap, hdr, src, featmap);
     return check_launch("pooled_rows");
+}
+
+extern "C" int prcnn_pooled_rows(int clouds, int rows_per_cloud, const int *cnt, int *rowmap, unsigned int *hdr, int hdr_is_zero, void *stream)
+{
+    return prcnn_pooled_rows_src(clouds, rows_per_cloud, cnt, nullptr, rowmap, nullptr, hdr, hdr_is_zero, stream);
 }
 
 // cnt (clouds) i32 distinct rows per cloud of rows_per_cloud rows (prcnn_roipool3d_canonical's pooled_cnt) -> tilemap

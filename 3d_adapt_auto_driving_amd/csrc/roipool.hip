@@ -234,11 +234,15 @@ __global__ __launch_bounds__(RP_THREADS) void roipool3d_kernel(
 // layout the RCNN point MLPs consume:  [x', y', z', seg mask, depth, 0, 0, 0 | C features]  (C % 4 == 0, every
 // 16-byte chunk aligned).  The caller does not pre-clear: empty boxes are written here too.  Selection is the same code
 // as roipool3d_kernel, hence the same points.
+// SRC: the form that copies no features.  `pooled` holds the two leading chunks only (32-byte rows), and src_out (b, m, sampled) names
+// every row's point instead: row b * pts_num + k of the (b * pts_num, C) feature matrix, the wrap-around rows that of row s % cnt, -1
+// in every slot of an empty box (its features are zero rows).  The reader gathers the features where they are (csrc/rcnn_entrance.hip).
+template <bool SRC>
 __global__ __launch_bounds__(RP_THREADS) void roipool3d_canonical_kernel(
     int pts_num, int boxes_num, int feat_len, int sampled, float extra, float extra2, const float *__restrict__ xyz,
     const float *__restrict__ rois, const float *__restrict__ feats, const float *__restrict__ seg_mask,
     const float *__restrict__ depth, float4 *__restrict__ pooled, int *__restrict__ empty_flag, int *__restrict__ pooled_cnt,
-    const float4 *__restrict__ pxyz, const float4 *__restrict__ aabb, float *__restrict__ xyz_out)
+    const float4 *__restrict__ pxyz, const float4 *__restrict__ aabb, float *__restrict__ xyz_out, int *__restrict__ src_out)
 {
     extern __shared__ __align__(16) int rp_lds[];
     float4 *s_c01 = reinterpret_cast<float4 *>(rp_lds);               // [sampled][2]: the two leading chunks of every distinct row
@@ -258,7 +262,7 @@ __global__ __launch_bounds__(RP_THREADS) void roipool3d_canonical_kernel(
     if (cnt < 0)                                                         // no groups given, or a box holding more than 4 x sampled points
         cnt = select_points(pts_num, sampled, pts, rx, ry_bottom + extra, rz, bx[3] + extra2, bx[4] + extra2,
                             bx[5] + extra2, heading, s_sel, s_part, s_cnt);
-    const int q4 = 2 + feat_len / 4;                                     // float4 chunks per row
+    const int q4 = SRC ? 2 : 2 + feat_len / 4;                           // float4 chunks per row
     float4 *__restrict__ dst = pooled + ((long)b * boxes_num + box) * (long)sampled * q4;
     const long chunks = (long)sampled * q4;
     const float cosa = cosf(heading), sina = sinf(heading);             // torch.cos / torch.sin of the f32 heading
@@ -268,7 +272,8 @@ __global__ __launch_bounds__(RP_THREADS) void roipool3d_canonical_kernel(
     // rows) never read beyond -- while the coordinate / mask / depth chunks of ALL rows are written (FPS and the ball query
     // of SA1 run over all `sampled` points, copies included, exactly as the reference does).
     if (pooled_cnt && t == 0) pooled_cnt[(long)b * boxes_num + box] = max(cnt, 1);
-    const int feat_rows = pooled_cnt ? ((max(cnt, 1) + 63) & ~63) : sampled;
+    const int feat_rows = SRC ? 0 : pooled_cnt ? ((max(cnt, 1) + 63) & ~63) : sampled;
+    int *__restrict__ so = SRC ? src_out + ((long)b * boxes_num + box) * (long)sampled : nullptr;
     if (cnt == 0) {
         // the reference leaves zero rows and then applies the canonical transform to ALL rows (rcnn_net.py:147-156):
         // an empty box holds the image of the origin, zero features
@@ -284,6 +289,8 @@ __global__ __launch_bounds__(RP_THREADS) void roipool3d_canonical_kernel(
             float *xo = xyz_out + ((long)b * boxes_num + box) * (long)sampled * 3;
             for (int e = t; e < sampled; e += RP_THREADS) { xo[3 * e] = origin.x; xo[3 * e + 1] = origin.y; xo[3 * e + 2] = origin.z; }
         }
+        if (SRC)
+            for (int e = t; e < sampled; e += RP_THREADS) so[e] = -1;
         return;
     }
     if (t == 0) empty_flag[(long)b * boxes_num + box] = 0;
@@ -322,6 +329,11 @@ __global__ __launch_bounds__(RP_THREADS) void roipool3d_canonical_kernel(
             const int src = s2 < cnt ? s2 : s2 % cnt;
             xo[e] = sc[8 * src + c];
         }
+    }
+    if (SRC) {                                                           // the rows' points by name; nothing of theirs is copied
+        const int first = b * pts_num;
+        for (int e = t; e < sampled; e += RP_THREADS) so[e] = first + s_sel[e < cnt ? e : e % cnt];
+        return;
     }
     // feature chunks of the rows below feat_rows.  (Sending the first batch of gathers out in FRONT of the coordinate phase, to overlap its
     // loads and its barrier, was tried in round 4: the compiler keeps the eight rows in scratch across the barrier -- 42 instead of 35 us.)
@@ -373,10 +385,47 @@ extern "C" int prcnn_roipool3d(int batch_size, int pts_num, int boxes_num, int f
 // Fast-path RCNN input assembly (see roipool3d_canonical_kernel).  xyz (b,n,3), rois (b,m,7) NOT enlarged,
 // feats (b,n,c) point-major with c % 4 == 0, seg_mask / depth (b,n) -> pooled (b,m,sampled,8+c), empty (b,m) i32.
 // xyz_out (optional, (b, m, sampled, 3)): the rows' canonical coordinates as dense clouds as well.
+// src != NULL: the form without the features (prcnn_roipool3d_canonical_src): pooled (b,m,sampled,8), src (b,m,sampled) i32.
+static int canonical_launch(const char *who, int batch_size, int pts_num, int boxes_num, int feature_len, int sampled_pts_num,
+                            float pool_extra_width, const float *xyz, const float *rois, const float *feats, const float *seg_mask,
+                            const float *depth, float *pooled, int *src, int *pooled_empty_flag, int *pooled_cnt, const float *pxyz,
+                            const float *aabb, float *xyz_out, void *stream)
+{
+    PRCNN_REQUIRE((pxyz == nullptr) == (aabb == nullptr), "%s: pxyz and aabb go together (prcnn_point_groups)", who);
+    PRCNN_REQUIRE(!pxyz || (pts_num % 64 == 0 && pts_num <= 65536 && (((uintptr_t)pxyz | (uintptr_t)aabb) & 15) == 0),
+                  "%s: spatial groups need pts_num a multiple of 64, <= 65536", who);
+    PRCNN_REQUIRE(batch_size >= 0 && pts_num >= 0 && boxes_num >= 0 && feature_len >= 0 && sampled_pts_num >= 0, "%s: bad sizes", who);
+    PRCNN_REQUIRE(feature_len % 4 == 0, "%s: feature length %d is not a multiple of 4", who, feature_len);
+    PRCNN_REQUIRE(sampled_pts_num <= RP_MAX_S, "%s: sampled_pts_num=%d > %d unsupported", who, sampled_pts_num, RP_MAX_S);
+    PRCNN_REQUIRE(batch_size <= 65535, "%s: batch > 65535", who);
+    PRCNN_REQUIRE(!src || (long)batch_size * pts_num <= 0x7fffffffL, "%s: src holds 32-bit row numbers", who);
+    if (batch_size == 0 || boxes_num == 0 || sampled_pts_num == 0) return PRCNN_OK;
+    PRCNN_REQUIRE(rois && pooled && pooled_empty_flag && (pts_num == 0 || (xyz && seg_mask && depth && (src || feats || feature_len == 0))),
+                  "%s: null pointer", who);
+    PRCNN_REQUIRE((((uintptr_t)pooled | (uintptr_t)feats) & 15) == 0, "%s: 16-byte alignment required", who);
+    dim3 grid(boxes_num, batch_size);
+    const size_t lds = ((size_t)13 * sampled_pts_num + 4 + (pxyz ? pts_num / 64 : 0)) * sizeof(int);   // s_c01 | s_sel | s_part | s_cnt | s_cand
+    auto kernel = src ? roipool3d_canonical_kernel<true> : roipool3d_canonical_kernel<false>;
+    if (lds > 64 * 1024) {
+        const int rc = ensure_dynamic_lds((const void *)kernel, lds, who);
+        if (rc != PRCNN_OK) return rc;
+    }
+    hipLaunchKernelGGL(kernel, grid, dim3(RP_THREADS), lds, (hipStream_t)stream, pts_num, boxes_num, feature_len, sampled_pts_num,
+                       pool_extra_width, (float)((double)pool_extra_width * 2.0), xyz, rois, feats, seg_mask, depth,
+                       reinterpret_cast<float4 *>(pooled), pooled_empty_flag, pooled_cnt, reinterpret_cast<const float4 *>(pxyz),
+                       reinterpret_cast<const float4 *>(aabb), xyz_out, src);
+    return check_launch(who);
+}
+
 extern "C" int prcnn_roipool3d_canonical_xyz(int batch_size, int pts_num, int boxes_num, int feature_len, int sampled_pts_num,
                                              float pool_extra_width, const float *xyz, const float *rois, const float *feats,
                                              const float *seg_mask, const float *depth, float *pooled, int *pooled_empty_flag,
-                                             int *pooled_cnt, const float *pxyz, const float *aabb, float *xyz_out, void *stream);
+                                             int *pooled_cnt, const float *pxyz, const float *aabb, float *xyz_out, void *stream)
+{
+    return canonical_launch("roipool3d_canonical", batch_size, pts_num, boxes_num, feature_len, sampled_pts_num, pool_extra_width, xyz, rois,
+                            feats, seg_mask, depth, pooled, nullptr, pooled_empty_flag, pooled_cnt, pxyz, aabb, xyz_out, stream);
+}
+
 extern "C" int prcnn_roipool3d_canonical(int batch_size, int pts_num, int boxes_num, int feature_len, int sampled_pts_num,
                                          float pool_extra_width, const float *xyz, const float *rois, const float *feats,
                                          const float *seg_mask, const float *depth, float *pooled, int *pooled_empty_flag,
@@ -386,32 +435,14 @@ extern "C" int prcnn_roipool3d_canonical(int batch_size, int pts_num, int boxes_
                                          seg_mask, depth, pooled, pooled_empty_flag, pooled_cnt, pxyz, aabb, nullptr, stream);
 }
 
-extern "C" int prcnn_roipool3d_canonical_xyz(int batch_size, int pts_num, int boxes_num, int feature_len, int sampled_pts_num,
-                                             float pool_extra_width, const float *xyz, const float *rois, const float *feats,
-                                             const float *seg_mask, const float *depth, float *pooled, int *pooled_empty_flag,
-                                             int *pooled_cnt, const float *pxyz, const float *aabb, float *xyz_out, void *stream)
+// The same selection and the same leading chunks without the feature copy: rows (b,m,sampled,8) = [x',y',z',mask | depth,0,0,0],
+// src (b,m,sampled) i32 = each row's row of the (b * n, c) feature matrix (-1: an empty box, zero features).
+extern "C" int prcnn_roipool3d_canonical_src(int batch_size, int pts_num, int boxes_num, int sampled_pts_num, float pool_extra_width,
+                                             const float *xyz, const float *rois, const float *seg_mask, const float *depth, float *rows,
+                                             int *src, int *pooled_empty_flag, int *pooled_cnt, const float *pxyz, const float *aabb,
+                                             float *xyz_out, void *stream)
 {
-    PRCNN_REQUIRE((pxyz == nullptr) == (aabb == nullptr), "roipool3d_canonical: pxyz and aabb go together (prcnn_point_groups)");
-    PRCNN_REQUIRE(!pxyz || (pts_num % 64 == 0 && pts_num <= 65536 && (((uintptr_t)pxyz | (uintptr_t)aabb) & 15) == 0),
-                  "roipool3d_canonical: spatial groups need pts_num a multiple of 64, <= 65536");
-    PRCNN_REQUIRE(batch_size >= 0 && pts_num >= 0 && boxes_num >= 0 && feature_len >= 0 && sampled_pts_num >= 0,
-                  "roipool3d_canonical: bad sizes");
-    PRCNN_REQUIRE(feature_len % 4 == 0, "roipool3d_canonical: feature length %d is not a multiple of 4", feature_len);
-    PRCNN_REQUIRE(sampled_pts_num <= RP_MAX_S, "roipool3d_canonical: sampled_pts_num=%d > %d unsupported", sampled_pts_num, RP_MAX_S);
-    PRCNN_REQUIRE(batch_size <= 65535, "roipool3d_canonical: batch > 65535");
-    if (batch_size == 0 || boxes_num == 0 || sampled_pts_num == 0) return PRCNN_OK;
-    PRCNN_REQUIRE(rois && pooled && pooled_empty_flag && (pts_num == 0 || (xyz && seg_mask && depth && (feats || feature_len == 0))),
-                  "roipool3d_canonical: null pointer");
-    PRCNN_REQUIRE((((uintptr_t)pooled | (uintptr_t)feats) & 15) == 0, "roipool3d_canonical: 16-byte alignment required");
-    dim3 grid(boxes_num, batch_size);
-    const size_t lds = ((size_t)13 * sampled_pts_num + 4 + (pxyz ? pts_num / 64 : 0)) * sizeof(int);   // s_c01 | s_sel | s_part | s_cnt | s_cand
-    if (lds > 64 * 1024) {
-        const int rc = ensure_dynamic_lds((const void *)roipool3d_canonical_kernel, lds, "roipool3d_canonical");
-        if (rc != PRCNN_OK) return rc;
-    }
-    hipLaunchKernelGGL(roipool3d_canonical_kernel, grid, dim3(RP_THREADS), lds, (hipStream_t)stream, pts_num, boxes_num,
-                       feature_len, sampled_pts_num, pool_extra_width, (float)((double)pool_extra_width * 2.0), xyz, rois, feats,
-                       seg_mask, depth, reinterpret_cast<float4 *>(pooled), pooled_empty_flag, pooled_cnt,
-                       reinterpret_cast<const float4 *>(pxyz), reinterpret_cast<const float4 *>(aabb), xyz_out);
-    return check_launch("roipool3d_canonical");
+    PRCNN_REQUIRE(src || batch_size == 0 || boxes_num == 0 || sampled_pts_num == 0, "roipool3d_canonical_src: null pointer");
+    return canonical_launch("roipool3d_canonical_src", batch_size, pts_num, boxes_num, 0, sampled_pts_num, pool_extra_width, xyz, rois, nullptr,
+                            seg_mask, depth, rows, src, pooled_empty_flag, pooled_cnt, pxyz, aabb, xyz_out, stream);
 }

@@ -844,6 +844,42 @@ def rcnn_point_mlp_rows_wrapper(rows, fcol, wu1, bu1, wu2, bu2, wm, bm, wp, bp, 
     return p
 
 
+def pooled_rows_src_wrapper(cnt, rows_per_cloud, src, hdr=None):
+    """pooled_rows_wrapper that also hands on, per listed row, the feature row roipool3d_cuda.forward_canonical_src named for it:
+    src (clouds * rows_per_cloud) i32 -> (rowmap, hdr, featmap), featmap[e] = src[rowmap[e]] (prcnn_pooled_rows_src, the same one launch)."""
+    _chk(torch.int32, cnt, src)
+    clouds = cnt.numel()
+    if src.numel() != clouds * rows_per_cloud:
+        raise ValueError("pooled_rows_src: src must hold clouds * rows_per_cloud entries")
+    rowmap = torch.empty((max(1, clouds * rows_per_cloud),), dtype=torch.int32, device=cnt.device)
+    featmap = torch.empty_like(rowmap)
+    zero = hdr is not None
+    if zero:
+        _chk(torch.int32, hdr)
+        if hdr.numel() != 4:
+            raise ValueError("pooled_rows_src: hdr must hold 4 int32")
+    else:
+        hdr = torch.empty((4,), dtype=torch.int32, device=cnt.device)
+    _lib.call("prcnn_pooled_rows_src", clouds, rows_per_cloud, cnt.data_ptr(), src.data_ptr(), rowmap.data_ptr(), featmap.data_ptr(),
+              hdr.data_ptr(), int(zero), _lib.current_stream(cnt))
+    return rowmap, hdr, featmap
+
+
+def rcnn_point_mlp_rows_src_wrapper(rows, feats, wu1, bu1, wu2, bu2, wm, bm, wp, bp, p, rowlist):
+    """rcnn_point_mlp_rows_wrapper over rows without features: rows (R, ld >= 8) [x',y',z',mask,depth, ...], feats (F, 128) the feature
+    matrix the rows' points live in, rowlist = pooled_rows_src_wrapper's (rowmap, hdr, featmap): listed row e is gathered from
+    feats[featmap[e]], zeros where featmap[e] < 0 (prcnn_rcnn_point_mlp_rows_src).  Same bits as the copying form."""
+    _chk(torch.float32, rows, feats, wu1, bu1, wu2, bu2, wm, bm, wp, bp, p)
+    rowmap, hdr, featmap = rowlist
+    _chk(torch.int32, rowmap, hdr, featmap)
+    if feats.dim() != 2 or feats.size(1) != 128:
+        raise ValueError("rcnn_point_mlp_rows_src: feats must be (F, 128)")
+    _lib.call("prcnn_rcnn_point_mlp_rows_src", rows.size(0), rows.size(1), rows.data_ptr(), feats.data_ptr(), wu1.data_ptr(), bu1.data_ptr(),
+              wu2.data_ptr(), bu2.data_ptr(), wm.data_ptr(), bm.data_ptr(), wp.data_ptr(), bp.data_ptr(), p.data_ptr(),
+              rowmap.data_ptr(), featmap.data_ptr(), hdr.data_ptr(), _lib.current_stream(rows))
+    return p
+
+
 def sa_xyz_mlp_packed_wrapper(new_xyz, xyz, pack, w1, b1, w2, b2, w3, b3, out, out_col, zeroed=False):
     """sa_xyz_mlp_wrapper over the distinct rows of the level's index tensor (BallPack) -- bit-identical results."""
     _chk(torch.float32, w1, b1, w2, b2, w3, b3, out)

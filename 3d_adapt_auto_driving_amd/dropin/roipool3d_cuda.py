@@ -79,6 +79,30 @@ def forward_canonical(xyz, rois, feats, seg_mask, depth, pool_extra_width, poole
     return 1
 
 
+def forward_canonical_src(xyz, rois, seg_mask, depth, pool_extra_width, rows, src, pooled_empty_flag, pooled_cnt=None, groups=None, xyz_out=None):
+    """forward_canonical without the feature copy (prcnn_roipool3d_canonical_src): rows (B,M,S,8) = [x',y',z',mask,depth,0,0,0] of all
+    rows, src (B,M,S) i32 = each row's row of the (B*N, C) feature matrix (wrap-around rows: that of row s % cnt; an empty box: -1).
+    pooled_cnt, groups, xyz_out as there."""
+    _chk(torch.float32, xyz, rois, seg_mask, depth, rows)
+    if groups is not None:
+        _chk(torch.float32, *groups)
+    _chk(torch.int32, pooled_empty_flag, src)
+    if pooled_cnt is not None:
+        _chk(torch.int32, pooled_cnt)
+    B, M, S = xyz.size(0), rois.size(1), rows.size(2)
+    if tuple(rows.shape) != (B, M, S, 8) or tuple(src.shape) != (B, M, S):
+        raise RuntimeError("roipool3d_cuda.forward_canonical_src: rows must be (B, M, S, 8) and src (B, M, S)")
+    if xyz_out is not None:
+        _chk(torch.float32, xyz_out)
+        if tuple(xyz_out.shape) != (B, M, S, 3):
+            raise RuntimeError("roipool3d_cuda.forward_canonical_src: xyz_out must be (B, M, S, 3)")
+    _lib.call("prcnn_roipool3d_canonical_src", B, xyz.size(1), M, S, float(pool_extra_width), xyz.data_ptr(), rois.data_ptr(),
+              seg_mask.data_ptr(), depth.data_ptr(), rows.data_ptr(), src.data_ptr(), pooled_empty_flag.data_ptr(), _lib.ptr(pooled_cnt),
+              None if groups is None else groups[0].data_ptr(), None if groups is None else groups[1].data_ptr(),
+              _lib.ptr(xyz_out), _lib.current_stream(xyz))
+    return 1
+
+
 def _chk_host(dtype, *tensors):
     for t in tensors:
         if t.is_cuda:

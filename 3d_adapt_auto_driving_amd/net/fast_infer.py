@@ -20,6 +20,7 @@ kernels.  Parity is tested against the reference fixtures with the 1e-4 box tole
 """
 import contextlib
 import os
+import types
 import typing
 
 import torch
@@ -34,6 +35,7 @@ from .. import iou3d_utils
 
 # The engine's switches: what each selects, and what its other setting is (A/B).  Measurements and history: DESIGN.md section 12.
 USE_ROIPOOL_CANONICAL = True   # RCNN input assembly through roipool3d_canonical_kernel; False: the torch-op sequence
+USE_POOL_BY_NAME = True        # ... its rows name their RPN features, the entrance gathers them at the source; False: the rows carry a copy (same bits)
 USE_RCNN_POINT_MLP = True      # RCNN entrance chain through csrc/rcnn_entrance.hip; False: library GEMMs + concat
 USE_XYZ_MLP = True             # coordinates-only SA scales through csrc/sa_xyz_mlp.hip; False: the grouped GEMM chain
 # SA levels over the DISTINCT grouped rows only (csrc/sa_packed.hip, same bits); PRCNN_NO_PACK=1: all nsample rows (csrc/sa_mlp_fused.hip)
@@ -1132,18 +1134,36 @@ class FastPointRCNN:
         w = mlp.wide
         return bool(below.out_width == w.wf.shape[0] and ext.sa_wide_fused3_supported(w.wf.shape[0], w.wf.shape[1], w.w2.shape[1], w.w3.shape[1]))
 
+    def _pool_by_name_ok(self, feats):
+        """may the pooled rows NAME their features (row of the RPN's feature matrix per pooled row: forward_canonical_src ->
+        pooled_rows_src_wrapper -> rcnn_point_mlp_rows_src_wrapper) instead of carrying a copy of them?  Only the fused entrance over
+        the row list reads the copy, and it gathers at the source as well.  Asked of the drop-in modules themselves: a proxy in their
+        place (the call-by-call oracle shadow of the test suite, a call timer) is shown the copying entries, which every stand-in knows."""
+        rp, ext = roipool3d_utils.roipool3d_cuda, pu.pointnet2
+        return bool(USE_POOL_BY_NAME and feats.shape[2] == 128 and feats.is_contiguous()
+                    and isinstance(rp, types.ModuleType) and isinstance(ext, types.ModuleType)
+                    and has_entry(rp, "forward_canonical_src") and has_entry(ext, "pooled_rows_wrapper")
+                    and has_entry(ext, "pooled_rows_src_wrapper") and has_entry(ext, "rcnn_point_mlp_rows_src_wrapper"))
+
     def _pool_canonical(self, xyz, feats, seg_mask, pts_depth, rois, depth_norm, groups):
         """enlarge + pool + canonical transform + aligned row layout [x',y',z',mask,depth,0,0,0 | feats] in ONE kernel
-        -> (pooled (B,M,P,8+C), distinct points per RoI or None, the rows' coordinates as dense clouds, entrance rows, feature rows)"""
+        -> (pooled (B,M,P,8+C), distinct points per RoI or None, the rows' coordinates as dense clouds, entrance rows, feature rows);
+        by name (`_pool_by_name_ok`): pooled (B,M,P,8), and in place of the feature rows ((B*N, C) feature matrix, (B*M*P) i32 row of it per pooled row)"""
         R = self.cfg.RCNN
         B, M, P, W = rois.shape[0], rois.shape[1], R.NUM_POINTS, 8 + feats.shape[2]
-        pooled = torch.empty((B, M, P, W), dtype=torch.float32, device=xyz.device)
         empty = torch.empty((B, M), dtype=torch.int32, device=xyz.device)
         dedup = USE_POOL_DEDUP and USE_PACKED and USE_RCNN_POINT_MLP and P % 64 == 0 and self._point_mlp_ok()
         pooled_cnt = torch.empty((B, M), dtype=torch.int32, device=xyz.device) if dedup else None
         # ... and the rows' coordinates once more as dense clouds (what sampling and ball queries read; was a strided copy)
         xyz_dense = torch.empty((B, M, P, 3), dtype=torch.float32, device=xyz.device)
         depth_norm = depth_norm if depth_norm is not None else (pts_depth / 70.0 - 0.5).contiguous()
+        if dedup and self._pool_by_name_ok(feats):
+            pooled = torch.empty((B, M, P, 8), dtype=torch.float32, device=xyz.device)
+            src = torch.empty((B, M, P), dtype=torch.int32, device=xyz.device)
+            roipool3d_utils.roipool3d_cuda.forward_canonical_src(xyz, rois.contiguous(), seg_mask.contiguous(), depth_norm, R.POOL_EXTRA_WIDTH,
+                                                                 pooled, src, empty, pooled_cnt, groups, xyz_dense)
+            return pooled, pooled_cnt, xyz_dense, pooled.view(B * M * P, 8), (feats.view(-1, feats.shape[2]), src.view(-1))
+        pooled = torch.empty((B, M, P, W), dtype=torch.float32, device=xyz.device)
         roipool3d_utils.roipool3d_cuda.forward_canonical(xyz, rois.contiguous(), feats, seg_mask.contiguous(), depth_norm, R.POOL_EXTRA_WIDTH,
                                                          pooled, empty, pooled_cnt, groups, xyz_dense)
         rows = pooled.view(B * M * P, W)
@@ -1268,13 +1288,19 @@ class FastPointRCNN:
             pooled, pooled_cnt, xyz_dense, a, rpn_part = self._pool_torch(xyz, feats, seg_mask, pts_depth, rois, nin)
         B, M, P, W = pooled.shape
         rows = pooled.view(B * M * P, W)
-        point_mlp = bool(USE_RCNN_POINT_MLP and W == 136 and rows.shape[0] % 64 == 0 and self._point_mlp_ok())
+        by_name = isinstance(rpn_part, tuple)                                  # rows of 8 floats; rpn_part = (feature matrix, row of it per pooled row)
+        point_mlp = bool(USE_RCNN_POINT_MLP and (W == 136 or by_name) and rows.shape[0] % 64 == 0 and self._point_mlp_ok())
         use_rows = bool(point_mlp and pooled_cnt is not None and has_entry(ext, "pooled_rows_wrapper"))
         cur_xyz = xyz_dense.view(B * M, P, 3) if xyz_dense is not None else pooled.view(B * M, P, W)[:, :, 0:3].contiguous()
         # one zero fill for this stage: the headers of its three row lists and the pooled outputs of its levels (see ZeroArena)
         zarena = ZeroArena(("rcnn", B, M, P, str(rows.device)), rows.device)
         zhdr = (lambda: (zarena.take((4,), torch.int32),)) if getattr(ext, "IS_HIP_EXTENSION", False) else (lambda: ())   # positional (7th) argument
-        rowlist = ext.pooled_rows_wrapper(pooled_cnt.view(-1), P, *zhdr()) if use_rows else None       # the distinct pooled rows of all RoIs, back to back
+        rowlist = None
+        if by_name:                            # the distinct pooled rows of all RoIs, back to back, each with the feature row it stands for
+            rowlist = ext.pooled_rows_src_wrapper(pooled_cnt.view(-1), P, rpn_part[1], *zhdr())
+            rpn_part = (rpn_part[0], rowlist[2])
+        elif use_rows:
+            rowlist = ext.pooled_rows_wrapper(pooled_cnt.view(-1), P, *zhdr())
         # representative map of the CURRENT level's points (None: every point counts as distinct): which of them are exact copies
         # of one another.  Level 0: pooled point k >= count is a copy of k % count (`limit`); deeper: the centres the sampling
         # picked from copies of one source are copies of one another -- coordinates, ball and therefore features (dup_rep).  The
@@ -1316,7 +1342,9 @@ class FastPointRCNN:
             (wm, bm, _), = self.merge_down.layers
             wf, _, b1 = self.rcnn_sa[0].mlp.split
             P_pre = torch.empty((rows.shape[0], 128), dtype=torch.float32, device=rows.device)
-            if rg.get("rowlist") is not None:
+            if rg.get("rowlist") is not None and len(rg["rowlist"]) == 3:         # rows of 8 floats: the features are gathered where they are
+                ext.rcnn_point_mlp_rows_src_wrapper(rows, rg["rpn_part"][0], wu1, bu1, wu2, bu2, wm, bm, wf, b1, P_pre, rg["rowlist"])
+            elif rg.get("rowlist") is not None:
                 ext.rcnn_point_mlp_rows_wrapper(rows, 8, wu1, bu1, wu2, bu2, wm, bm, wf, b1, P_pre, rg["rowlist"])     # only P, only the distinct rows
             else:
                 ext.rcnn_point_mlp_wrapper(rows, 8, wu1, bu1, wu2, bu2, wm, bm, wf, b1, None, None, P_pre)   # only P is needed

@@ -425,6 +425,18 @@ int prcnn_pooled_rows(int clouds, int rows_per_cloud, const int *cnt, int *rowma
 int prcnn_rcnn_point_mlp_rows(long r, int ld, int fcol, const float *rows, const float *wu1, const float *bu1,
                               const float *wu2, const float *bu2, const float *wm, const float *bm, const float *wp,
                               const float *bp, float *p, const int *rowmap, const unsigned int *hdr, void *stream);
+/* The list and the chain over pooled rows that carry NO features (prcnn_roipool3d_canonical_src: rows of 8 floats and src, each row's
+ * row of the RPN's (points, 128) feature matrix).  prcnn_pooled_rows_src = prcnn_pooled_rows that also writes featmap[e] = src[rowmap[e]]
+ * in the same pass (src, featmap: both or neither; src (clouds * rows_per_cloud) i32).  prcnn_rcnn_point_mlp_rows_src: rows (r, ld >= 8)
+ * [x',y',z',mask,depth, ...]; list entry e takes its 128 features from row featmap[e] of feats, zeros where featmap[e] < 0 (the one listed
+ * row of an empty box).  Nothing is copied between the RPN's feature matrix and the chain; per row the arithmetic is
+ * prcnn_rcnn_point_mlp's: same bits. */
+int prcnn_pooled_rows_src(int clouds, int rows_per_cloud, const int *cnt, const int *src, int *rowmap, int *featmap, unsigned int *hdr,
+                          int hdr_is_zero, void *stream);
+int prcnn_rcnn_point_mlp_rows_src(long r, int ld, const float *rows, const float *feats, const float *wu1, const float *bu1,
+                                  const float *wu2, const float *bu2, const float *wm, const float *bm, const float *wp,
+                                  const float *bp, float *p, const int *rowmap, const int *featmap, const unsigned int *hdr,
+                                  void *stream);
 
 /* One 128-wide shared-MLP / Conv1d layer (pytorch_utils.py:35-101 with BN folded) on the same tiled MFMA kernel:
  * out (r,128) = act(A0 w[0:128] [+ A1 w[128:256]] + bias), r % 64 == 0; A0 = src0 rows (128 floats at column col0, row
@@ -556,6 +568,14 @@ int prcnn_roipool3d_canonical_xyz(int batch_size, int pts_num, int boxes_num, in
                                   float pool_extra_width, const float *xyz, const float *rois, const float *feats,
                                   const float *seg_mask, const float *depth, float *pooled, int *pooled_empty_flag,
                                   int *pooled_cnt, const float *pxyz, const float *aabb, float *xyz_out, void *stream);
+/* The form that copies no features: the same selection, rows (b,m,sampled,8) = [x', y', z', seg mask, depth, 0, 0, 0] of ALL rows, and
+ * src (b,m,sampled) i32 = the row of the (b * pts_num, c) feature matrix that each pooled row stands for: b * pts_num + point for the
+ * distinct rows, the value of row s % cnt for the wrap-around rows, -1 in every slot of an empty box (whose features are zero rows).
+ * pooled_cnt, pooled_empty_flag, pxyz / aabb, xyz_out as above.  The reader gathers at the source (prcnn_rcnn_point_mlp_rows_src). */
+int prcnn_roipool3d_canonical_src(int batch_size, int pts_num, int boxes_num, int sampled_pts_num, float pool_extra_width,
+                                  const float *xyz, const float *rois, const float *seg_mask, const float *depth, float *rows,
+                                  int *src, int *pooled_empty_flag, int *pooled_cnt, const float *pxyz, const float *aabb,
+                                  float *xyz_out, void *stream);
 /* Spatial groups of clouds xyz (b,n,3), n % 64 == 0, n <= 65536: pxyz (b,n,4) = the points in Morton order over (x,z) with the
  * original index in the 4th lane (int bits), aabb (b, n/64, 2, 4) = min / max corner of every 64-point group.  Any box-vs-cloud
  * sweep (RoI pooling here) can cull by group.  Not part of the reference ABI. */

@@ -7,10 +7,10 @@ os.environ.setdefault("DEBUG_CLR_GRAPH_PACKET_CAPTURE", "0")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TARGETS = [("none", None, None), ("fps_new_xyz (sampling, 32 CUs)", "pointnet2", "fps_new_xyz_wrapper"),
            ("rpn_tail_lin_boxes (MFMA, whole chip)", "pointnet2", "rpn_tail_lin_boxes_wrapper"),
-           ("forward_canonical (RoI pooling, HBM)", "roipool3d", "forward_canonical"),
+           ("forward_canonical_src (RoI pooling, HBM)", "roipool3d", "forward_canonical_src"),
            ("rcnn_roi_geometry_packs (a wave per RoI: sampling, ball queries, the three row lists)", "pointnet2", "rcnn_roi_geometry_packs_wrapper"),
            ("rpn_proposals_boxes (sort, bands, NMS)", "iou3d", "rpn_proposals_boxes"),
-           ("rcnn_point_mlp_rows (entrance, MFMA)", "pointnet2", "rcnn_point_mlp_rows_wrapper"),
+           ("rcnn_point_mlp_rows_src (entrance, MFMA)", "pointnet2", "rcnn_point_mlp_rows_src_wrapper"),
            ("sa_wide_fused3 (MFMA)", "pointnet2", "sa_wide_fused3_wrapper"),
            ("ball_query_full (grid build + query)", "pointnet2", "ball_query_full_wrapper"),
            ("three_nn_weights", "pointnet2", "three_nn_weights_wrapper"),
