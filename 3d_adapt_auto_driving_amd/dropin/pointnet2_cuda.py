@@ -196,6 +196,63 @@ def query_and_group_wrapper(b, n, m, c, radius, nsample, new_xyz, xyz, features,
     return 1
 
 
+# -- extension beyond the reference module: the order-fixed backward (csrc/scatter_plan.hip) -------
+class ScatterPlan:
+    """The transposed index of an operator's idx over n destinations (prcnn_scatter_plan): offsets (b, n+1) i32 and entries
+    (b, slots) i32, per destination the ascending list of the slots that name it; device-resident, no host sync."""
+    __slots__ = ("offsets", "entries", "n", "slots")
+
+    def tensors(self):
+        return (self.offsets, self.entries)
+
+    def record_stream(self, stream):
+        for t in self.tensors():
+            t.record_stream(stream)
+
+
+def scatter_plan_wrapper(idx, n):
+    """idx (b, ...) i32 -- (b,npoint,nsample), (b,npoint) or (b,n_unknown,3), flattened per cloud -- -> ScatterPlan over n
+    destinations.  Values outside [0, n) belong to no list."""
+    _chk(torch.int32, idx)
+    b, n = idx.shape[0], int(n)
+    slots = 1
+    for d in idx.shape[1:]:
+        slots *= int(d)
+    pl = ScatterPlan()
+    pl.n, pl.slots = n, slots
+    pl.offsets = torch.empty((b, n + 1), dtype=torch.int32, device=idx.device)
+    pl.entries = torch.empty((b, slots), dtype=torch.int32, device=idx.device)
+    work = torch.empty((_lib.call("prcnn_scatter_plan_workspace", b, n, slots),), dtype=torch.int32, device=idx.device)
+    _lib.call("prcnn_scatter_plan", b, n, slots, idx.data_ptr(), pl.offsets.data_ptr(), pl.entries.data_ptr(), work.data_ptr(),
+              _lib.current_stream(idx))
+    return pl
+
+
+def group_points_grad_ordered_wrapper(b, c, n, slots, c_total, c0, grad_out, plan, grad_points):
+    """grad_points (b,c,n) <- the ordered sums of channels c0 .. c0+c-1 of grad_out (b,c_total,slots) over plan's lists; every
+    element is written (grad_points may be torch.empty).  The gather operator is slots = npoint."""
+    _chk(torch.float32, grad_out, grad_points); _chk(torch.int32, *plan.tensors())
+    if plan.n != n or plan.slots != slots or plan.offsets.shape[0] != b:
+        raise ValueError("group_points_grad_ordered: the plan was built for another shape")
+    if grad_out.numel() != b * c_total * slots or grad_points.numel() != b * c * n:
+        raise ValueError("group_points_grad_ordered: tensor sizes do not match b, c, n, slots, c_total")
+    _lib.call("prcnn_group_points_grad_ordered", b, c, n, slots, c_total, c0, grad_out.data_ptr(), plan.offsets.data_ptr(),
+              plan.entries.data_ptr(), grad_points.data_ptr(), _lib.current_stream(grad_out))
+    return 1
+
+
+def three_interpolate_grad_ordered_wrapper(b, c, n, m, grad_out, weight, plan, grad_points):
+    """grad_points (b,c,m) <- the ordered sums of grad_out (b,c,n)[.., s / 3] * weight (b,n,3)[s] over the lists of plan (built
+    from idx (b,n,3) over m destinations); every element is written."""
+    _chk(torch.float32, grad_out, weight, grad_points); _chk(torch.int32, *plan.tensors())
+    if plan.n != m or plan.slots != 3 * n or plan.offsets.shape[0] != b:
+        raise ValueError("three_interpolate_grad_ordered: the plan was built for another shape")
+    if grad_out.numel() != b * c * n or weight.numel() != b * n * 3 or grad_points.numel() != b * c * m:
+        raise ValueError("three_interpolate_grad_ordered: tensor sizes do not match b, c, n, m")
+    _lib.call("prcnn_three_interpolate_grad_ordered", b, c, n, m, grad_out.data_ptr(), weight.data_ptr(), plan.offsets.data_ptr(),
+              plan.entries.data_ptr(), grad_points.data_ptr(), _lib.current_stream(grad_out))
+
+
 # -- extension beyond the reference module: shared-MLP epilogues -----------------------------------
 def bias_relu_inplace_wrapper(x, bias):
     """x (B, C, ...) in place: x = relu(x + bias[c])."""

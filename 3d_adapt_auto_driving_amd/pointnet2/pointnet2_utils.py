@@ -7,6 +7,8 @@ exactly where the reference has ``import pointnet2_cuda as pointnet2`` (:7).  Ou
 allocated on the inputs' device with the same dtypes/shapes the reference allocates; there is
 no CPU implementation here -- CPU tensors are rejected by the extension.
 """
+import contextlib
+
 import torch
 import torch.nn as nn
 from torch.autograd import Function
@@ -18,6 +20,45 @@ from ..dropin import pointnet2_cuda as pointnet2
 # the reference's Python gets from the drop-in modules (eval_rcnn.reference_api_only(); bench.py config.dropin_module_scenes_per_s).
 # Also taken when the extension module offers no fused entry (the compiled dropin_native modules export the reference's 9 names).
 REFERENCE_ORDER = False
+
+# True: the backward of GatherOperation, GroupingOperation, ThreeInterpolate and the fused QueryAndGroup sums every destination's
+# contributions in a FIXED order (the index transposed once per call -- scatter_plan_wrapper -- then a per-destination sum:
+# csrc/scatter_plan.hip) instead of one float atomicAdd per slot in arrival order: the same input gives the same bits.  The same
+# path is taken while torch.are_deterministic_algorithms_enabled().  An extension module without the ordered entries (the compiled
+# dropin_native modules export the reference's nine names) then RAISES: there is no silent return to the atomic kernels.
+# False (default): the reference's kernels, exactly as before.
+ORDERED_BACKWARD = False
+
+
+@contextlib.contextmanager
+def ordered_backward(flag=True):
+    """with ordered_backward(): loss.backward() -- ORDERED_BACKWARD for the duration (read when backward RUNS, not at forward)"""
+    global ORDERED_BACKWARD
+    saved, ORDERED_BACKWARD = ORDERED_BACKWARD, bool(flag)
+    try:
+        yield
+    finally:
+        ORDERED_BACKWARD = saved
+
+
+def _ordered():
+    return ORDERED_BACKWARD or torch.are_deterministic_algorithms_enabled()
+
+
+def _ordered_entry(name):
+    fn = getattr(pointnet2, name, None)
+    if fn is None:
+        raise RuntimeError("ordered backward is selected but extension module %s has no entry %r (the atomic kernels are never "
+                           "taken in its place)" % (getattr(pointnet2, "__name__", pointnet2), name))
+    return fn
+
+
+def _plan_of(ctx, idx, n):
+    """the scatter plan of a Function's saved index, built on the first backward that needs it"""
+    plan = getattr(ctx, "scatter_plan", None)
+    if plan is None:
+        plan = ctx.scatter_plan = _ordered_entry("scatter_plan_wrapper")(idx, n)
+    return plan
 
 
 def _contig(*ts):
@@ -61,6 +102,11 @@ class GatherOperation(Function):
     def backward(ctx, grad_out):
         idx, C, N = ctx.for_backwards
         B, npoint = idx.size()
+        if _ordered():
+            grad_features = torch.empty((B, C, N), dtype=torch.float32, device=grad_out.device)
+            _ordered_entry("group_points_grad_ordered_wrapper")(B, C, N, npoint, C, 0, grad_out.contiguous(), _plan_of(ctx, idx, N),
+                                                                grad_features)
+            return grad_features, None
         grad_features = torch.zeros((B, C, N), dtype=torch.float32, device=grad_out.device)
         pointnet2.gather_points_grad_wrapper(B, C, N, npoint, grad_out.contiguous(), idx, grad_features)
         return grad_features, None
@@ -106,6 +152,11 @@ class ThreeInterpolate(Function):
     def backward(ctx, grad_out):
         idx, weight, m = ctx.three_interpolate_for_backward
         B, c, n = grad_out.size()
+        if _ordered():
+            grad_features = torch.empty((B, c, m), dtype=torch.float32, device=grad_out.device)
+            _ordered_entry("three_interpolate_grad_ordered_wrapper")(B, c, n, m, grad_out.contiguous(), weight, _plan_of(ctx, idx, m),
+                                                                     grad_features)
+            return grad_features, None, None
         grad_features = torch.zeros((B, c, m), dtype=torch.float32, device=grad_out.device)
         pointnet2.three_interpolate_grad_wrapper(B, c, n, m, grad_out.contiguous(), idx, weight, grad_features)
         return grad_features, None, None
@@ -130,6 +181,11 @@ class GroupingOperation(Function):
     def backward(ctx, grad_out):
         idx, N = ctx.for_backwards
         B, C, npoint, nsample = grad_out.size()
+        if _ordered():
+            grad_features = torch.empty((B, C, N), dtype=torch.float32, device=grad_out.device)
+            _ordered_entry("group_points_grad_ordered_wrapper")(B, C, N, npoint * nsample, C, 0, grad_out.contiguous(),
+                                                                _plan_of(ctx, idx, N), grad_features)
+            return grad_features, None
         grad_features = torch.zeros((B, C, N), dtype=torch.float32, device=grad_out.device)
         pointnet2.group_points_grad_wrapper(B, C, N, npoint, nsample, grad_out.contiguous(), idx, grad_features)
         return grad_features, None
@@ -182,6 +238,12 @@ class _QueryAndGroupFused(Function):
         if C == 0:
             return None, None, None, None, None
         B, _, npoint, nsample = grad_out.size()
+        if _ordered():
+            # grad_out whole: the entry reads channels 3 .. 3+C-1 of the (B, 3+C, slots) tensor in place (no copy of [:, 3:])
+            grad_features = torch.empty((B, C, N), dtype=torch.float32, device=grad_out.device)
+            _ordered_entry("group_points_grad_ordered_wrapper")(B, C, N, npoint * nsample, 3 + C, 3, grad_out.contiguous(),
+                                                                _plan_of(ctx, idx, N), grad_features)
+            return None, None, None, None, grad_features
         g = grad_out[:, 3:].contiguous()
         grad_features = torch.zeros((B, C, N), dtype=torch.float32, device=grad_out.device)
         pointnet2.group_points_grad_wrapper(B, C, N, npoint, nsample, g, idx, grad_features)

@@ -148,6 +148,39 @@ int prcnn_query_and_group(int b, int n, int m, int c, float radius, int nsample,
                           const float *new_xyz, const float *xyz, const float *features,
                           int *idx, float *out, void *stream);
 
+/* ---- the order-fixed backward of grouping, gather and three_interpolate (csrc/scatter_plan.hip; not in the
+ *      reference ABI).  The three gradients above are scatter-adds through float atomics: the order of a destination's sum is arrival
+ *      order.  Here the index is transposed once per call and every destination sums its own list in a fixed order: no atomics on
+ *      floats, the same input gives the same bits. ------------------------------------------------------------------------------- */
+
+/* The transposed index ("scatter plan") of idx (b,slots) i32 over n destinations per cloud -- any of the three operators' index
+ * tensors, flattened per cloud: (b, npoint*nsample), (b, npoint) or (b, 3*n_unknown):
+ *   offsets (b,n+1) i32: offsets[i][k+1] - offsets[i][k] = the number of slots s with idx[i][s] == k;
+ *   entries (b,slots) i32: entries[i][offsets[i][k] .. offsets[i][k+1]) = those slots in ASCENDING order (per cloud the stable argsort
+ *   of idx[i], restricted to the values in range); what lies behind offsets[i][n] is unspecified.
+ * A slot whose value lies outside [0, n) belongs to no list; nothing is read or written out of bounds for any index content.  A pure
+ * function of idx.  No host read and no allocation: work holds prcnn_scatter_plan_workspace(b, n, slots) i32 words (contents
+ * arbitrary on entry), so the call is safe on any stream and under graph capture.  b <= 65535, b * n < 2^31. */
+int prcnn_scatter_plan_workspace(int b, int n, int slots);
+int prcnn_scatter_plan(int b, int n, int slots, const int *idx, int *offsets, int *entries, int *work, void *stream);
+
+/* The ordered sums over a plan.  ARITHMETIC CONTRACT: a destination's list is cut into consecutive chunks of PRCNN_SCATTER_CHUNK
+ * entries; each chunk is summed left to right in f32 starting from +0.0f; the chunk sums are then added left to right starting from
+ * +0.0f (one rounding per operation, no fma).  EVERY element of grad_points is written -- an empty list gives +0.0f -- so the caller
+ * does not zero-fill.  (The chunk rule lets an implementation split a long list over waves and combine the partials in chunk order;
+ * it obliges none to.  A cloud with every slot on one point is summed correctly; its speed is no goal.) */
+enum { PRCNN_SCATTER_CHUNK = 256 };
+/* grad_points (b,c,n)[i][ch][k] = ordered sum over s in list k of grad_out (b,c_total,slots)[i][c0 + ch][s]: the gradient of
+ * prcnn_group_points (slots = npoints * nsample, c_total = c, c0 = 0), of the feature channels of prcnn_query_and_group (its whole
+ * output gradient with c_total = 3 + c, c0 = 3: nothing is copied) and of prcnn_gather_points (slots = npoints). */
+int prcnn_group_points_grad_ordered(int b, int c, int n, int slots, int c_total, int c0, const float *grad_out, const int *offsets,
+                                    const int *entries, float *grad_points, void *stream);
+/* The gradient of prcnn_three_interpolate: grad_out (b,c,n), weight (b,n,3), the plan of idx (b,3*n) over m destinations -- slot s is
+ * unknown point s / 3, neighbour s % 3 -- -> grad_points (b,c,m)[i][ch][k] = ordered sum over s in list k of the f32 product
+ * grad_out[i][ch][s / 3] * weight[i][s]. */
+int prcnn_three_interpolate_grad_ordered(int b, int c, int n, int m, const float *grad_out, const float *weight, const int *offsets,
+                                         const int *entries, float *grad_points, void *stream);
+
 /* ---- shared-MLP epilogues (fused forms of pytorch_utils.py Conv2d -> BN(eval) -> ReLU and of
  *      the max over nsample of pointnet2_modules.py:41-44; not in the reference ABI) ------------ */
 
