@@ -253,6 +253,97 @@ def three_interpolate_grad_ordered_wrapper(b, c, n, m, grad_out, weight, plan, g
               plan.entries.data_ptr(), grad_points.data_ptr(), _lib.current_stream(grad_out))
 
 
+# -- extension beyond the reference module: the order-fixed training layer (csrc/train_layer.hip) --
+def _train_layer_shape(what, x, w):
+    """x (b, cin, ...) and w (cout, cin, 1...) -> (b, cin, cout, p)"""
+    if x.dim() < 3 or w.dim() < 2 or x.shape[1] != w.shape[1] or w.numel() != w.shape[0] * w.shape[1]:
+        raise ValueError("%s: x %s and w %s are no 1x1 convolution" % (what, tuple(x.shape), tuple(w.shape)))
+    b, cin, cout = int(x.shape[0]), int(x.shape[1]), int(w.shape[0])
+    if x.numel() == 0:
+        raise ValueError("%s: empty input %s" % (what, tuple(x.shape)))
+    return b, cin, cout, x.numel() // (b * cin)
+
+
+def _train_layer_vectors(what, cout, *vectors):
+    for v in vectors:
+        if v is not None and v.numel() != cout:
+            raise ValueError("%s: a per-channel tensor holds %d values, the layer has %d channels" % (what, v.numel(), cout))
+
+
+def train_layer_workspace_wrapper(b, cin, cout, p):
+    """-> (f64 elements of `work`, f32 elements of the backward's `dw_work`)"""
+    stat, dw = ctypes.c_long(0), ctypes.c_long(0)
+    _lib.call("prcnn_train_layer_workspace", b, cin, cout, p, ctypes.byref(stat), ctypes.byref(dw))
+    return stat.value, dw.value
+
+
+def train_layer_forward_wrapper(x, w, gamma, beta, eps, momentum, running_mean, running_var, relu):
+    """One conv(1x1) + BatchNorm(batch statistics) + ReLU block forward.  x (b, cin, ...) f32, w (cout, cin[, 1[, 1]]).
+    gamma given: -> (y, z, stats (2, cout) f64 = mean, rstd); running_mean / running_var (or None) are updated in place.
+    gamma None: beta is the bias (or None) -> (y, None, None) with y = act(z + bias)."""
+    what = "train_layer_forward"
+    _chk(torch.float32, x, w)
+    b, cin, cout, p = _train_layer_shape(what, x, w)
+    bn = gamma is not None
+    per_channel = [t for t in (gamma, beta, running_mean, running_var) if t is not None]
+    _chk(torch.float32, *per_channel)
+    _train_layer_vectors(what, cout, *per_channel)
+    y = torch.empty((b, cout) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
+    if not bn:
+        _lib.call("prcnn_train_layer_forward", b, cin, cout, p, 0, int(bool(relu)), x.data_ptr(), w.data_ptr(), None, _lib.ptr(beta), 0.0, 0.0,
+                  None, None, None, y.data_ptr(), None, None, _lib.current_stream(x))
+        return y, None, None
+    if beta is None:
+        raise ValueError("%s: BatchNorm needs gamma and beta" % what)
+    if b * p == 1:
+        raise ValueError("%s: expected more than 1 value per channel when training, got input size %s" % (what, tuple(x.shape)))
+    z = torch.empty_like(y)
+    stats = torch.empty((2, cout), dtype=torch.float64, device=x.device)
+    work = torch.empty((train_layer_workspace_wrapper(b, cin, cout, p)[0],), dtype=torch.float64, device=x.device)
+    _lib.call("prcnn_train_layer_forward", b, cin, cout, p, 1, int(bool(relu)), x.data_ptr(), w.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+              float(eps), float(momentum), _lib.ptr(running_mean), _lib.ptr(running_var), z.data_ptr(), y.data_ptr(), stats.data_ptr(),
+              work.data_ptr(), _lib.current_stream(x))
+    return y, z, stats
+
+
+def train_layer_backward_wrapper(dy, x, w, zy, gamma, beta, stats, relu, need_dx, need_dw, need_dbias=True):
+    """The block's backward from dy, the layer's input x and what the forward returned (zy = z with BatchNorm, y without; stats).
+    -> (dx | None, dw | None, dgamma | None, dbeta or dbias | None): dx only with need_dx, dw only with need_dw, the bias gradient of
+    the block without BatchNorm only with need_dbias."""
+    what = "train_layer_backward"
+    _chk(torch.float32, dy, x, w)
+    b, cin, cout, p = _train_layer_shape(what, x, w)
+    if dy.numel() != b * cout * p:
+        raise ValueError("%s: dy %s does not match x %s and w %s" % (what, tuple(dy.shape), tuple(x.shape), tuple(w.shape)))
+    bn = gamma is not None
+    relu = bool(relu)
+    if bn or relu:
+        if zy is None or zy.numel() != dy.numel():
+            raise ValueError("%s: the saved %s does not match dy %s" % (what, "z" if bn else "y", tuple(dy.shape)))
+        _chk(torch.float32, zy)
+    dev = x.device
+    dgamma = dbeta = None
+    if bn:
+        if beta is None or stats is None or stats.numel() != 2 * cout:
+            raise ValueError("%s: BatchNorm needs gamma, beta and stats (2, %d)" % (what, cout))
+        _chk(torch.float32, gamma, beta); _chk(torch.float64, stats)
+        _train_layer_vectors(what, cout, gamma, beta)
+        dgamma = torch.empty((cout,), dtype=torch.float32, device=dev)
+        dbeta = torch.empty((cout,), dtype=torch.float32, device=dev)
+    elif need_dbias:
+        dbeta = torch.empty((cout,), dtype=torch.float32, device=dev)
+    stat_n, dw_n = train_layer_workspace_wrapper(b, cin, cout, p)
+    work = torch.empty((stat_n,), dtype=torch.float64, device=dev) if (bn or relu or need_dbias) else None
+    dz = torch.empty_like(dy) if (bn or relu) else None
+    dx = torch.empty_like(x) if need_dx else None
+    dw = torch.empty_like(w) if need_dw else None
+    dw_work = torch.empty((dw_n,), dtype=torch.float32, device=dev) if need_dw else None
+    _lib.call("prcnn_train_layer_backward", b, cin, cout, p, int(bn), int(relu), dy.data_ptr(), x.data_ptr(), w.data_ptr(), _lib.ptr(zy),
+              _lib.ptr(gamma) if bn else None, _lib.ptr(beta) if bn else None, _lib.ptr(stats) if bn else None, _lib.ptr(dz), _lib.ptr(dx),
+              _lib.ptr(dw), _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(work), _lib.ptr(dw_work), _lib.current_stream(dy))
+    return dx, dw, dgamma, dbeta
+
+
 # -- extension beyond the reference module: shared-MLP epilogues -----------------------------------
 def bias_relu_inplace_wrapper(x, bias):
     """x (B, C, ...) in place: x = relu(x + bias[c])."""

@@ -4,7 +4,27 @@
 ``activation`` (``in`` for instance norm), and ``bn`` is itself a one-child Sequential named
 ``bn`` -- hence checkpoint keys like ``...layer0.bn.bn.running_mean``.
 """
+import contextlib
+
 import torch.nn as nn
+
+# True: a conv block in training mode that train_layer.covers() -- 1x1 convolution, BatchNorm on batch statistics or none, ReLU or
+# none, on a CUDA f32 input -- runs forward AND backward on the project's own order-fixed kernels (train_layer.TrainLayer over
+# csrc/train_layer.hip: sums of a fixed shape, no float atomics, the same input gives the same bits) instead of torch's Conv /
+# BatchNorm / ReLU modules.  The parameters, the BatchNorm buffers and the state_dict are the same objects either way.  An extension
+# module without the entries then RAISES.  False (default): the nn.Sequential forward, exactly as before.
+FUSED_TRAIN_LAYERS = False
+
+
+@contextlib.contextmanager
+def fused_train_layers(flag=True):
+    """with fused_train_layers(): loss = model(x) ... -- FUSED_TRAIN_LAYERS for the duration (read when a block's forward runs)"""
+    global FUSED_TRAIN_LAYERS
+    saved, FUSED_TRAIN_LAYERS = FUSED_TRAIN_LAYERS, bool(flag)
+    try:
+        yield
+    finally:
+        FUSED_TRAIN_LAYERS = saved
 
 
 class _Norm(nn.Sequential):
@@ -54,6 +74,13 @@ class _ConvBlock(nn.Sequential):
         parts = extras + [(name + "conv", conv)] if preact else [(name + "conv", conv)] + extras
         for key, mod in parts:
             self.add_module(key, mod)
+
+    def forward(self, x):
+        if FUSED_TRAIN_LAYERS and self.training:
+            from . import train_layer
+            if train_layer.covers(self, x):
+                return train_layer.run(self, x)
+        return super().forward(x)
 
 
 class Conv1d(_ConvBlock):

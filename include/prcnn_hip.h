@@ -181,6 +181,45 @@ int prcnn_group_points_grad_ordered(int b, int c, int n, int slots, int c_total,
 int prcnn_three_interpolate_grad_ordered(int b, int c, int n, int m, const float *grad_out, const float *weight, const int *offsets,
                                          const int *entries, float *grad_points, void *stream);
 
+/* ---- the order-fixed TRAINING layer: forward and backward of a 1x1 convolution, BatchNorm on batch statistics and ReLU
+ *      (pytorch_utils.Conv1d / Conv2d in training mode; csrc/train_layer.hip; not in the reference ABI).
+ *      x (b,cin,p) f32, w (cout,cin), z / y / dz (b,cout,p): torch's layout, p = N of a Conv1d block or npoint * nsample of a
+ *      Conv2d block; n = b * p values per channel.  Any cin, cout, p >= 1; b <= 65535, p <= 65535 * PRCNN_TRAIN_CHUNK.
+ *      No float atomics, no host read, no allocation: the caller sizes the workspaces with prcnn_train_layer_workspace.
+ *
+ * ARITHMETIC CONTRACT.  A cloud's positions are cut into consecutive chunks of PRCNN_TRAIN_CHUNK.  Every sum below has a shape that
+ * is a function of (b, cin, cout, p) and the constants here alone, so the same input gives the same bits:
+ *  (1) a product element -- z[i][co][q] = sum over ci of w[co][ci] x[i][ci][q], and dx[i][ci][q] = sum over co of w[co][ci] dz[i][co][q] --
+ *      is the f32 fmaf chain over the summed index ASCENDING from +0.0f (what v_mfma_f32_32x32x2_f32 computes);
+ *  (2) a per-channel sum over positions (of z and z * z in the forward; of g and g * zhat in the backward) is taken in f64: inside a
+ *      chunk in a fixed tree -- forward: per column j of the chunk's 128-wide sub-tiles the terms at j, j + 128, ... left to right,
+ *      the 32 columns of a quarter in the xor tree (distance 1, 2, 4, 8, 16), the four quarters left to right; backward: per
+ *      thread t of 256 the terms at t, t + 256, ... left to right, the 64 lanes of a wave in the xor tree (1 .. 32), the four waves
+ *      left to right -- then the chunks left to right from 0.0, cloud-major (cloud 0's chunks, cloud 1's, ...);
+ *  (3) mean = S1 / n, var = max(S2 / n - mean * mean, 0), rstd = 1 / sqrt(var + eps) in f64 (stats (2,cout) f64: mean, rstd);
+ *      running_mean = (1 - m) running_mean + m mean and running_var = (1 - m) running_var + m (var n / (n - 1)), f64, rounded once;
+ *  (4) zhat = (z - mean) rstd, pre = zhat gamma + beta, y = max(pre, 0) per element in f64 from the f32 z, rounded once; without
+ *      BatchNorm y = max(z + bias, 0) in f32 (one rounding); relu = 0 leaves the max out;
+ *  (5) g = dy where pre > 0 (recomputed as in (4); without BatchNorm: where y > 0), else 0; dbeta (dbias) = s1 = sum g and
+ *      dgamma = s2 = sum g zhat, rounded once; dz = gamma rstd ((g - s1 / n) - zhat (s2 / n)) per element in f64, rounded once;
+ *      without BatchNorm dz = g;
+ *  (6) dw[co][ci]: per (cloud, chunk) the f32 fmaf chain over the chunk's positions ascending of dz[i][co][q] x[i][ci][q] from
+ *      +0.0f; these partials are added in f64 left to right, cloud-major, and rounded once. */
+enum { PRCNN_TRAIN_CHUNK = 1024 };
+/* element counts of the two workspaces: work (f64, *stat_f64 elements) and dw_work (f32, *dw_f32 elements; the backward's, needed
+ * only where dw is wanted).  Contents arbitrary on entry. */
+int prcnn_train_layer_workspace(int b, int cin, int cout, int p, long *stat_f64, long *dw_f32);
+/* bn != 0: z, stats and y are written, running_mean / running_var (either may be NULL) updated in place; b * p = 1 is an error.
+ * bn == 0: y = act(z + beta) with beta the bias (NULL: none); gamma, the running buffers, z, stats and work are not touched. */
+int prcnn_train_layer_forward(int b, int cin, int cout, int p, int bn, int relu, const float *x, const float *w, const float *gamma,
+                              const float *beta, double eps, double momentum, float *running_mean, float *running_var, float *z, float *y,
+                              double *stats, double *work, void *stream);
+/* zy is the saved z (bn != 0) or the saved y (bn == 0; read only with relu).  dz (b,cout,p) is scratch, written unless bn == 0 and
+ * relu == 0.  dx, dw, dgamma, dbeta (the bias gradient when bn == 0) are each skipped when NULL. */
+int prcnn_train_layer_backward(int b, int cin, int cout, int p, int bn, int relu, const float *dy, const float *x, const float *w,
+                               const float *zy, const float *gamma, const float *beta, const double *stats, float *dz, float *dx, float *dw,
+                               float *dgamma, float *dbeta, double *work, float *dw_work, void *stream);
+
 /* ---- shared-MLP epilogues (fused forms of pytorch_utils.py Conv2d -> BN(eval) -> ReLU and of
  *      the max over nsample of pointnet2_modules.py:41-44; not in the reference ABI) ------------ */
 
