@@ -5,23 +5,18 @@
 // Host code only (no device kernels here): the matching is a short sequential scan per image with
 // data-dependent control flow -- it stays on the CPU in the reference too -- but it is called
 // images x difficulties x overlap levels x 42 times per metric, so it lives in the library instead of
-// a Python loop.  All arithmetic is f64, as numba types it from the f64 label arrays.
+// a Python loop.  All arithmetic is f64, as numba types it from the f64 label arrays.  The scan itself is
+// kitti_match.hpp, shared with the device form of these statistics (kitti_ap.hip), whose definition this file is.
 #include "common.hpp"
+#include "kitti_match.hpp"
 #include <math.h>
 #include <vector>
 
 namespace prcnn {
 
-// image_box_overlap(boxes, query, criterion = 0) of one pair (eval2.py:102-128): intersection / area(box)
-static double overlap_over_box_area(const double *box, const double *q)
-{
-    const double iw = fmin(box[2], q[2]) - fmax(box[0], q[0]);
-    if (!(iw > 0)) return 0.0;
-    const double ih = fmin(box[3], q[3]) - fmax(box[1], q[1]);
-    if (!(ih > 0)) return 0.0;
-    const double ua = (box[2] - box[0]) * (box[3] - box[1]);
-    return iw * ih / ua;
-}
+// one true positive's orientation term; prcnn_kitti_pair_cos fills the device path's table with this same call
+static double pair_cos_term(double delta) { return (1.0 + cos(delta)) / 2.0; }
+
 
 struct ImageStats {
     long long tp, fp, fn;
@@ -29,8 +24,27 @@ struct ImageStats {
     int n_thresholds;
 };
 
-// compute_statistics_jit (eval2.py:170-289).  overlaps is (n_dt, n_gt) row-major; gt_datas (n_gt,5) =
-// [bbox x4, alpha]; dt_datas (n_dt,6) = [bbox x4, alpha, score]; thresholds_out has room for n_gt values.
+// one image's columns as the host entries take them
+struct HostView {
+    const double *overlaps, *dt_datas, *dc_bboxes;
+    const long long *ig, *id;
+    int n_gt;
+    int ignored_gt(int i) const { return (int)ig[i]; }
+    int ignored_det(int j) const { return (int)id[j]; }
+    double score(int j) const { return dt_datas[6 * j + 5]; }
+    double overlap(int j, int i) const { return overlaps[(size_t)j * n_gt + i]; }
+    const double *det_box(int j) const { return dt_datas + 6 * j; }
+    const double *dc_box(int i) const { return dc_bboxes + 4 * i; }
+};
+
+struct HostBits {
+    std::vector<char> &b;
+    bool get(int j) const { return b[j] != 0; }
+    void set(int j) { b[j] = 1; }
+};
+
+// compute_statistics_jit (eval2.py:170-289) around the shared scan (kitti_match.hpp).  overlaps is (n_dt, n_gt) row-major;
+// gt_datas (n_gt,5) = [bbox x4, alpha]; dt_datas (n_dt,6) = [bbox x4, alpha, score]; thresholds_out has room for n_gt values.
 static ImageStats image_stats(int n_gt, int n_dt, int n_dc, const double *overlaps, const double *gt_datas,
                               const double *dt_datas, const long long *ignored_gt, const long long *ignored_det,
                               const double *dc_bboxes, int metric, double min_overlap, double thresh, bool compute_fp,
@@ -42,67 +56,23 @@ static ImageStats image_stats(int n_gt, int n_dt, int n_dc, const double *overla
     delta.clear();
     if (compute_fp)
         for (int j = 0; j < n_dt; ++j) below[j] = dt_datas[6 * j + 5] < thresh;
-    const double NO_DETECTION = -10000000.0;
+    const HostView view = {overlaps, dt_datas, dc_bboxes, ignored_gt, ignored_det, n_gt};
+    HostBits abits = {assigned};
+    const HostBits bbits = {below};
     ImageStats st = {0, 0, 0, 0.0, 0};
-    for (int i = 0; i < n_gt; ++i) {
-        if (ignored_gt[i] == -1) continue;
-        int det_idx = -1;
-        double valid_detection = NO_DETECTION, max_overlap = 0.0;
-        bool assigned_ignored_det = false;
-        for (int j = 0; j < n_dt; ++j) {
-            if (ignored_det[j] == -1 || assigned[j] || below[j]) continue;
-            const double overlap = overlaps[(size_t)j * n_gt + i];
-            const double score = dt_datas[6 * j + 5];
-            if (!compute_fp && overlap > min_overlap && score > valid_detection) {
-                det_idx = j;
-                valid_detection = score;
-            } else if (compute_fp && overlap > min_overlap && (overlap > max_overlap || assigned_ignored_det) &&
-                       ignored_det[j] == 0) {
-                max_overlap = overlap;
-                det_idx = j;
-                valid_detection = 1;
-                assigned_ignored_det = false;
-            } else if (compute_fp && overlap > min_overlap && valid_detection == NO_DETECTION && ignored_det[j] == 1) {
-                det_idx = j;
-                valid_detection = 1;
-                assigned_ignored_det = true;
-            }
-        }
-        if (valid_detection == NO_DETECTION && ignored_gt[i] == 0) {
-            st.fn += 1;
-        } else if (valid_detection != NO_DETECTION && (ignored_gt[i] == 1 || ignored_det[det_idx] == 1)) {
-            assigned[det_idx] = 1;
-        } else if (valid_detection != NO_DETECTION) {
-            st.tp += 1;
-            if (thresholds_out) thresholds_out[st.n_thresholds] = dt_datas[6 * det_idx + 5];
-            st.n_thresholds += 1;
-            if (compute_aos) delta.push_back(gt_datas[5 * i + 4] - dt_datas[6 * det_idx + 4]);
-            assigned[det_idx] = 1;
-        }
-    }
-    if (compute_fp) {
-        for (int j = 0; j < n_dt; ++j)
-            if (!(assigned[j] || ignored_det[j] == -1 || ignored_det[j] == 1 || below[j])) st.fp += 1;
-        long long nstuff = 0;
-        if (metric == 0) {
-            for (int i = 0; i < n_dc; ++i)
-                for (int j = 0; j < n_dt; ++j) {
-                    if (assigned[j] || ignored_det[j] == -1 || ignored_det[j] == 1 || below[j]) continue;
-                    if (overlap_over_box_area(dt_datas + 6 * j, dc_bboxes + 4 * i) > min_overlap) {
-                        assigned[j] = 1;
-                        nstuff += 1;
-                    }
-                }
-        }
-        st.fp -= nstuff;
-        if (compute_aos) {
-            if (st.tp > 0 || st.fp > 0) {
-                double s = 0.0;   // fp zeros first, then (1 + cos(delta)) / 2 per true positive, summed in that order
-                for (double d : delta) s += (1.0 + cos(d)) / 2.0;
-                st.similarity = s;
-            } else {
-                st.similarity = -1;
-            }
+    const MatchCounts c = match_image(view, n_gt, n_dt, n_dc, metric, min_overlap, compute_fp, abits, bbits, [&](int i, int det_idx) {
+        if (thresholds_out) thresholds_out[st.n_thresholds] = dt_datas[6 * det_idx + 5];
+        st.n_thresholds += 1;
+        if (compute_aos) delta.push_back(gt_datas[5 * i + 4] - dt_datas[6 * det_idx + 4]);
+    });
+    st.tp = c.tp; st.fp = c.fp; st.fn = c.fn;
+    if (compute_fp && compute_aos) {
+        if (st.tp > 0 || st.fp > 0) {
+            double s = 0.0;   // fp zeros first, then (1 + cos(delta)) / 2 per true positive, summed in that order
+            for (double d : delta) s += pair_cos_term(d);
+            st.similarity = s;
+        } else {
+            st.similarity = -1;
         }
     }
     return st;
@@ -182,6 +152,23 @@ extern "C" int prcnn_kitti_accumulate_pr(int n_img, const long long *gt_nums, co
             if (st.similarity != -1) pr[4 * t + 3] += st.similarity;
         }
         gt0 += ng; dt0 += nd; dc0 += nc; ov0 += (size_t)ng * nd;
+    }
+    return PRCNN_OK;
+}
+
+// (1 + cos(gt alpha - dt alpha)) / 2 of every (detection, ground-truth) pair of every image, in the overlap blocks' layout
+// (pair_off[img] + j * n_gt + i).  HOST pointers.  The device pass adds these terms and never calls a cosine of its own.
+extern "C" int prcnn_kitti_pair_cos(int n_img, const long long *gt_off, const long long *dt_off, const long long *pair_off,
+                                    const double *gt_alpha, const double *dt_alpha, double *out)
+{
+    PRCNN_REQUIRE(n_img >= 0 && (n_img == 0 || (gt_off && dt_off && pair_off)), "kitti_pair_cos: bad arguments");
+    for (int m = 0; m < n_img; ++m) {
+        const long long ng = gt_off[m + 1] - gt_off[m], nd = dt_off[m + 1] - dt_off[m];
+        PRCNN_REQUIRE(ng >= 0 && nd >= 0 && pair_off[m + 1] - pair_off[m] == ng * nd, "kitti_pair_cos: offsets of image %d disagree", m);
+        PRCNN_REQUIRE(ng * nd == 0 || (gt_alpha && dt_alpha && out), "kitti_pair_cos: null pointer");
+        for (long long j = 0; j < nd; ++j)
+            for (long long i = 0; i < ng; ++i)
+                out[pair_off[m] + j * ng + i] = pair_cos_term(gt_alpha[gt_off[m] + i] - dt_alpha[dt_off[m] + j]);
     }
     return PRCNN_OK;
 }

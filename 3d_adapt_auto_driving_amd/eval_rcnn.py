@@ -33,7 +33,7 @@ from .runners import (_RUNNER_STREAMS, _runner_streams, PipelinedRunner, ModuleR
 from .host import (_NODE_AFFINITY, _node_affinity, _cpu_topology, slice_topology, host_budget, pin_to_budget, PIN_CORES,
                    _limit_worker_threads)
 from .gather import shard_scene_ids, pack_detections, all_gather_detections
-from .results import (kitti_result_text, kitti_result_lines, save_kitti_format, detections_to_annos, evaluate_detections, RecallStats,
+from .results import (kitti_result_text, kitti_result_lines, save_kitti_format, detections_to_annos, evaluate_detections, prepare_gt, RecallStats,
                       _calib_row, _RowCalib, _write_batch, _write_rpn_batch)
 
 
@@ -564,6 +564,8 @@ def build_parser():
                     help="--eval_ap difficulty rule: new = distance bands, old = KITTI's bbox-height levels")
     ap.add_argument("--ap_dataset", type=str, default="kitti", choices=["kitti", "argo", "nusc", "lyft", "waymo"],
                     help="--ap_metric old: whose focal length scales the 40 / 25 / 25 px height caps")
+    ap.add_argument("--ap_stats_device", type=str, default="cpu", choices=["cpu", "cuda"],
+                    help="--eval_ap: flags, matching and PR sums on the host (default) or on the GPU; the same numbers")
     ap.add_argument("--recall", action="store_true", help="RoI / refined-box recall vs the ground truth (the reference's statistics without --test)")
     ap.add_argument("--save_result", action="store_true", help="--eval_mode rpn: write detections/data and seg_result")
     ap.add_argument("--save_rpn_feature", action="store_true", help="--eval_mode rpn: also write the backbone features (features/)")
@@ -619,11 +621,13 @@ def main(argv=None):
     return evaluate_model(args, model, cfg, device, source, my_ids, rank, args.output_dir)
 
 
-def evaluate_model(args, model, cfg, device, source, my_ids, rank, output_dir, runner=None, labels=None, timings=None):
+def evaluate_model(args, model, cfg, device, source, my_ids, rank, output_dir, runner=None, labels=None, timings=None,
+                   prepared_gt=None):
     """One evaluation of ``model`` as it stands, in the mode of ``args``: what a --ckpt run does behind its checkpoint load, with its
     files under ``output_dir``.  -> the mode's result dictionary (rpn: RpnStats.result(), None with --test; rcnn: scenes, detections,
     the recalls with --recall, the AP dictionary with --eval_ap).  The sweep passes the ``runner`` it keeps, ``labels`` (the source
-    behind a label cache, for the AP) and ``timings``, a dict that receives the seconds of 'inference' and 'ap'."""
+    behind a label cache, for the AP), ``timings``, a dict that receives the seconds of 'inference' and 'ap', and with
+    --ap_stats_device cuda ``prepared_gt``, the labels' table built once (results.prepare_gt)."""
     timings = {} if timings is None else timings
     if args.eval_mode == "rpn":
         t0 = time.perf_counter()
@@ -653,7 +657,8 @@ def evaluate_model(args, model, cfg, device, source, my_ids, rank, output_dir, r
         if args.eval_ap:
             t1 = time.perf_counter()
             text, ap = evaluate_detections(table, counts, labels if labels is not None else source, dataset=args.ap_dataset,
-                                           device_id=device.index or 0, metric=args.ap_metric)
+                                           device_id=device.index or 0, metric=args.ap_metric,
+                                           stats_device=getattr(args, "ap_stats_device", "cpu"), prepared_gt=prepared_gt)
             timings["ap"] = time.perf_counter() - t1
             res["ap"] = ap
             print(text)

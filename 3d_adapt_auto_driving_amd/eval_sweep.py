@@ -154,6 +154,9 @@ def sweep(args, model, cfg, device, source, my_ids, rank=0, world=1):
         for key, val in sorted(vars(args).items()):
             log.info("%-16s %s", key, val)
         labels = _LabelCache(source)
+        prepared_gt = None             # the device AP path: the labels' half of the split table, built once for every checkpoint
+        if rank == 0 and args.eval_ap and args.eval_mode != "rpn" and getattr(args, "ap_stats_device", "cpu") == "cuda":
+            prepared_gt = E.prepare_gt(labels, sorted(source.ids))
         runner = None
         failed = {}                    # path -> modification time at the failed attempt: tried again only once the file has changed
         clock = time.perf_counter
@@ -196,7 +199,7 @@ def sweep(args, model, cfg, device, source, my_ids, rank=0, world=1):
             os.makedirs(out_dir, exist_ok=True)
             timings = {}
             result = E.evaluate_model(args, model, cfg, device, source, my_ids, rank, out_dir, runner=runner, labels=labels,
-                                      timings=timings)
+                                      timings=timings, prepared_gt=prepared_gt)
             seconds = {"load": t1 - t0, "reload": t2 - t1, "inference": timings.get("inference", 0.0), "ap": timings.get("ap", 0.0)}
             write({"epoch": epoch, "ckpt": path, "result": result, "seconds": {k: round(v, 4) for k, v in seconds.items()}})
             if rank == 0:

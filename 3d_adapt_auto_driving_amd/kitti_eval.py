@@ -25,7 +25,11 @@ that BEV overlap, and the same for every ground-truth box.  ``best_match(device=
 (``prcnn_bev_best_match``, csrc/eval_match.hip) that never writes the pair matrix; ``device="cpu"`` is numpy's max / argmax over
 ``calculate_iou(..., 1)``.  align_size / align_front then run on the device too (``prcnn_eval_align``).
 
-Command line:  python -m 3d_adapt_auto_driving_amd.kitti_eval --result_path ... --dataset_path ... [--metric old] [--align_size] ...
+``stats_device="cuda"`` (off by default) moves the statistics themselves to the device: one table of the split's columns (SplitTable),
+then flags, overlaps, both matching passes, thresholds and PR sums as kernels of csrc/kitti_ap.hip (DeviceStats) with one read at
+the end.  The host path is its definition and its checker; both give the same bits.
+
+Command line:  python -m 3d_adapt_auto_driving_amd.kitti_eval --result_path ... --dataset_path ... [--metric old] [--align_size] [--stats_device cuda] ...
 """
 import ctypes
 import io
@@ -302,18 +306,347 @@ class _Split:
         self.dontcares, self.gt_datas, self.dt_datas = cat(dcs, 4, np.float64), cat(gts, 5, np.float64), cat(dts, 6, np.float64)
 
 
+# ---------------------------------------------------------------------------------------------------
+# the split as one table, and the statistics on the device (csrc/kitti_ap.hip)
+# ---------------------------------------------------------------------------------------------------
+class StatsDeviceError(RuntimeError):
+    """stats_device="cuda" was asked for and no GPU is usable.  There is no fallback to the host path."""
+
+
+def _check_stats_device(stats_device):
+    if stats_device not in ("cpu", "cuda"):
+        raise ValueError("stats_device %r is neither 'cpu' nor 'cuda'" % (stats_device,))
+
+
+CLASS_CODE = {"car": 0, "pedestrian": 1, "cyclist": 2, "van": 3, "person_sitting": 4}      # include/prcnn_hip.h: the split table
+SIBLING_CODE = {0: 3, 1: 4}                                                                # Van for Car, Person_sitting for Pedestrian
+REG_DETS = _lib.PRCNN_AP_REG_DETS                    # detections per image whose scan flags the kernels keep in registers
+
+
+class SplitSide:
+    """One side (labels or detections) of a split as concatenated columns: ``off`` (n_img + 1) i64, ``code`` i8 class codes of the
+    lower-cased names (lower-casing runs over the UNIQUE names), ``is_dc`` (the name is exactly "DontCare"), and the numeric columns
+    occluded, truncated, bbox, alpha, location, dimensions (l, h, w), rotation_y, score as f64."""
+
+    def __init__(self, annos):
+        self.n_img = len(annos)
+        nums = np.array([len(a["name"]) for a in annos], dtype=np.int64)
+        self.off = np.concatenate([[0], np.cumsum(nums)]).astype(np.int64)
+        names = np.concatenate([np.asarray(a["name"], dtype=str).reshape(-1) for a in annos]) if self.n_img else np.zeros((0,), dtype=str)
+        uniq, inv = np.unique(names, return_inverse=True) if names.size else (np.zeros((0,), dtype=str), np.zeros((0,), dtype=np.int64))
+        self.code = np.array([CLASS_CODE.get(u.lower(), -1) for u in uniq], dtype=np.int8)[inv].reshape(-1)
+        self.is_dc = np.array([u == "DontCare" for u in uniq], dtype=bool)[inv].reshape(-1)
+        col = lambda key, w: _cat([a[key] for a in annos], w)
+        self.occluded, self.truncated, self.alpha = col("occluded", 0), col("truncated", 0), col("alpha", 0)
+        self.bbox, self.location, self.dimensions = col("bbox", 4), col("location", 3), col("dimensions", 3)
+        self.rotation_y, self.score = col("rotation_y", 0), col("score", 0)
+
+    def __len__(self):
+        return int(self.off[-1])
+
+    @property
+    def box3d(self):                                 # _d3_boxes: x y z l h w ry
+        return np.ascontiguousarray(np.concatenate([self.location, self.dimensions, self.rotation_y[:, None]], axis=1))
+
+    @property
+    def bev(self):                                   # _bev_boxes == _d3_boxes[:, [0, 2, 3, 5, 6]], narrowed as rotate_iou_segmented does
+        return np.ascontiguousarray(self.box3d[:, [0, 2, 3, 5, 6]].astype(np.float32))
+
+
+class PreparedGT:
+    """The ground-truth half of a split, parsed and tabulated once: pass it wherever ``gt_annos`` goes (the device path takes its
+    columns, the host path its annotation list) -- a sweep evaluates every checkpoint against the same one."""
+
+    def __init__(self, gt_annos, ids=None):
+        self.annos = list(gt_annos)
+        self.ids = None if ids is None else list(ids)
+        self.side = SplitSide(self.annos)
+
+    def __len__(self):
+        return len(self.annos)
+
+
+def _plain_gt(gt_annos):
+    return gt_annos.annos if isinstance(gt_annos, PreparedGT) else gt_annos
+
+
+class SplitTable:
+    """Both sides of a split and what pairs them: per-image offsets of ground truth, detections, DontCare rows and (n_dt x n_gt)
+    pair blocks; ``dc_rows``: the ground-truth rows named DontCare, in order.  Built in whole-array numpy, once per evaluation;
+    ``gt_annos`` may be a PreparedGT."""
+
+    def __init__(self, gt_annos, dt_annos):
+        self.gt = gt_annos.side if isinstance(gt_annos, PreparedGT) else SplitSide(gt_annos)
+        self.dt = SplitSide(dt_annos)
+        if self.gt.n_img != self.dt.n_img:
+            raise ValueError("SplitTable: %d label images but %d detection images" % (self.gt.n_img, self.dt.n_img))
+        self.n_img = self.gt.n_img
+        self.gt_off, self.dt_off = self.gt.off, self.dt.off
+        self.gt_nums, self.dt_nums = np.diff(self.gt_off), np.diff(self.dt_off)
+        self.pair_off = np.concatenate([[0], np.cumsum(self.gt_nums * self.dt_nums)]).astype(np.int64)
+        self.dc_rows = np.flatnonzero(self.gt.is_dc)
+        self.dc_off = np.searchsorted(self.dc_rows, self.gt_off).astype(np.int64)
+        self.dc_bbox = np.ascontiguousarray(self.gt.bbox[self.dc_rows])
+        self.max_dt = int(self.dt_nums.max()) if self.n_img else 0
+        big = self.dt_nums > REG_DETS
+        self.ws_slot = np.where(big, np.cumsum(big) - 1, -1).astype(np.int32)
+        self.n_big = int(big.sum())
+
+
+def difficulty_caps(dataset, difficultys, metric):
+    """(n_diff, 5) f64 rows [max occlusion, max truncation, band near, band far, min bbox height] of clean_data's comparisons"""
+    _difficulties(metric)
+    rows = []
+    for d in difficultys:
+        if metric == "old":
+            rows.append([OLD_MAX_OCCLUSION[d], OLD_MAX_TRUNCATION[d], 0.0, 0.0, min_height(dataset)[d]])
+        else:
+            rows.append([MAX_OCCLUSION[d], MAX_TRUNCATION[d], DIST_BOUNDARY[0, d], DIST_BOUNDARY[1, d], 0.0])
+    return np.ascontiguousarray(np.array(rows, dtype=np.float64).reshape(-1, 5))
+
+
+def split_flags(table, current_class, dataset, difficulty, metric="new"):
+    """clean_data for every image of the split at once -> ignored_gt (n_gt) i64, ignored_dt (n_dt) i64, num_valid_gt, dc_bboxes
+    (n_dc, 4): the concatenation of what clean_data gives image by image, and the definition of prcnn_ap_flags."""
+    CLASS_NAMES[current_class]
+    max_occ, max_trunc, near, far, cap = difficulty_caps(dataset, [difficulty], metric)[0]
+    gt, dt = table.gt, table.dt
+    if metric == "old":
+        capped = (gt.occluded > max_occ) | (gt.truncated > max_trunc) | (gt.bbox[:, 3] - gt.bbox[:, 1] <= cap)
+        in_band = ~(np.abs(dt.bbox[:, 3] - dt.bbox[:, 1]) < cap)
+    else:
+        capped = (gt.occluded > max_occ) | (gt.truncated > max_trunc) | ~((near < gt.location[:, 2]) & (gt.location[:, 2] < far))
+        in_band = (near < dt.location[:, 2]) & (dt.location[:, 2] < far)
+    own, sibling = gt.code == current_class, gt.code == SIBLING_CODE.get(current_class, -2)
+    ignored_gt = np.full(len(gt), -1, dtype=np.int64)
+    ignored_gt[sibling | (own & capped)] = 1
+    ignored_gt[own & ~capped] = 0
+    ignored_dt = np.where(in_band, np.where(dt.code == current_class, 0, -1), 1).astype(np.int64)
+    return ignored_gt, ignored_dt, int(np.count_nonzero(ignored_gt == 0)), table.dc_bbox
+
+
+def thresholds_loop(sorted_scores, num_gt, num_sample_pts=N_SAMPLE_PTS):
+    """The reference's loop as written (evaluate/eval2.py:8-25) over scores already in descending order: the definition of
+    prcnn_ap_thresholds (get_thresholds is its closed form)."""
+    current_recall = 0
+    thresholds = []
+    n = len(sorted_scores)
+    for i, score in enumerate(sorted_scores):
+        l_recall = (i + 1) / num_gt
+        r_recall = (i + 2) / num_gt if i < n - 1 else l_recall
+        if (r_recall - current_recall) < (current_recall - l_recall) and i < n - 1:
+            continue
+        thresholds.append(score)
+        current_recall += 1 / (num_sample_pts - 1.0)
+    return thresholds
+
+
+def pair_cos(table):
+    """(n_pair) f64: (1 + cos(gt alpha - dt alpha)) / 2 per pair in the overlap blocks' layout, by the library's host entry"""
+    out = np.zeros((int(table.pair_off[-1]),), dtype=np.float64)
+    _lib.call("prcnn_kitti_pair_cos", table.n_img, _ptr(table.gt_off), _ptr(table.dt_off), _ptr(table.pair_off),
+              _ptr(table.gt.alpha), _ptr(table.dt.alpha), _ptr(out))
+    return out
+
+
+class DeviceStats:
+    """A SplitTable on the device and the stages of csrc/kitti_ap.hip over it.  Every stage returns DEVICE tensors and reads nothing
+    back; eval_class chains them and reads once.  All launches go to torch's current stream of the device."""
+    CHUNK_BYTES = 256 << 20                          # bound on the per-image similarity buffer and the score rows of one chunk of levels
+
+    def __init__(self, table, device_id=0):
+        import torch
+        if not torch.cuda.is_available():
+            raise StatsDeviceError("stats_device='cuda': torch sees no usable GPU (torch.cuda.is_available() is False); "
+                                   "there is no fallback -- pass stats_device='cpu' for the host path")
+        self.torch, self.table = torch, table
+        self.dev = torch.device("cuda", device_id)
+        up = self._up
+        gt, dt = table.gt, table.dt
+        self.t = {"gt_off": up(table.gt_off), "dt_off": up(table.dt_off), "dc_off": up(table.dc_off), "pair_off": up(table.pair_off),
+                  "ws_slot": up(table.ws_slot), "gt_code": up(gt.code), "dt_code": up(dt.code), "gt_occluded": up(gt.occluded),
+                  "gt_truncated": up(gt.truncated), "gt_bbox": up(gt.bbox), "gt_depth": up(gt.location[:, 2]), "gt_box3d": up(gt.box3d),
+                  "dt_bbox": up(dt.bbox), "dt_depth": up(dt.location[:, 2]), "dt_score": up(dt.score), "dt_box3d": up(dt.box3d),
+                  "dc_bbox": up(table.dc_bbox), "gt_bev": up(gt.bev), "dt_bev": up(dt.bev)}
+        self.n_gt, self.n_dt, self.n_pair = len(gt), len(dt), int(table.pair_off[-1])
+        # the table as the entries take it: a host array of i64 words, counts then device pointers (include/prcnn_hip.h PRCNN_AP_*)
+        self.words = np.zeros((_lib.PRCNN_AP_SPLIT_WORDS,), dtype=np.int64)
+        for key, value in (("n_img", table.n_img), ("max_dt", table.max_dt), ("n_gt", self.n_gt), ("n_dt", self.n_dt),
+                           ("n_dc", len(table.dc_rows)), ("n_pair", self.n_pair)) + tuple((k, v.data_ptr()) for k, v in self.t.items()):
+            self.words[getattr(_lib, "PRCNN_AP_" + key.upper())] = value
+        self._flags, self._overlaps, self._cos = {}, {}, None
+
+    def _up(self, a):
+        return self.torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
+
+    def _empty(self, shape, dtype):
+        return self.torch.empty(shape, dtype=dtype, device=self.dev)
+
+    def _call(self, name, *args):
+        with self.torch.cuda.device(self.dev):
+            _lib.call(name, *args, _lib.current_stream(self.t["gt_off"]))
+
+    def flags(self, current_class, dataset, difficultys, metric="new"):
+        """-> ignored_gt (n_diff, n_gt) i8, ignored_dt (n_diff, n_dt) i8, num_valid_gt (n_diff) i32; one launch, kept per key"""
+        key = (current_class, dataset if metric == "old" else None, tuple(difficultys), metric)
+        if key not in self._flags:
+            CLASS_NAMES[current_class]
+            T, n_diff = self.torch, len(difficultys)
+            caps = difficulty_caps(dataset, difficultys, metric)
+            ig, idt, nv = self._empty((n_diff, self.n_gt), T.int8), self._empty((n_diff, self.n_dt), T.int8), self._empty((n_diff,), T.int32)
+            self._call("prcnn_ap_flags", _ptr(self.words), int(current_class), SIBLING_CODE.get(current_class, -2),
+                       int(metric == "old"), n_diff, _ptr(caps), _lib.ptr(ig), _lib.ptr(idt), _lib.ptr(nv))
+            self._flags[key] = (ig, idt, nv)
+        return self._flags[key]
+
+    def overlaps(self, kind):
+        """-> (n_pair) f64, the flat concatenation of calculate_iou(dt, gt, kind)'s blocks; kept per kind"""
+        if kind not in self._overlaps:
+            T = self.torch
+            if kind == 0:
+                out = self._empty((self.n_pair,), T.float64)
+                self._call("prcnn_ap_overlaps", _ptr(self.words), 0, None, _lib.ptr(out))
+            elif kind in (1, 2):
+                raw = self._empty((self.n_pair,), T.float32)
+                off32 = lambda a: self._up(a.astype(np.int32))
+                if not hasattr(self, "_off32"):
+                    self._off32 = (off32(self.table.dt_off), off32(self.table.gt_off))
+                self._call("prcnn_rotate_iou_eval_segmented", self.table.n_img, self.n_pair, _lib.ptr(self.t["pair_off"]),
+                           _lib.ptr(self._off32[0]), _lib.ptr(self._off32[1]), _lib.ptr(self.t["dt_bev"]), _lib.ptr(self.t["gt_bev"]),
+                           _lib.ptr(raw), -1 if kind == 1 else 2)
+                if kind == 1:
+                    out = raw.double()
+                else:
+                    out = self._empty((self.n_pair,), T.float64)
+                    self._call("prcnn_ap_overlaps", _ptr(self.words), 2, _lib.ptr(raw), _lib.ptr(out))
+            else:
+                raise ValueError("unknown metric")
+            self._overlaps[kind] = out
+        return self._overlaps[kind]
+
+    def upload_overlaps(self, blocks):
+        """A caller's per-image (n_dt, n_gt) blocks, as they are"""
+        flat = np.concatenate([np.asarray(o, dtype=np.float64).reshape(-1) for o in blocks]) if len(blocks) else np.zeros((0,))
+        if flat.shape[0] != self.n_pair:
+            raise ValueError("overlaps hold %d pairs, the split has %d" % (flat.shape[0], self.n_pair))
+        return self._up(flat.astype(np.float64))
+
+    def pair_cos(self):
+        if self._cos is None:
+            self._cos = self._up(pair_cos(self.table))
+        return self._cos
+
+    def _workspace(self, n_groups, lanes):
+        words = (self.table.max_dt + 63) // 64 if self.table.n_big else 0
+        ws = self._empty((max(1, self.table.n_big * n_groups * lanes * words),), self.torch.int64)
+        return ws, words
+
+    def scores(self, flags, overlaps, kind, min_overlaps):
+        """Pass 1.  min_overlaps (n_lev) f64 device -> scores (n_groups, n_gt) f64 (-inf where unmatched), valid (n_groups, n_gt) i8"""
+        T, (ig, idt, nv) = self.torch, flags
+        n_diff, n_lev = ig.shape[0], min_overlaps.shape[0]
+        scores, valid = self._empty((n_diff * n_lev, self.n_gt), T.float64), self._empty((n_diff * n_lev, self.n_gt), T.int8)
+        ws, words = self._workspace(n_diff * n_lev, 1)
+        self._call("prcnn_ap_scores", _ptr(self.words), _lib.ptr(ig), _lib.ptr(idt), n_diff, n_lev, _lib.ptr(min_overlaps),
+                   _lib.ptr(overlaps), int(kind), _lib.ptr(scores), _lib.ptr(valid), _lib.ptr(ws), words)
+        return scores, valid
+
+    def thresholds(self, scores, valid, num_valid_gt):
+        """One batched descending sort, the per-group count, then the reference's loop per group
+        -> sorted (n_groups, n_gt), count (n_groups) i32, thresholds (n_groups, 41) f64, n_thr (n_groups) i32"""
+        T, n_groups = self.torch, scores.shape[0]
+        ordered = T.sort(scores, dim=1, descending=True).values.contiguous()
+        count = valid.sum(dim=1, dtype=T.int32)
+        thr, n_thr = self._empty((n_groups, N_SAMPLE_PTS), T.float64), self._empty((n_groups,), T.int32)
+        self._call("prcnn_ap_thresholds", n_groups, n_groups // num_valid_gt.shape[0], self.n_gt, _lib.ptr(ordered), _lib.ptr(count),
+                   _lib.ptr(num_valid_gt), _lib.ptr(thr), _lib.ptr(n_thr))
+        return ordered, count, thr, n_thr
+
+    def pr(self, flags, overlaps, kind, min_overlaps, thr, n_thr, compute_aos):
+        """Pass 2 and the sums -> pr (n_groups, 41, 4) f64 = [tp, fp, fn, similarity]"""
+        T, (ig, idt, nv) = self.torch, flags
+        n_diff, n_lev = ig.shape[0], min_overlaps.shape[0]
+        n_groups = n_diff * n_lev
+        counts, pr = self._empty((n_groups, N_SAMPLE_PTS, 3), T.int64), self._empty((n_groups, N_SAMPLE_PTS, 4), T.float64)
+        sim = self._empty((self.table.n_img, n_groups, N_SAMPLE_PTS), T.float64) if compute_aos else None
+        cos = self.pair_cos() if compute_aos else None
+        ws, words = self._workspace(n_groups, 2 * 64)
+        self._call("prcnn_ap_pr", _ptr(self.words), _lib.ptr(ig), _lib.ptr(idt), n_diff, n_lev, _lib.ptr(min_overlaps),
+                   _lib.ptr(overlaps), int(kind), _lib.ptr(thr), _lib.ptr(n_thr), _lib.ptr(cos), _lib.ptr(counts), _lib.ptr(sim),
+                   _lib.ptr(pr), _lib.ptr(ws), words)
+        return pr
+
+    def level_chunk(self, n_diff, n_lev):
+        per_level = 8 * n_diff * max(self.table.n_img * N_SAMPLE_PTS, 3 * self.n_gt, 1)
+        return max(1, min(n_lev, self.CHUNK_BYTES // per_level))
+
+    def eval_class(self, current_classes, dataset, difficultys, kind, min_overlaps, compute_aos=False, overlaps=None,
+                   difficulty_metric="new"):
+        """-> pr (n_class, n_diff, n_lev, 41, 4) f64 and n_thr (n_class, n_diff, n_lev) int, numpy, from ONE device-to-host read"""
+        T = self.torch
+        with T.cuda.device(self.dev):
+            ov = self.overlaps(kind) if overlaps is None else self.upload_overlaps(overlaps)
+            n_cls, n_diff, n_lev, width = len(current_classes), len(difficultys), len(min_overlaps), 4 * N_SAMPLE_PTS
+            out = T.zeros((n_cls, n_diff, n_lev, width + 1), dtype=T.float64, device=self.dev)
+            step = self.level_chunk(n_diff, n_lev)
+            for m, current_class in enumerate(current_classes):
+                flags = self.flags(current_class, dataset, difficultys, difficulty_metric)
+                levels = self._up(np.asarray(min_overlaps[:, kind, m], dtype=np.float64))
+                for k0 in range(0, n_lev, step):
+                    lev = levels[k0:k0 + step]
+                    scores, valid = self.scores(flags, ov, kind, lev)
+                    _, _, thr, n_thr = self.thresholds(scores, valid, flags[2])
+                    pr = self.pr(flags, ov, kind, lev, thr, n_thr, compute_aos)
+                    out[m, :, k0:k0 + step, :width] = pr.view(n_diff, lev.shape[0], width)
+                    out[m, :, k0:k0 + step, width] = n_thr.view(n_diff, lev.shape[0]).double()
+            host = out.cpu().numpy()                                                     # the read
+        n_thr = host[..., width].astype(np.int64)
+        if n_thr.size and n_thr.max() > N_SAMPLE_PTS:
+            raise _lib.PrcnnError("a group took %d recall thresholds (> %d)" % (n_thr.max(), N_SAMPLE_PTS))
+        return host[..., :width].reshape(n_cls, n_diff, n_lev, N_SAMPLE_PTS, 4), n_thr
+
+
+def _fill_curves(precision, recall, aos, pr, compute_aos):
+    """pr (n_thresholds, 4) = [tp, fp, fn, similarity] -> one group's 41-sample rows, in place (eval2.py:545-560)."""
+    n = len(pr)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for i in range(n):
+            recall[i] = pr[i, 0] / (pr[i, 0] + pr[i, 2])
+            precision[i] = pr[i, 0] / (pr[i, 0] + pr[i, 1])
+            if compute_aos:
+                aos[i] = pr[i, 3] / (pr[i, 0] + pr[i, 1])
+    for i in range(n):      # monotone envelope, right to left
+        precision[i] = np.max(precision[i:], axis=-1)
+        recall[i] = np.max(recall[i:], axis=-1)
+        if compute_aos:
+            aos[i] = np.max(aos[i:], axis=-1)
+
+
 def eval_class(gt_annos, dt_annos, current_classes, dataset, difficultys, metric, min_overlaps, compute_aos=False,
-               device_id=0, overlaps=None, difficulty_metric="new"):
+               device_id=0, overlaps=None, difficulty_metric="new", stats_device="cpu", split=None):
     """-> dict(recall, precision, orientation), each [num_class, num_difficulty, num_minoverlap, 41]
     (eval2.py:460-569).  min_overlaps: [num_minoverlap, metric, num_class].  ``metric`` is the overlap kind (0 image box / 1 BEV /
-    2 3D) as in the reference; the difficulty rule ("new" | "old", the ``metric`` keyword everywhere else) is ``difficulty_metric``."""
+    2 3D) as in the reference; the difficulty rule ("new" | "old", the ``metric`` keyword everywhere else) is ``difficulty_metric``.
+    stats_device "cpu": the host entries of csrc/kitti_stats.hip; "cuda": flags, overlaps, both passes, thresholds and sums on the
+    device (csrc/kitti_ap.hip) with one read at the end -- the same bits.  ``split``: a DeviceStats of these annotations to reuse."""
+    _check_stats_device(stats_device)
+    shape = [len(current_classes), len(difficultys), len(min_overlaps), N_SAMPLE_PTS]
+    precision, recall, aos = np.zeros(shape), np.zeros(shape), np.zeros(shape)
+    if stats_device == "cuda":
+        if split is None:
+            split = DeviceStats(SplitTable(gt_annos, dt_annos), device_id)
+        pr, n_thr = split.eval_class(current_classes, dataset, difficultys, metric, min_overlaps, compute_aos, overlaps, difficulty_metric)
+        for m in range(shape[0]):
+            for l in range(shape[1]):
+                for k in range(shape[2]):
+                    _fill_curves(precision[m, l, k], recall[m, l, k], aos[m, l, k], pr[m, l, k, :n_thr[m, l, k]], compute_aos)
+        return {"recall": recall, "precision": precision, "orientation": aos}
+    gt_annos = _plain_gt(gt_annos)
     assert len(gt_annos) == len(dt_annos)
     n_img = len(gt_annos)
     if overlaps is None:
         overlaps = calculate_iou(dt_annos, gt_annos, metric, device_id)
     flat = np.ascontiguousarray(np.concatenate([o.reshape(-1) for o in overlaps]) if n_img else np.zeros((0,)), dtype=np.float64)
-    shape = [len(current_classes), len(difficultys), len(min_overlaps), N_SAMPLE_PTS]
-    precision, recall, aos = np.zeros(shape), np.zeros(shape), np.zeros(shape)
     for m, current_class in enumerate(current_classes):
         for l, difficulty in enumerate(difficultys):
             sp = _Split(gt_annos, dt_annos, current_class, dataset, difficulty, difficulty_metric)
@@ -330,17 +663,7 @@ def eval_class(gt_annos, dt_annos, current_classes, dataset, difficultys, metric
                               _ptr(flat), _ptr(sp.gt_datas), _ptr(sp.dt_datas), _ptr(sp.dontcares), _ptr(sp.ignored_gts),
                               _ptr(sp.ignored_dets), int(metric), float(min_overlap), _ptr(thresholds), len(thresholds),
                               int(bool(compute_aos)), _ptr(pr))
-                with np.errstate(divide="ignore", invalid="ignore"):
-                    for i in range(len(thresholds)):
-                        recall[m, l, k, i] = pr[i, 0] / (pr[i, 0] + pr[i, 2])
-                        precision[m, l, k, i] = pr[i, 0] / (pr[i, 0] + pr[i, 1])
-                        if compute_aos:
-                            aos[m, l, k, i] = pr[i, 3] / (pr[i, 0] + pr[i, 1])
-                for i in range(len(thresholds)):      # monotone envelope, right to left
-                    precision[m, l, k, i] = np.max(precision[m, l, k, i:], axis=-1)
-                    recall[m, l, k, i] = np.max(recall[m, l, k, i:], axis=-1)
-                    if compute_aos:
-                        aos[m, l, k, i] = np.max(aos[m, l, k, i:], axis=-1)
+                _fill_curves(precision[m, l, k], recall[m, l, k], aos[m, l, k], pr, compute_aos)
     return {"recall": recall, "precision": precision, "orientation": aos}
 
 
@@ -350,16 +673,17 @@ def get_mAP(prec):
     return np.cumsum(prec[..., ::4], axis=-1)[..., -1] / 11 * 100
 
 
-def do_eval(gt_annos, dt_annos, current_classes, dataset, min_overlaps, compute_aos=False, device_id=0, metric="new"):
+def do_eval(gt_annos, dt_annos, current_classes, dataset, min_overlaps, compute_aos=False, device_id=0, metric="new", stats_device="cpu"):
     difficultys = _difficulties(metric)
-    ret = eval_class(gt_annos, dt_annos, current_classes, dataset, difficultys, 0, min_overlaps, compute_aos, device_id,
-                     difficulty_metric=metric)
+    _check_stats_device(stats_device)
+    # the device path builds the split table and its uploads once; the three overlap kinds share them and the flags
+    split = DeviceStats(SplitTable(gt_annos, dt_annos), device_id) if stats_device == "cuda" else None
+    more = {"device_id": device_id, "difficulty_metric": metric, "stats_device": stats_device, "split": split}
+    ret = eval_class(gt_annos, dt_annos, current_classes, dataset, difficultys, 0, min_overlaps, compute_aos, **more)
     mAP_bbox = get_mAP(ret["precision"])
     mAP_aos = get_mAP(ret["orientation"]) if compute_aos else None
-    mAP_bev = get_mAP(eval_class(gt_annos, dt_annos, current_classes, dataset, difficultys, 1, min_overlaps,
-                                 device_id=device_id, difficulty_metric=metric)["precision"])
-    mAP_3d = get_mAP(eval_class(gt_annos, dt_annos, current_classes, dataset, difficultys, 2, min_overlaps,
-                                device_id=device_id, difficulty_metric=metric)["precision"])
+    mAP_bev = get_mAP(eval_class(gt_annos, dt_annos, current_classes, dataset, difficultys, 1, min_overlaps, **more)["precision"])
+    mAP_3d = get_mAP(eval_class(gt_annos, dt_annos, current_classes, dataset, difficultys, 2, min_overlaps, **more)["precision"])
     return mAP_bbox, mAP_bev, mAP_3d, mAP_aos
 
 
@@ -383,7 +707,8 @@ def _alpha_is_valid(dt_annos):
     return False
 
 
-def get_official_eval_result(gt_annos, dt_annos, current_classes, dataset="kitti", dense_sample=False, device_id=0, metric="new"):
+def get_official_eval_result(gt_annos, dt_annos, current_classes, dataset="kitti", dense_sample=False, device_id=0, metric="new",
+                             stats_device="cpu"):
     """-> (result text, dict) in the reference's format (eval2.py:629-722; metric="old": eval_old.py:619-695, three numbers per
     line and no dense sampling)."""
     overlap_0_7 = np.array([[0.7, 0.5, 0.5, 0.7, 0.5], [0.7, 0.5, 0.5, 0.7, 0.5], [0.7, 0.5, 0.5, 0.7, 0.5]])
@@ -399,7 +724,7 @@ def get_official_eval_result(gt_annos, dt_annos, current_classes, dataset="kitti
     min_overlaps = min_overlaps[:, :, current_classes]
     compute_aos = _alpha_is_valid(dt_annos)
     mAPbbox, mAPbev, mAP3d, mAPaos = do_eval(gt_annos, dt_annos, current_classes, dataset, min_overlaps, compute_aos, device_id,
-                                             metric)
+                                             metric, stats_device)
     levels = range(len(_difficulties(metric)))
     result = ""
     res = {}
@@ -423,7 +748,8 @@ def get_official_eval_result(gt_annos, dt_annos, current_classes, dataset="kitti
 COCO_RANGE = {0: [0.5, 0.95, 10], 1: [0.25, 0.7, 10], 2: [0.25, 0.7, 10], 3: [0.5, 0.95, 10], 4: [0.25, 0.7, 10]}
 
 
-def do_coco_style_eval(gt_annos, dt_annos, current_classes, overlap_ranges, compute_aos, dataset="kitti", device_id=0, metric="new"):
+def do_coco_style_eval(gt_annos, dt_annos, current_classes, overlap_ranges, compute_aos, dataset="kitti", device_id=0, metric="new",
+                       stats_device="cpu"):
     """mAP averaged over ten overlap thresholds (eval2.py:611-626).  overlap_ranges: [lo / hi / count, overlap kind, num_class].
     The reference's call of do_eval is one argument short since ``dataset`` joined its signature; this passes it."""
     min_overlaps = np.zeros([10, *overlap_ranges.shape[1:]])
@@ -432,18 +758,18 @@ def do_coco_style_eval(gt_annos, dt_annos, current_classes, overlap_ranges, comp
             lo, hi, num = overlap_ranges[:, i, j]
             min_overlaps[:, i, j] = np.linspace(lo, hi, int(num))
     mAP_bbox, mAP_bev, mAP_3d, mAP_aos = do_eval(gt_annos, dt_annos, current_classes, dataset, min_overlaps, compute_aos, device_id,
-                                                 metric)
+                                                 metric, stats_device)
     return mAP_bbox.mean(-1), mAP_bev.mean(-1), mAP_3d.mean(-1), None if mAP_aos is None else mAP_aos.mean(-1)
 
 
-def get_coco_eval_result(gt_annos, dt_annos, current_classes, dataset="kitti", device_id=0, metric="new"):
+def get_coco_eval_result(gt_annos, dt_annos, current_classes, dataset="kitti", device_id=0, metric="new", stats_device="cpu"):
     """-> result text (eval2.py:725-784): three numbers per line for either metric."""
     current_classes = _class_ids(current_classes)
     overlap_ranges = np.zeros([3, 3, len(current_classes)])
     for i, curcls in enumerate(current_classes):
         overlap_ranges[:, :, i] = np.array(COCO_RANGE[curcls])[:, np.newaxis]
     compute_aos = _alpha_is_valid(dt_annos)
-    mAPs = do_coco_style_eval(gt_annos, dt_annos, current_classes, overlap_ranges, compute_aos, dataset, device_id, metric)
+    mAPs = do_coco_style_eval(gt_annos, dt_annos, current_classes, overlap_ranges, compute_aos, dataset, device_id, metric, stats_device)
     result = ""
     for j, curcls in enumerate(current_classes):
         lo, hi, num = COCO_RANGE[curcls]
@@ -675,12 +1001,14 @@ _TRANSFORMS = {"rescale_pred": rescale_pred, "align_size": align_size, "align_fr
 def evaluate(result_path, label_path, image_ids, current_class=0, dataset="kitti", score_thresh=-1, device_id=0, metric="new",
              coco=False, toground=False, rescale_pred=None, align_size=False, align_front=False, reverse_align=False,
              dense_sample=False, direct_save=False, output_iou=False, adapted=False, planes_path=None, src_stats=None,
-             dst_stats=None, scale_map="regular", device="cuda"):
+             dst_stats=None, scale_map="regular", device="cuda", stats_device="cpu"):
     """Result folder + label folder + id list -> (result text, dict); the text alone with ``coco``; None with ``output_iou``
     (evaluate.py:84-275, the switches in the reference's order of application).  The transformed labels go where the reference
     puts them: grounded/, align_size/, align_front/, reverse_align/, with_iou/, with_iou_gt/ beside the result folder.
     planes_path defaults to <label folder>/../planes; reverse_align reads its two statistics from src_stats / dst_stats.
-    ``device`` selects how best matches and alignment are computed ("cuda": csrc/eval_match.hip, "cpu": numpy)."""
+    ``device`` selects how best matches and alignment are computed ("cuda": csrc/eval_match.hip, "cpu": numpy); ``stats_device`` where
+    the AP statistics run ("cpu": csrc/kitti_stats.hip's host entries, "cuda": csrc/kitti_ap.hip)."""
+    _check_stats_device(stats_device)
     g = _TRANSFORMS
     image_ids = list(image_ids)
     parent = os.path.dirname(result_path)
@@ -709,8 +1037,8 @@ def evaluate(result_path, label_path, image_ids, current_class=0, dataset="kitti
     if output_iou:
         return None
     if coco:
-        return get_coco_eval_result(gt_annos, dt_annos, current_class, dataset, device_id, metric)
-    text, ret = get_official_eval_result(gt_annos, dt_annos, current_class, dataset, dense_sample, device_id, metric)
+        return get_coco_eval_result(gt_annos, dt_annos, current_class, dataset, device_id, metric, stats_device)
+    text, ret = get_official_eval_result(gt_annos, dt_annos, current_class, dataset, dense_sample, device_id, metric, stats_device)
     if direct_save:
         g["direct_save"](result_path, text, ret["result"], toground, align_size, reverse_align, adapted)
     return text, ret
@@ -746,6 +1074,8 @@ def main(argv=None):
     ap.add_argument("--dst_stats", type=str, default=None, help="label_stats_<split>.json of the model's dataset")
     ap.add_argument("--scale_map", type=str, default="regular", choices=["regular", "gaussian", "log"])
     ap.add_argument("--device", type=str, default="cuda", choices=["cuda", "cpu"], help="best match / alignment: fused HIP launch or numpy")
+    ap.add_argument("--stats_device", type=str, default="cpu", choices=["cpu", "cuda"],
+                    help="AP statistics (flags, matching, PR sums): host entries or the device kernels; the same numbers")
     args = vars(ap.parse_args(argv))
     dataset_path = args.pop("dataset_path")
     split_file, label_path = args.pop("label_split_file"), args.pop("label_path")

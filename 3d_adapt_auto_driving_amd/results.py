@@ -65,13 +65,27 @@ def detections_to_annos(table, counts, source, cls_name="Car"):
     return ids, annos
 
 
-def evaluate_detections(table, counts, source, current_class=0, dataset="kitti", device_id=0, metric="new"):
+def prepare_gt(source, ids):
+    """The labels of scenes ``ids`` (in that order) parsed and tabulated once, for evaluate_detections(prepared_gt=...)."""
+    from . import kitti_eval
+    return kitti_eval.PreparedGT([kitti_eval.annos_from_lines(source.label_lines(i)) for i in ids], ids)
+
+
+def evaluate_detections(table, counts, source, current_class=0, dataset="kitti", device_id=0, metric="new", stats_device="cpu",
+                        prepared_gt=None):
     """Rank-0 tail of the sharded evaluation: AP of the gathered detections against the source's labels
-    (tools/eval_rcnn.py:706-713 -> evaluate/evaluate.py).  Returns (result text, dict)."""
+    (tools/eval_rcnn.py:706-713 -> evaluate/evaluate.py).  Returns (result text, dict).  stats_device: where the AP statistics run
+    (kitti_eval.eval_class); prepared_gt: prepare_gt(source, ids) of the same scenes, instead of parsing the labels again."""
     from . import kitti_eval
     ids, dt_annos = detections_to_annos(table, counts, source)
-    gt_annos = [kitti_eval.annos_from_lines(source.label_lines(i)) for i in ids]
-    return kitti_eval.get_official_eval_result(gt_annos, dt_annos, current_class, dataset, device_id=device_id, metric=metric)
+    if prepared_gt is None:
+        gt_annos = [kitti_eval.annos_from_lines(source.label_lines(i)) for i in ids]
+    elif prepared_gt.ids != ids:
+        raise ValueError("evaluate_detections: prepared_gt was made for other scenes than the gathered table holds")
+    else:
+        gt_annos = prepared_gt
+    return kitti_eval.get_official_eval_result(gt_annos, dt_annos, current_class, dataset, device_id=device_id, metric=metric,
+                                               stats_device=stats_device)
 
 
 class RecallStats:

@@ -751,6 +751,70 @@ int prcnn_kitti_accumulate_pr(int n_img, const long long *gt_nums, const long lo
                               int metric, double min_overlap, const double *thresholds, int n_thresh, int compute_aos,
                               double *pr);
 
+/* (1 + cos(gt alpha - dt alpha)) / 2 of every (detection j, ground-truth i) pair of every image, written at
+ * pair_off[image] + j * n_gt + i -- the overlap blocks' layout -- by the very cosine call prcnn_kitti_image_stats sums.  HOST
+ * pointers; gt_off / dt_off / pair_off (n_img + 1) i64 prefix offsets.  The device pass (prcnn_ap_pr) only ADDS these terms: a device
+ * cosine need not agree with libm's in the last bit, and the orientation similarity is compared bit for bit. */
+int prcnn_kitti_pair_cos(int n_img, const long long *gt_off, const long long *dt_off, const long long *pair_off,
+                         const double *gt_alpha, const double *dt_alpha, double *out);
+
+/* ---- evaluate/eval2.py: the same statistics on the device (csrc/kitti_ap.hip; DEVICE pointers unless said otherwise) ----
+ *
+ * Contract: every stage gives the bits of its host definition -- kitti_eval.split_flags / clean_data, calculate_iou, the host entries
+ * above, kitti_eval.thresholds_loop -- for any input without NaNs.  Nothing is read back between the stages; all launches go to
+ * `stream`.
+ *
+ * The split table: the concatenated columns of all images (kitti_eval.SplitTable).  Offsets are (n_img + 1) i64 prefix sums; pair_off
+ * counts n_dt x n_gt per image and a pair (j, i) of image m lives at pair_off[m] + j * n_gt_m + i.  Class codes are i8: 0 car,
+ * 1 pedestrian, 2 cyclist, 3 van, 4 person_sitting, -1 anything else (lower-cased names).  dc_bbox holds the rows named exactly
+ * "DontCare", image by image.  *_box3d (n,7) f64 = location x y z, dimensions l h w, rotation_y; *_bev (n,5) f32 = x z l w ry.
+ * max_dt = the largest n_dt of an image; ws_slot (n_img) i32 = rank of the image among those with n_dt > PRCNN_AP_REG_DETS, in image
+ * order (unread for the others): such an image keeps its scan flags in the workspace, any n_dt works.  Every entry below takes
+ * the table as `split` (HOST words, see the index enum). */
+enum { PRCNN_AP_SAMPLE_PTS = 41, PRCNN_AP_REG_DETS = 128 };
+/* The table is handed over as a HOST array of PRCNN_AP_SPLIT_WORDS i64 words: the counts, then the DEVICE pointers, at these indices. */
+enum { PRCNN_AP_N_IMG = 0, PRCNN_AP_MAX_DT, PRCNN_AP_N_GT, PRCNN_AP_N_DT, PRCNN_AP_N_DC, PRCNN_AP_N_PAIR,
+       PRCNN_AP_GT_OFF, PRCNN_AP_DT_OFF, PRCNN_AP_DC_OFF, PRCNN_AP_PAIR_OFF,      /* (n_img + 1) i64 each */
+       PRCNN_AP_WS_SLOT,                                                          /* (n_img) i32 */
+       PRCNN_AP_GT_CODE, PRCNN_AP_DT_CODE,                                        /* i8 */
+       PRCNN_AP_GT_OCCLUDED, PRCNN_AP_GT_TRUNCATED, PRCNN_AP_GT_BBOX, PRCNN_AP_GT_DEPTH, PRCNN_AP_GT_BOX3D,      /* f64 */
+       PRCNN_AP_DT_BBOX, PRCNN_AP_DT_DEPTH, PRCNN_AP_DT_SCORE, PRCNN_AP_DT_BOX3D, PRCNN_AP_DC_BBOX,              /* f64 */
+       PRCNN_AP_GT_BEV, PRCNN_AP_DT_BEV,                                          /* f32 */
+       PRCNN_AP_SPLIT_WORDS };
+
+/* clean_data (eval2.py:28-98; metric_old: eval_old.py:28-91) of the whole split for n_diff <= 8 difficulties in one launch.
+ * cls / sibling: class codes (sibling -2: none).  caps HOST (n_diff,5) f64 = max occlusion, max truncation, band near, band far,
+ * minimum bbox height.  -> ignored_gt (n_diff,n_gt) / ignored_dt (n_diff,n_dt) i8 in {-1,0,1}, num_valid_gt (n_diff) i32. */
+int prcnn_ap_flags(const long long *split, int cls, int sibling, int metric_old, int n_diff, const double *caps,
+                   char *ignored_gt, char *ignored_dt, int *num_valid_gt, void *stream);
+
+/* Overlap blocks in f64, flat (n_pair): kind 0 image_box_overlap(dt, gt, -1); kind 2 the 3D overlap from rinc (n_pair) f32, the
+ * criterion-2 output of prcnn_rotate_iou_eval_segmented over dt_bev / gt_bev (kind 1 is that launch with criterion -1, widened). */
+int prcnn_ap_overlaps(const long long *split, int kind, const float *rinc, double *out, void *stream);
+
+/* Pass 1 for every (image, group), group = difficulty * n_lev + level; min_overlaps (n_lev) f64; overlaps (n_pair) f64.
+ * -> scores (n_groups,n_gt): the matched detection's score in the slot of its ground-truth box, -inf elsewhere; valid (n_groups,n_gt)
+ * i8 marks.  workspace: workspace_words >= ceil(max_dt / 64) u64 words per (image with a ws_slot, group); unused (may be NULL) when
+ * max_dt <= PRCNN_AP_REG_DETS. */
+int prcnn_ap_scores(const long long *split, const char *ignored_gt, const char *ignored_dt, int n_diff, int n_lev,
+                    const double *min_overlaps, const double *overlaps, int kind, double *scores, char *valid,
+                    unsigned long long *workspace, long long workspace_words, void *stream);
+
+/* get_thresholds (eval2.py:8-25) per group on its row of sorted_scores (n_groups,n_gt_total), descending, the first count[g] valid;
+ * num_valid_gt (n_groups / n_lev) i32.  -> thresholds (n_groups,41) f64, n_thr (n_groups) i32 (what the loop takes; > 41 is stored
+ * up to 41 only). */
+int prcnn_ap_thresholds(int n_groups, int n_lev, long long n_gt_total, const double *sorted_scores, const int *count,
+                        const int *num_valid_gt, double *thresholds, int *n_thr, void *stream);
+
+/* Pass 2 + sums: image_stats with compute_fp for every (image, group, threshold < n_thr) and pr (n_groups,41,4) f64 =
+ * [tp, fp, fn, similarity].  counts (n_groups,41,3) u64 scratch (cleared here).  Orientation: pair_cos (n_pair) from
+ * prcnn_kitti_pair_cos and sim_img (n_img,n_groups,41) f64 scratch, both or neither; per-image sums add in ground-truth order, the
+ * total in image order.  workspace: 2 x 64 x workspace_words u64 words per (image with a ws_slot, group). */
+int prcnn_ap_pr(const long long *split, const char *ignored_gt, const char *ignored_dt, int n_diff, int n_lev,
+                const double *min_overlaps, const double *overlaps, int kind, const double *thresholds, const int *n_thr,
+                const double *pair_cos, unsigned long long *counts, double *sim_img, double *pr,
+                unsigned long long *workspace, long long workspace_words, void *stream);
+
 /* Statistical normalization (stat_norm/norm.py:186-330 rescale_ptc) over a batch of ragged scenes (csrc/stat_norm.hip).
  * Device pointers; offsets are prefix sums over the scenes (n_scenes + 1 entries).  Points: velo (sum n, 4) f32 raw .bin rows,
  * pt_off; 64-point tiles: tile_off; rescaled boxes: box_off, boxd (n_box, PRCNN_SN_BOXD) f64 records, boxi (n_box, PRCNN_SN_BOXI) i32 state (zeroed),

@@ -6,7 +6,10 @@ batch (with (a): the warm-up and the captures), the remaining batches, the AP.  
 (loader and writer processes are the same for both ways and are not what this probe is about); a new process per checkpoint -- the
 interpreter, the imports, the HIP runtime -- comes on top of (a) and is NOT in its column.
 
-  python profiles/eval_sweep_probe.py [--ckpts 4] [--scenes 512] [--batch_size 8] [--reps 3] [--out FILE.json]"""
+--ap_stats_device cuda runs the AP phase with its statistics on the device (kitti_eval's stats_device) against the labels' table
+built once before the clock starts, as the sweep does.
+
+  python profiles/eval_sweep_probe.py [--ckpts 4] [--scenes 512] [--batch_size 8] [--reps 3] [--ap_stats_device cpu|cuda] [--out FILE.json]"""
 import argparse, gc, importlib, json, os, statistics, sys, tempfile, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -19,6 +22,7 @@ import helpers
 ap = argparse.ArgumentParser()
 ap.add_argument("--ckpts", type=int, default=4); ap.add_argument("--scenes", type=int, default=512); ap.add_argument("--batch_size", type=int, default=8)
 ap.add_argument("--reps", type=int, default=3); ap.add_argument("--out", type=str, default=None)
+ap.add_argument("--ap_stats_device", type=str, default="cpu", choices=["cpu", "cuda"])
 a = ap.parse_args()
 dev = torch.device("cuda", 0); cfg = C.default_eval_cfg(); model = E.build_model(cfg, dev, seed=0)
 src = K.SyntheticSource(cfg, a.scenes)
@@ -34,6 +38,7 @@ for k in range(a.ckpts):
     files.append(os.path.join(tmp, "checkpoint_epoch_%d.pth" % k))
     torch.save({"model_state": model.state_dict(), "epoch": k, "it": 0}, files[-1])
 clock = time.perf_counter
+prepared_gt = E.prepare_gt(src, sorted(ids)) if a.ap_stats_device == "cuda" else None
 
 
 def sync():
@@ -77,7 +82,7 @@ def one(path, runner):
     dets = [tuple(x.cpu() for x in d) for d in dets]
     t4 = sync(); t["inference"] = t4 - t3
     table, counts = G.pack_detections(ids, dets, M)
-    E.evaluate_detections(table, counts, src)
+    E.evaluate_detections(table, counts, src, stats_device=a.ap_stats_device, prepared_gt=prepared_gt)
     t["ap"] = clock() - t4
     return t, runner, dets
 
@@ -109,7 +114,7 @@ def column(sel, key):
 
 
 phases = ("load", "build_or_reload", "first_batch", "inference", "ap")
-report = {"scenes": len(ids), "batch_size": B, "ckpts": a.ckpts, "reps": a.reps,
+report = {"scenes": len(ids), "batch_size": B, "ckpts": a.ckpts, "reps": a.reps, "ap_stats_device": a.ap_stats_device,
           "a_new_engine_per_ckpt": {p: column(rows["a"], p) for p in phases},
           "b_reload_warm": {p: column([r for r in rows["b"] if r["warm"]], p) for p in phases},
           "b_first_ckpt_of_a_sweep": {p: column([r for r in rows["b"] if not r["warm"]], p) for p in phases}}
