@@ -37,20 +37,26 @@ constexpr int NMS_THREADS = 512;
 constexpr int NMS_MAX_N = 65536;   // removed-bitmask lives in LDS (8 KiB)
 constexpr int NMS_RCH = 8;         // rows per work item
 
-// ---- quota form: max_keep <= NMS_QUOTA_MAX (the proposal layer keeps 70 + 30 of up to 6300 + 2700 boxes per scene) ------------
+// ---- quota form: max_keep <= NMS_QUOTA_MAX, or <= NMS_QUOTA_WIDE in its second instantiation (the proposal layer keeps 70 + 30 of up to 6300 + 2700 boxes per scene) ------------
 // The general kernel below lets the kept rows of a block knock out EVERY later column before it moves on: 6236 columns x 64
 // rows of IoUs after the first block of a 6300-box problem whose quota is reached inside the second block (0.22 ms, the
 // longest kernel of the proposal stream).  Here the kept boxes (at most max_keep of them) stay in LDS and a block's 64 columns
 // are tested against them when the block is staged: 64 x kept IoUs per block, nothing for columns that are never reached.
 // Same decisions: a column is dropped iff an earlier KEPT row overlaps it (row, column argument order as nms_kernel :285).
+// CAP = rows of the kept-box table, a template parameter: <NMS_QUOTA_MAX> is the inference form (70 + 30 kept; 7 KiB of table, 9.3 KiB
+// of LDS in all), <NMS_QUOTA_WIDE> the training form (RPN_POST_NMS_TOP_N = 512: 358 + 154 kept at thresh 0.85, where little is
+// suppressed and the general kernel's step D is at its worst; 14 KiB of table, 16.3 KiB of LDS).  One 512-thread workgroup per problem and
+// 2 * B problems per launch: the grid never fills a CU's 160 KiB, so neither footprint bounds occupancy.  Same code for both.
 constexpr int NMS_QUOTA_MAX = 256;
+constexpr int NMS_QUOTA_WIDE = 512;
 
+template <int CAP>
 __global__ __launch_bounds__(NMS_THREADS) void nms_quota_kernel(
     int n_max, const int *__restrict__ counts, const float *__restrict__ boxes_all, float thresh,
     int max_keep, int *__restrict__ keep_all, int *__restrict__ num_keep_all)
 {
     __shared__ float s_row[64 * 7];             // the 64 row boxes of the block
-    __shared__ float s_kbox[NMS_QUOTA_MAX * 7]; // the kept boxes so far (same 7-float slots as s_row)
+    __shared__ float s_kbox[CAP * 7];           // the kept boxes so far (same 7-float slots as s_row); max_keep <= CAP (nms_device)
     __shared__ unsigned long long s_diag[64];   // word(c): rows of the block with IoU > thresh, r < c
     __shared__ unsigned long long s_gone;       // columns of the block dropped by earlier kept rows
     __shared__ int s_nkeep;
@@ -318,7 +324,9 @@ int nms_device(int nprob, int n_max, const int *counts, const float *boxes, floa
     if (rotated)
         hipLaunchKernelGGL(nms_lazy_kernel<true>, dim3(nprob), dim3(NMS_THREADS), 0, st, n_max, counts, boxes, thresh, max_keep, keep, num_keep);
     else if (quota_form && max_keep >= 1 && max_keep <= NMS_QUOTA_MAX)
-        hipLaunchKernelGGL(nms_quota_kernel, dim3(nprob), dim3(NMS_THREADS), 0, st, n_max, counts, boxes, thresh, max_keep, keep, num_keep);
+        hipLaunchKernelGGL(nms_quota_kernel<NMS_QUOTA_MAX>, dim3(nprob), dim3(NMS_THREADS), 0, st, n_max, counts, boxes, thresh, max_keep, keep, num_keep);
+    else if (quota_form && max_keep > NMS_QUOTA_MAX && max_keep <= NMS_QUOTA_WIDE)       // the proposal layer's training quotas (<= 358 + 154)
+        hipLaunchKernelGGL(nms_quota_kernel<NMS_QUOTA_WIDE>, dim3(nprob), dim3(NMS_THREADS), 0, st, n_max, counts, boxes, thresh, max_keep, keep, num_keep);
     else
         hipLaunchKernelGGL(nms_lazy_kernel<false>, dim3(nprob), dim3(NMS_THREADS), 0, st, n_max, counts, boxes, thresh, max_keep, keep, num_keep);
     return check_launch("nms");

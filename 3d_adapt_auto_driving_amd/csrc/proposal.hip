@@ -10,8 +10,9 @@
 //   3. band_select_kernel    one workgroup per scene: ordered compaction (wave ballot + LDS prefix) of the
 //                            sorted proposals into the (0,40] m and (40,80] m tables, top 70 % / 30 % of
 //                            RPN_PRE_NMS_TOP_N, with the reference's "no far points" fallback
-//   4. nms_lazy_kernel       (iou3d.hip) all 2*B problems in one launch, stops at the post-NMS quota
-//   5. assemble_rois_kernel  near keeps, then far keeps, zero padded -> rois (B, M, 7), scores (B, M)
+//   4. nms_lazy_kernel       (iou3d.hip) all 2*B problems in one launch, stops at the post-NMS quota (axis-aligned: its quota form,
+//                            nms_quota_kernel, with a 256- or 512-row kept-box table)
+//   5. assemble_rois_kernel  near keeps, then far keeps, zero padded -> rois (B, M, 7), scores (B, M); M <= 512
 // No host synchronisation anywhere.
 #include "common.hpp"
 #include "rbox_iou.hpp"
@@ -267,24 +268,27 @@ __global__ __launch_bounds__(128) void assemble_rois_kernel(
     int rows, int keep_stride, int post_near, int post_far, const float *__restrict__ payload,
     const int *__restrict__ keep, const int *__restrict__ num, float *__restrict__ rois, float *__restrict__ scores)
 {
-    const int b = blockIdx.x, j = threadIdx.x;
+    // one workgroup per scene, lane j takes RoIs j, j + 128, ...: one trip for the inference quotas (post <= 128), up to four for
+    // the training ones (post <= 512)
+    const int b = blockIdx.x;
     const int post = post_near + post_far;
-    if (j >= post) return;
     const int kn = min(num[b * 2], post_near), kf = min(num[b * 2 + 1], post_far);
-    float *o = rois + ((long)b * post + j) * 7;
-    int band = -1, slot = 0;
-    if (j < kn) { band = 0; slot = keep[(b * 2) * keep_stride + j]; }
-    else if (j < kn + kf) { band = 1; slot = keep[(b * 2 + 1) * keep_stride + (j - kn)]; }
-    if (band < 0) {
+    for (int j = threadIdx.x; j < post; j += 128) {
+        float *o = rois + ((long)b * post + j) * 7;
+        int band = -1, slot = 0;
+        if (j < kn) { band = 0; slot = keep[(b * 2) * keep_stride + j]; }
+        else if (j < kn + kf) { band = 1; slot = keep[(b * 2 + 1) * keep_stride + (j - kn)]; }
+        if (band < 0) {
 #pragma unroll
-        for (int e = 0; e < 7; ++e) o[e] = 0.f;
-        scores[(long)b * post + j] = 0.f;
-        return;
+            for (int e = 0; e < 7; ++e) o[e] = 0.f;
+            scores[(long)b * post + j] = 0.f;
+            continue;
+        }
+        const float *q = payload + (((long)b * 2 + band) * rows + slot) * 8;
+#pragma unroll
+        for (int e = 0; e < 7; ++e) o[e] = q[e];
+        scores[(long)b * post + j] = q[7];
     }
-    const float *q = payload + (((long)b * 2 + band) * rows + slot) * 8;
-#pragma unroll
-    for (int e = 0; e < 7; ++e) o[e] = q[e];
-    scores[(long)b * post + j] = q[7];
 }
 
 // ---- final stage (eval_rcnn.py:506-530, 611-629): decode the RCNN regression against its RoI, score
@@ -586,7 +590,9 @@ static int rpn_proposals_any(int b, int n, const DecodeCfg *dc, int pre_nms_top_
     PRCNN_REQUIRE(npad <= 65536, "rpn_proposals: n=%d > 65536 points per scene unsupported by the fused path", n);   // (round 5: 32768 = tools/cfgs/double.yaml; the chunked sort and the band scan take any n)
     const int pre_near = (int)(pre_nms_top_n * 0.7), pre_far = pre_nms_top_n - pre_near;
     const int post_near = (int)(post_nms_top_n * 0.7), post_far = post_nms_top_n - post_near;
-    PRCNN_REQUIRE(post_nms_top_n <= 128 && post_near >= post_far && pre_near >= pre_far, "rpn_proposals: unsupported quotas");
+    // 512 = TRAIN.RPN_POST_NMS_TOP_N of the shipped configurations: 358 near + 154 far, the axis-aligned NMS on the quota form's second
+    // instantiation (iou3d.hip), the assembly in four trips; <= 128 launches what it always launched
+    PRCNN_REQUIRE(post_nms_top_n >= 0 && post_nms_top_n <= 512 && post_near >= post_far && pre_near >= pre_far, "rpn_proposals: unsupported quotas");
     if (b == 0) return PRCNN_OK;
     PRCNN_REQUIRE(scores && rois && roi_scores && (boxes_in || (xyz && reg)), "rpn_proposals: null pointer");
     hipStream_t st = (hipStream_t)stream;
@@ -644,6 +650,7 @@ static int rpn_proposals_any(int b, int n, const DecodeCfg *dc, int pre_nms_top_
 
 // xyz (b,n,3), scores (b,n) raw RPN scores, reg (b,n,channels) -> rois (b, post_top_n, 7), roi_scores (b, post_top_n)
 // distance-based proposal (RPN_DISTANCE_BASED_PROPOSE), get_y_by_bin = False, get_ry_fine = False.
+// post_top_n <= 512 (near int(0.7 post) <= 358, far <= 154; near >= far for pre and post): inference asks for <= 128, training for 512.
 extern "C" int prcnn_rpn_proposals(int b, int n, int channels, float loc_scope, float loc_bin_size,
                                    int num_head_bin, int xz_fine, const float *anchor_size_host,
                                    int pre_nms_top_n, int post_nms_top_n, float nms_thresh, int rotated_nms,

@@ -396,10 +396,16 @@ def _narrow_pair_weights(scales):
 
 
 class FastPointRCNN:
-    def __init__(self, model, cfg, _fresh=None):
-        """_fresh (reload_weights only): a dict that receives the SharedMLP folds instead of the modules' caches"""
-        assert not model.training, "FastPointRCNN is an inference engine: call model.eval() first"
-        if cfg.RCNN.ENABLED and cfg.RCNN.USE_INTENSITY:
+    def __init__(self, model, cfg, _fresh=None, rpn_only=False):
+        """_fresh (reload_weights only): a dict that receives the SharedMLP folds instead of the modules' caches.
+        rpn_only (net/frozen_rpn.py: the frozen first stage of --train_mode rcnn): the engine is built over model.rpn alone -- the state
+        it folds and version-tracks is the RPN's parameters and buffers, nothing of rcnn_net is folded or watched (the optimizer steps
+        on it), only model.rpn has to be in eval mode, and the fused proposal path takes the training quotas (`_tail_decode_cfg`)."""
+        self.rpn_only = bool(rpn_only)
+        self.rcnn_on = bool(cfg.RCNN.ENABLED) and not self.rpn_only
+        self.post_max = 512 if self.rpn_only else 128         # RPN_POST_NMS_TOP_N the fused proposal path is asked for (csrc/proposal.hip takes <= 512)
+        self._check_eval(model)
+        if self.rcnn_on and cfg.RCNN.USE_INTENSITY:
             raise NotImplementedError("fast path: cfg.RCNN.USE_INTENSITY (reflectance as an RCNN input feature) is not covered")
         self.model, self.cfg = model, cfg
         # per-point input features of the backbone (cfg.RPN.USE_INTENSITY: one reflectance column, rpn.py:17 /
@@ -409,9 +415,9 @@ class FastPointRCNN:
         # heads run layer by layer; the coordinates-only specialisations (csrc/sa_xyz_mlp.hip, the early SA levels on the
         # geometry stream, csrc/rpn_tail.hip) are for the shipped configurations.
         self.in_feat = int(model.rpn.backbone_net.SA_modules[0].mlps[0][0].conv.in_channels) - 3
-        self._state = _state_tensors(model)
+        self._state = _state_tensors(self._tracked(model))
         self._folded_at = _state_version(self._state)       # BN is folded into the weights HERE: see check_weights()
-        self._shapes = _state_shapes(model)                  # what reload_weights() accepts
+        self._shapes = _state_shapes(self._tracked(model))   # what reload_weights() accepts
         rpn = model.rpn
         bb = rpn.backbone_net
         self.sa = []
@@ -435,7 +441,7 @@ class FastPointRCNN:
         self._zero_bias = self.rpn_cls.layers[0][0].new_zeros((max([1024] + [m.layers[0][0].shape[1] for m in self.fp]),))
         self._groupall = {}
         self._pm_ok = self._is_covered = None
-        if cfg.RCNN.ENABLED:
+        if self.rcnn_on:
             r = model.rcnn_net
             self.xyz_up = _Mlp(_fold_shared_mlp(r.xyz_up_layer, _fresh))
             self.merge_down = _Mlp(_fold_shared_mlp(r.merge_down_layer, _fresh))
@@ -455,12 +461,22 @@ class FastPointRCNN:
                     c0[0].shape == r0[0].shape and c0[0].shape[0] % 128 == 0 and c0[0].shape[1] % 128 == 0):
                 self.rcnn_head1 = (torch.cat([c0[0], r0[0]], 1).contiguous(), torch.cat([c0[1], r0[1]]).contiguous(), c0[0].shape[1])
 
+    def _tracked(self, model):
+        """the module whose parameters and buffers this engine folds and version-tracks"""
+        return model.rpn if self.rpn_only else model
+
+    def _check_eval(self, model):
+        if self.rpn_only:
+            assert not model.rpn.training, "FastPointRCNN(rpn_only): the first stage is folded with its running statistics: call model.rpn.eval() first"
+        else:
+            assert not model.training, "FastPointRCNN is an inference engine: call model.eval() first"
+
     def _covered(self):
         """True when every MLP of this network runs on a kernel of this build with the product switches at their defaults:
         RPN SA scales on the packed / wide / coordinates-only kernels, the fused RPN tail, the RCNN entrance chain and SA levels."""
         try:
             ok = bool(PAD128 and self.rpn_tail is not None) and all(level.on_packed for level in self.sa)
-            if self.cfg.RCNN.ENABLED:
+            if self.rcnn_on:
                 ok = ok and self._point_mlp_ok() and all(level.mlp.on_packed for level in self.rcnn_sa)
             return ok
         except Exception:
@@ -514,7 +530,7 @@ class FastPointRCNN:
             out += _mlp_tensors("fp[%d]" % k, m)
         out += _mlp_tensors("rpn_cls", self.rpn_cls) + _mlp_tensors("rpn_reg", self.rpn_reg)
         out += [("rpn_tail[%s]" % key, self.rpn_tail[key]) for key in ("wcat", "bcat", "wc2", "bc2", "w1", "wcat_lin") if self.rpn_tail is not None]
-        if self.cfg.RCNN.ENABLED:
+        if self.rcnn_on:
             out += _mlp_tensors("xyz_up", self.xyz_up) + _mlp_tensors("merge_down", self.merge_down)
             for k, level in enumerate(self.rcnn_sa):
                 out += _mlp_tensors("rcnn_sa[%d]" % k, level.mlp)
@@ -535,8 +551,8 @@ class FastPointRCNN:
         before anything is written.  Nothing allocated here outlives the call; the copies run on the caller's current stream --
         the caller orders them against other streams that run the engine (the runners' reload_weights() do)."""
         model = self.model
-        assert not model.training, "FastPointRCNN is an inference engine: call model.eval() first"
-        now = _state_shapes(model)
+        self._check_eval(model)
+        now = _state_shapes(self._tracked(model))
         if [n for n, _ in now] != [n for n, _ in self._shapes]:
             odd = sorted(set(n for n, _ in now) ^ set(n for n, _ in self._shapes))
             raise ValueError("FastPointRCNN.reload_weights: the model's parameters and buffers are not the ones the engine was built for "
@@ -546,7 +562,7 @@ class FastPointRCNN:
                 raise ValueError("FastPointRCNN.reload_weights: %s has shape %s, the engine was built for %s" % (n, shape, built))
         folds = {}
         try:
-            fresh = FastPointRCNN(model, self.cfg, _fresh=folds)
+            fresh = FastPointRCNN(model, self.cfg, _fresh=folds, rpn_only=self.rpn_only)
         except (AssertionError, NotImplementedError, IndexError, RuntimeError) as e:
             raise ValueError("FastPointRCNN.reload_weights: the model no longer folds into this engine (%s: %s)" % (type(e).__name__, e))
         mine, new = self.weight_tensors(), fresh.weight_tensors()
@@ -556,7 +572,7 @@ class FastPointRCNN:
             if n != n2 or old.shape != t.shape or old.dtype != t.dtype or old.device != t.device:
                 raise ValueError("FastPointRCNN.reload_weights: %s is %s %s on %s, the engine holds %s %s %s on %s"
                                  % (n2, tuple(t.shape), t.dtype, t.device, n, tuple(old.shape), old.dtype, old.device))
-        cached = [m for m in model.modules() if "_prcnn_folded" in m.__dict__]
+        cached = [m for m in self._tracked(model).modules() if "_prcnn_folded" in m.__dict__]
         for m in cached:
             if id(m) not in folds:
                 folds[id(m)] = fused_mlp.fold_fresh(m)
@@ -570,7 +586,7 @@ class FastPointRCNN:
             old.copy_(t)
         if SPLIT_BF16 and getattr(pu.pointnet2, "IS_HIP_EXTENSION", False) and has_entry(pu.pointnet2, "resplit_weights_bf16x3"):
             pu.pointnet2.resplit_weights_bf16x3([t for _, t in mine])
-        self._state = _state_tensors(model)
+        self._state = _state_tensors(self._tracked(model))
         self._folded_at = _state_version(self._state)
 
     # ------------------------------------------------------------------ geometry (xyz only)
@@ -730,7 +746,7 @@ class FastPointRCNN:
         """Spatial groups of the input clouds for the RCNN's RoI pooling (csrc/point_groups.hip prcnn_point_groups): xyz only, so they
         ride with the geometry chain on its side stream."""
         rp = roipool3d_utils.roipool3d_cuda
-        if not (self.cfg.RCNN.ENABLED and has_entry(rp, "point_groups") and xyz.shape[1] % 64 == 0 and xyz.shape[1] <= 65536):
+        if not (self.rcnn_on and has_entry(rp, "point_groups") and xyz.shape[1] % 64 == 0 and xyz.shape[1] <= 65536):
             return None
         return rp.point_groups(xyz)
 
@@ -975,12 +991,13 @@ class FastPointRCNN:
     def _tail_decode_cfg(self, N):
         """-> the arguments of the fused tail's decode when this configuration's proposal layer can take decoded boxes (the fused
         device-side layer of net/proposal_layer.py over the served regression layout, clouds of N <= 65536 points: ProposalLayer's own
-        guard -- a larger cloud keeps its regression rows and goes through ProposalLayer.forward's general path), else None"""
+        guard -- a larger cloud keeps its regression rows and goes through ProposalLayer.forward's general path), else None.
+        M <= post_max: 128 as ProposalLayer.forward's guard says, 512 for an engine built rpn_only (the training quotas)"""
         cfg, pl = self.cfg, self.model.rpn.proposal_layer
         M = cfg[pl.mode].RPN_POST_NMS_TOP_N
         ext3 = pl_ext()
         if not (USE_FP_LINEAR and self.rpn_tail is not None and getattr(pl, "fused", False) and N <= 65536
-                and cfg.TEST.RPN_DISTANCE_BASED_PROPOSE and M <= 128 and cfg.RPN.NMS_TYPE in ("normal", "rotate")
+                and cfg.TEST.RPN_DISTANCE_BASED_PROPOSE and M <= self.post_max and cfg.RPN.NMS_TYPE in ("normal", "rotate")
                 and has_entry(pu.pointnet2, "rpn_tail_lin_boxes_wrapper") and has_entry(ext3, "rpn_proposals_boxes")
                 and pu.pointnet2.rpn_tail_boxes_supported(self.rpn_tail["n_reg"], cfg.RPN.LOC_SCOPE, cfg.RPN.LOC_BIN_SIZE,
                                                          cfg.RPN.NUM_HEAD_BIN, cfg.RPN.LOC_XZ_FINE)):
@@ -1061,7 +1078,7 @@ class FastPointRCNN:
     @torch.no_grad()
     def propose(self, st):
         """The proposal layer on the RPN stage's outputs -> (rois, roi_scores_raw); also fills in the per-point RCNN inputs."""
-        if self.cfg.RCNN.ENABLED:
+        if self.rcnn_on:
             self.point_aux(st)
         if st.get("rpn_boxes") is not None:                  # decoded by the fused tail (rpn_stage): sort, bands, NMS, assembly
             cfg, pl = self.cfg, self.model.rpn.proposal_layer
@@ -1099,7 +1116,7 @@ class FastPointRCNN:
         out = self.rpn_stage(pts_input, geo, want_reg=want_reg)
         rois, roi_scores_raw = self.propose(out)
         out.update({"rois": rois, "roi_scores_raw": roi_scores_raw})
-        if not self.cfg.RCNN.ENABLED:                        # --eval_mode rpn: the RPN's outputs and its proposals
+        if not self.rcnn_on:                                 # --eval_mode rpn: the RPN's outputs and its proposals
             return out
         out.update(self.rcnn_stage(out, rois))
         return out

@@ -21,6 +21,16 @@ class PointRCNN(nn.Module):
                 raise NotImplementedError("RCNN backbone %r" % cfg.RCNN.BACKBONE)
             # 128 = width of the RPN backbone features handed to the second stage
             self.rcnn_net = RCNNNet(cfg, num_classes=num_classes, input_channels=128, use_xyz=use_xyz)
+        self._engine_first_stage = None          # use_engine_first_stage()
+
+    def use_engine_first_stage(self, stage):
+        """stage: a net/frozen_rpn.py FrozenFirstStage built over this model, or None.  While set (cfg.RPN.FIXED only) forward() takes the
+        first stage's outputs and the RCNN's feed from it instead of self.rpn; unset, forward() is what it always was."""
+        cfg = self.cfg
+        if stage is not None and not (cfg.RPN.ENABLED and cfg.RPN.FIXED and cfg.RCNN.ENABLED):
+            raise ValueError("PointRCNN.use_engine_first_stage: the engine stands in for a FIXED first stage under an RCNN "
+                             "(RPN.ENABLED, RPN.FIXED and RCNN.ENABLED), this model's RPN is trained or has no second stage")
+        self._engine_first_stage = stage
 
     # ---- stage 1: point-wise foreground score + box regression, with the RPN frozen when cfg.RPN.FIXED
     def _first_stage(self, batch):
@@ -48,11 +58,31 @@ class PointRCNN(nn.Module):
             if not cfg.RCNN.ENABLED:
                 raise NotImplementedError
             return self.rcnn_net(input_data)
+        if self._engine_first_stage is not None and cfg.RPN.FIXED:
+            return self._forward_engine_first_stage(input_data)
         result = dict(self._first_stage(input_data))
         if cfg.RCNN.ENABLED:
             extras, feed = self._second_stage_inputs(result)
             result.update(extras)
             if self.training:
                 feed["gt_boxes3d"] = input_data["gt_boxes3d"]
+                # the target stage takes contiguous tensors (rcnn_targets._check_inputs) and the module graph's features are a
+                # transposed view: without this copy a --train_mode rcnn iteration raised there
+                feed["rpn_features"] = feed["rpn_features"].contiguous()
             result.update(self.rcnn_net(feed))
+        return result
+
+    def _forward_engine_first_stage(self, input_data):
+        """forward() with the fixed first stage on the inference engine: no regression rows (the fused tail decodes the boxes itself),
+        features point-major as the RCNN's feed wants them"""
+        from .frozen_rpn import FEED_KEYS, EXTRA_KEYS
+        self.rpn.eval()
+        out = self._engine_first_stage(input_data["pts_input"])
+        result = {"rpn_cls": out["rpn_cls"], "rpn_reg": None, "backbone_xyz": out["backbone_xyz"],
+                  "backbone_features": out["rpn_features"].permute((0, 2, 1))}
+        result.update({k: out[k] for k in EXTRA_KEYS})
+        feed = {k: out[k] for k in FEED_KEYS}
+        if self.training:
+            feed["gt_boxes3d"] = input_data["gt_boxes3d"]
+        result.update(self.rcnn_net(feed))
         return result

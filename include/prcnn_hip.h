@@ -581,7 +581,10 @@ int prcnn_point_aux(long rows, float thresh, const float *scores, const float *x
  * decode -> per-scene score sort -> (0,40] / (40,80] m band selection (top 70 % / 30 % of pre_nms_top_n,
  * with the "no far points" fallback) -> batched NMS -> rois (b, post_nms_top_n, 7) + raw scores, zero padded.
  * xyz (b,n,3), scores (b,n), reg (b,n,channels); anchor_size_host = 3 floats in HOST memory (h,w,l).
- * n <= 65536 per scene (round 5: the chunked sort and the band scan take any n; tools/cfgs/double.yaml has 32768). */
+ * n <= 65536 per scene (round 5: the chunked sort and the band scan take any n; tools/cfgs/double.yaml has 32768).
+ * Quotas: post_nms_top_n <= 512 (near int(0.7 post) <= 358, far post - near <= 154), near >= far for both pre and post; anything
+ * else returns PRCNN_EINVAL "rpn_proposals: unsupported quotas".  post <= 128 (inference) and 129..512 (TRAIN.RPN_POST_NMS_TOP_N)
+ * differ in the axis-aligned NMS's kept-box table (256 / 512 rows of LDS) and in the trips of the assembly, not in any decision. */
 int prcnn_rpn_proposals(int b, int n, int channels, float loc_scope, float loc_bin_size, int num_head_bin,
                         int xz_fine, const float *anchor_size_host, int pre_nms_top_n, int post_nms_top_n,
                         float nms_thresh, int rotated_nms, const float *xyz, const float *scores,
