@@ -1,4 +1,4 @@
-// rbox_iou.hpp -- the BEV box geometry shared by the NMS kernels (iou3d.hip) and the fused final stage (proposal.hip): rotated overlap /
+// rbox_iou.hpp -- the BEV box geometry shared by the NMS kernels (nms_device.hip, iou3d.hip) and the fused final stage (final_stage.hip): rotated overlap /
 // IoU of two BEV boxes as the reference computes them (lib/utils/iou3d/src/iou3d_kernel.cu:50-221), the axis-aligned IoU (:295-303),
 // and the (row, column) suppression test of the NMS kernels.  Moved out of iou3d.hip unchanged (round 4).
 #pragma once

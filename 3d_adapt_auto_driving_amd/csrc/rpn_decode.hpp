@@ -1,5 +1,5 @@
 // rpn_decode.hpp -- the arithmetic of the bin-based box decode (decode_bbox_target, lib/utils/bbox_transform.py:24-127), written once for
-// its three sites: rpn_decode_kernel and rcnn_decode_box (csrc/proposal.hip: one lane per row, from the stored regression rows) and the
+// its three sites: rpn_decode_kernel (csrc/proposal.hip) and rcnn_decode_box (csrc/final_stage.hip), one lane per row, from the stored regression rows, and the
 // decode inside the fused RPN tail (csrc/rpn_tail.hip rpn_tail_lin_kernel<true, *>: four lanes per row, from the rows where they stand in
 // LDS; the RL_DEC_* blocks below).  One rounding per operation everywhere (__f*_rn: no contraction whatever the flags), in the
 // reference's order.
@@ -21,6 +21,24 @@ __device__ __forceinline__ float rd_anchor_size(float v, float a) { return __fad
 // arg-max over a row, first maximum, a NaN counts as the largest value (torch.argmax): does V displace the running best BV?  (A macro:
 // as a function returning bool it compiled to other compares inside rpn_tail_lin_kernel<true, *>'s first stage, 2840 -> 2813 opcodes.)
 #define RD_ARGMAX_TAKES(V, BV) ((V) > (BV) || ((V) != (V) && (BV) == (BV)))
+
+// the arg-max of the two one-lane-per-row decoders, over n values in memory
+__device__ __forceinline__ int argmax_row(const float *p, int n)
+{
+    int best = 0;
+    float bv = p[0];
+    for (int i = 1; i < n; ++i)                    // first maximum; a NaN counts as the largest value (torch.argmax)
+        if (RD_ARGMAX_TAKES(p[i], bv)) { bv = p[i]; best = i; }
+    return best;
+}
+
+// torch.remainder for f32: fmod, then shifted into the sign of the divisor
+__device__ __forceinline__ float torch_remainder(float a, float b)
+{
+    float m = fmodf(a, b);
+    if (m != 0.f && ((b < 0.f) != (m < 0.f))) m += b;
+    return m;
+}
 
 // fmodf(a, (float)(2 pi)) WITHOUT the library's loop (the fused decode rides inside a hand-scheduled MFMA stage: no control flow).
 // The remainder of two floats is exact in f32's own format, so it can be taken in f64: three reduction steps modulo b 2^80, b 2^40

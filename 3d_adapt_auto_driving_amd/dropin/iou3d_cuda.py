@@ -61,7 +61,7 @@ def nms_normal_gpu(boxes, keep, nms_overlap_thresh):
 
 # -- extension beyond the reference module: batched, device-resident greedy NMS -------------
 def nms_device(boxes, counts, thresh, rotated, max_keep, keep, num_keep):
-    """boxes (P, n_max, 5) f32, counts (P) i32 or None, keep (P, max_keep) i32, num_keep (P) i32."""
+    """csrc/nms_device.hip.  boxes (P, n_max, 5) f32, counts (P) i32 or None, keep (P, max_keep) i32, num_keep (P) i32."""
     _chk(boxes)
     _lib.call("prcnn_nms_device", boxes.size(0), boxes.size(1), _lib.ptr(counts), boxes.data_ptr(),
               float(thresh), int(bool(rotated)), int(max_keep), keep.data_ptr(), num_keep.data_ptr(),
@@ -111,7 +111,7 @@ def rcnn_postprocess_blobs(rois, rcnn_reg, rcnn_cls, anchor_size, loc_scope, loc
 
 def rcnn_postprocess(rois, rcnn_reg, rcnn_cls, anchor_size, loc_scope, loc_bin_size, num_head_bin, y_by_bin,
                      loc_y_scope, loc_y_bin_size, score_thresh, nms_thresh, pred_boxes3d, boxes, scores, num):
-    """Fused final stage (csrc/proposal.hip): decode against the RoIs, score threshold, rotated NMS.
+    """Fused final stage (csrc/final_stage.hip): decode against the RoIs, score threshold, rotated NMS.
     rois (B,M,7), rcnn_reg (B,M,C), rcnn_cls (B,M) -> pred_boxes3d (B,M,7), boxes (B,M,7), scores (B,M), num (B) i32."""
     import ctypes
     _chk(rois, rcnn_reg, rcnn_cls, pred_boxes3d, boxes, scores)

@@ -446,13 +446,14 @@ def test_engine_keeps_no_state_from_one_batch_to_the_next():
     assert not torch.equal(got["rcnn_reg"], E.infer_batch(model, cfg, a, engine=used)["rcnn_reg"])
 
 
-@pytest.mark.parametrize("N", [4096, 16384, 10000, 5000])
+@pytest.mark.parametrize("N", [4096, 16384, 10000, 5000, 1000, 40000])
 def test_fused_proposal_sort_order_with_ties_and_nans(ext, N):
     """The score sort's total order = (score descending, NaN first, index ascending on ties) == torch's STABLE descending
     sort; argmax over regression bins treats NaN as the largest value like torch.argmax.  Exercised through the fused
     proposal entry with every point in the near band and NMS threshold 1 (nothing suppressed): the RoIs come out in
     exactly that order.  N = 4096: one workgroup per scene (score_sort_kernel); larger N: 4096-key chunks sorted by a
-    workgroup each + merge-path rounds (round 3), incl. sizes that are not a power of two (pad keys in the last chunks)."""
+    workgroup each + merge-path rounds (round 3), incl. sizes that are not a power of two (pad keys in the last chunks).
+    N = 1000: npad 1024, one workgroup far below a full chunk; N = 40000: npad 65536, four merge rounds, whole chunks of pad keys."""
     rng = np.random.default_rng(3)
     B = 2
     xyz = torch.from_numpy(rng.uniform([-30, 0, 5], [30, 2, 35], (B, N, 3)).astype(np.float32)).to(DEV)
@@ -477,6 +478,48 @@ def test_fused_proposal_sort_order_with_ties_and_nans(ext, N):
         assert torch.equal(torch.isnan(got), torch.isnan(want))
         assert torch.equal(got[~torch.isnan(got)], want[~torch.isnan(want)])
         assert bool(torch.isnan(got[0]))                                # the NaN scores lead
+
+
+def test_final_stage_four_launch_form_keeps_the_best_selected_box(ext):
+    """prcnn_rcnn_postprocess with nms_thresh < 0 runs the four-launch form (decode + select, dense NMS, gather; the one-workgroup
+    kernel's candidate filter would answer differently there).  Every IoU is >= 0 > threshold, so the best selected box of a scene
+    suppresses every other one: num is 1 where any RoI passes the score threshold, slot 0 holds that RoI's decoded box and raw
+    score, everything behind is zero; and pred_boxes3d is, bit for bit, the one-workgroup kernel's (the same decode)."""
+    from helpers import boxes3d
+    cfg = pkg("config").default_eval_cfg()
+    R = cfg.RCNN
+    rng = np.random.default_rng(52)
+    B = 3
+    logit = float(np.log(R.SCORE_THRESH / (1.0 - R.SCORE_THRESH)))
+    for M in (37, 100, 128):
+        rois = torch.from_numpy(np.stack([boxes3d(rng, M) for _ in range(B)])).to(DEV)
+        reg = torch.from_numpy((rng.standard_normal((B, M, 46)) * 0.3).astype(np.float32)).to(DEV)
+        raw = (rng.standard_normal((B, M)) * 2).astype(np.float32)
+        raw[1] = -5.0 - rng.uniform(0, 1, M).astype(np.float32)            # scene 1: nothing above the score threshold
+        raw[np.abs(raw - logit) < 0.05] += 0.2                              # no score at the threshold itself
+        assert all(len(np.unique(raw[b])) == M for b in range(B))
+        cls = torch.from_numpy(raw).to(DEV)
+        out = {}
+        for thresh in (-1.0, R.NMS_THRESH):
+            pred = torch.full((B, M, 7), float("nan"), device=DEV)
+            boxes = torch.full((B, M, 7), float("nan"), device=DEV); scores = torch.full((B, M), float("nan"), device=DEV)
+            num = torch.full((B,), -9, dtype=torch.int32, device=DEV)
+            ext.iou3d.rcnn_postprocess(rois, reg, cls, [float(v) for v in np.asarray(cfg.CLS_MEAN_SIZE[0], dtype=np.float32)], R.LOC_SCOPE,
+                                       R.LOC_BIN_SIZE, R.NUM_HEAD_BIN, R.LOC_Y_BY_BIN, R.LOC_Y_SCOPE, R.LOC_Y_BIN_SIZE, R.SCORE_THRESH,
+                                       thresh, pred, boxes, scores, num)
+            out[thresh] = (pred, boxes, scores, num)
+        pred, boxes, scores, num = out[-1.0]
+        assert torch.equal(pred, out[R.NMS_THRESH][0])
+        sel = 1.0 / (1.0 + np.exp(-raw.astype(np.float64))) > R.SCORE_THRESH
+        assert sel[0].any() and sel[2].any() and not sel[1].any()
+        for b in range(B):
+            if not sel[b].any():
+                assert int(num[b]) == 0 and (boxes[b] == 0).all() and (scores[b] == 0).all()
+                continue
+            best = int(np.argmax(np.where(sel[b], raw[b], -np.inf)))
+            assert int(num[b]) == 1
+            assert torch.equal(boxes[b, 0], pred[b, best]) and float(scores[b, 0]) == float(raw[b, best])
+            assert (boxes[b, 1:] == 0).all() and (scores[b, 1:] == 0).all()
 
 
 def test_postprocess_batched_equals_per_scene_reference_order():
@@ -507,7 +550,7 @@ def test_postprocess_batched_equals_per_scene_reference_order():
 
 
 def test_fused_proposal_layer_equals_batched_torch_path():
-    """csrc/proposal.hip (decode + LDS sort + band selection + NMS + assembly) vs the batched torch-op
+    """csrc/proposal.hip (decode + score sort + band selection + NMS + assembly) vs the batched torch-op
     formulation of net/proposal_layer.py (itself checked against the reference's per-scene loop in
     tests/test_host_logic.py), incl. a scene with no far points and one with fewer near points than
     the quota."""

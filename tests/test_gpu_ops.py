@@ -484,11 +484,32 @@ def test_nms_device_batched_prefix(ext, oracle, K, thresh, spread):
         assert (keep[p, num[p]:] == -1).all()
 
 
+def test_nms_device_axis_aligned_beyond_the_quota_forms(ext, oracle):
+    """max_keep > 512 with more than 128 boxes: the axis-aligned general kernel (nms_lazy_kernel<false>; every smaller quota goes
+    to the quota form) == the first K entries of the oracle's greedy list.  Ragged counts; problem 0 is sparse and reaches the
+    quota (the early stop), problem 1 is dense and keeps fewer than half of it."""
+    rng = np.random.default_rng(21)
+    P, nmax, K, thresh = 4, 700, 600, 0.3
+    counts = np.array([700, 699, 130, 0], np.int32)
+    boxes = np.stack([bev_boxes(rng, nmax, spread=s, rotated=False) for s in (60.0, 10.0, 4.0, 20.0)], 0)
+    full = [oracle.nms_normal(boxes[p, :counts[p]], thresh) for p in range(P)]
+    assert len(full[0]) >= K and len(full[1]) < K // 2
+    keep = torch.empty((P, K), dtype=torch.int32, device=DEV)
+    num = torch.empty((P,), dtype=torch.int32, device=DEV)
+    ext.iou3d.nms_device(T(boxes), T(counts), thresh, False, K, keep, num)
+    keep, num = keep.cpu().numpy(), num.cpu().numpy()
+    for p in range(P):
+        want = full[p][:K]
+        assert num[p] == len(want)
+        assert np.array_equal(keep[p, :num[p]], want)
+        assert (keep[p, num[p]:] == -1).all()
+
+
 @pytest.mark.parametrize("rotated", [True, False])
 @pytest.mark.parametrize("nmax,K,thresh,spread", [(100, 100, 0.1, 6.0), (128, 128, 0.1, 3.0), (128, 40, 0.3, 2.0), (65, 65, 0.01, 4.0), (7, 7, 0.1, 1.0)])
 def test_nms_device_small_problems_dense_form(ext, oracle, nmax, K, thresh, spread, rotated):
     """n <= 128 (the final rotated NMS of a scene: <= 100 boxes, threshold 0.1): the all-pairs mask + one-wave resolve of
-    csrc/iou3d.hip (round 3) against the oracle's greedy loop, ragged counts (incl. 0 and 1), a keep quota below the answer,
+    csrc/nms_device.hip (round 3) against the oracle's greedy loop, ragged counts (incl. 0 and 1), a keep quota below the answer,
     boxes packed so tightly that most are suppressed by a box kept long before them."""
     rng = np.random.default_rng(nmax + K)
     P = 9

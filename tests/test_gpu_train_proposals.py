@@ -1,5 +1,5 @@
 """-m gpu: the proposal layer at the TRAINING quotas (csrc/proposal.hip with RPN_POST_NMS_TOP_N up to 512: 358 near + 154 far) and the
-axis-aligned quota NMS with the 512-row kept-box table (csrc/iou3d.hip nms_quota_kernel<512>, max_keep 257..512).
+axis-aligned quota NMS with the 512-row kept-box table (csrc/nms_device.hip nms_quota_kernel<512>, max_keep 257..512).
 
 Every comparison is exact (torch.equal / array_equal): the fused layer states the batched torch formulation operation for operation,
 and a keep list is a list of decisions.  Before the quotas were lifted everything above 128 raised "rpn_proposals: unsupported quotas"."""
