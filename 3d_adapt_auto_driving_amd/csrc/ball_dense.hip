@@ -9,7 +9,7 @@
 //
 // Here the same hashed cells are stored CONTIGUOUSLY (a counting sort by bucket inside one workgroup per cloud: LDS
 // histogram, scan, scatter of 16-byte (x, y, z, index) records; round 4: with the cloud in the workgroup's registers, see
-// dense_build_reg_kernel) and a WAVE serves one centre:
+// dense_build_kernel's register source) and a WAVE serves one centre:
 //   * lanes 0..8 fetch the nine bucket ranges (duplicate buckets -- two cells hashing alike -- are visited once);
 //   * the candidates are read 64 at a time, coalesced, tested with the reference's f32 expression (sqdist3), and
 //   * the wave keeps the nsample SMALLEST hit indices sorted across its lanes (lane i = i-th smallest; an insertion is one
@@ -20,141 +20,52 @@
 //     nsample-th smallest, the rest of the range cannot contribute and is skipped -- in a full ball most of every range.
 // Same results as the index-order scan bit for bit (tests/test_gpu_ops.py: all BASELINE configs[1] pairs on uniform, LiDAR-
 // shaped and duplicate-point clouds; shadowed at batch 8 in tests/test_gpu_shadow.py).
-#include "common.hpp"
-#include <math.h>
+#include "cell_sort.hpp"
 
 namespace prcnn {
 
-__device__ __forceinline__ unsigned dcell_hash(int ix, int iz, unsigned mask)
-{
-    return (((unsigned)ix * 73856093u) ^ ((unsigned)iz * 19349663u)) & mask;
-}
-
-__device__ __forceinline__ int dcell_coord(float v, double inv_s)
-{
-    double c = floor((double)v * inv_s);
-    c = fmin(fmax(c, -1.0e9), 1.0e9);
-    return (int)c;
-}
-
 constexpr int DB = 1024;        // build workgroup: one per cloud
 
-// GENERIC build (16384 < n <= 65535; the fast one follows).  range[b][0..H): (first record, length) of every bucket;
-// sorted[b][n]: (x, y, z, index) by bucket, by chunk inside
+// The build.  range[b][0..H): (first record, length) of every bucket; sorted[b][n]: (x, y, z, index) by bucket, by chunk inside.
+// Source (cell_sort.hpp) says where the cloud is:
+//   GlobalPoints (16384 < n <= 65535): every pass re-reads the points from global memory; a point's rank inside its bucket is kept in
+//   rank[b][n] (u16, scratch); a chunk is `chunk` indices (16 chunks per cloud).
+//   RegPoints<PPT> (n <= 16384, every level of the RPN backbone): the cloud lives in REGISTERS (thread t holds points t, t + 1024, ...),
+//   bucket << 16 | rank (rank < 16384, bucket < 32768) in the point's memo, so the rank-assignment rounds are LDS atomics + barriers only
+//   (from global memory they are 16 dependent round trips + 16 more in the scatter = most of the ~50 us the build then takes for
+//   8 clouds, measured as "B = 1, C = 0: 79 us per call" in profiles/r04_query_and_group_sweep.md).  A chunk is one round = 1024
+//   consecutive indices (chunk_shift 10).  The bucket ranges are laid out in the order (thread, slice) -- thread t owns buckets t,
+//   t + 1024, ... -- so that the scan reads LDS conflict-free; the query reads a bucket's (start, length) pair, the layout order is free.
+template <class Source>
 __global__ __launch_bounds__(DB) void dense_build_kernel(int n, unsigned mask, double inv_s, int chunk,
                                                          const float *__restrict__ xyz, int2 *__restrict__ range,
                                                          float4 *__restrict__ sorted, unsigned short *__restrict__ rank)
 {
     extern __shared__ int cnt[];               // H counters, then the buckets' start offsets
     __shared__ int wsum[DB / 64];
-    const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
-    const int H = (int)mask + 1;
-    const float *__restrict__ pts = xyz + (long)b * n * 3;
+    const int b = blockIdx.x, t = threadIdx.x;
+    const int H = (int)mask + 1;               // a power of two >= 2048
     unsigned short *__restrict__ rk = rank + (long)b * n;
-    for (int c = t; c < H; c += DB) cnt[c] = 0;
-    __syncthreads();
-    // slots inside a bucket are handed out chunk by chunk in index order: a bucket's records end up sorted by chunk
-    for (int base = 0; base < n; base += chunk) {
-        const int hi = min(base + chunk, n);
-        for (int k = base + t; k < hi; k += DB) {
-            const unsigned key = dcell_hash(dcell_coord(pts[3 * k], inv_s), dcell_coord(pts[3 * k + 2], inv_s), mask);
-            rk[k] = (unsigned short)atomicAdd(&cnt[key], 1);
-        }
-        __syncthreads();
-    }
-    // exclusive scan of the H counts; thread t owns `per` consecutive buckets
-    const int per = H / DB;                    // H is a power of two >= 2048
-    const int lo = t * per;
-    int sum = 0;
-    for (int c = lo; c < lo + per; ++c) sum += cnt[c];
-    int incl = sum;
-    for (int off = 1; off < 64; off <<= 1) {
-        const int v = __shfl_up(incl, off);
-        if (lane >= off) incl += v;
-    }
-    if (lane == 63) wsum[w] = incl;
-    __syncthreads();
-    int run = incl - sum;
-    for (int i = 0; i < w; ++i) run += wsum[i];
-    int2 *__restrict__ st = range + (long)b * H;
-    for (int c = lo; c < lo + per; ++c) {
-        const int v = cnt[c];
-        cnt[c] = run;
-        st[c] = make_int2(run, v);
-        run += v;
-    }
-    __syncthreads();
-    float4 *__restrict__ so = sorted + (long)b * n;
-    for (int k = t; k < n; k += DB) {
-        const float x = pts[3 * k], y = pts[3 * k + 1], z = pts[3 * k + 2];
-        const unsigned key = dcell_hash(dcell_coord(x, inv_s), dcell_coord(z, inv_s), mask);
-        so[cnt[key] + (int)rk[k]] = make_float4(x, y, z, __int_as_float(k));
-    }
-}
-
-
-// FAST build, n <= 16384 (every level of the RPN backbone): the cloud lives in REGISTERS (thread t holds points t, t + 1024, ...),
-// so the 16 rank-assignment rounds are LDS atomics + barriers only (the generic kernel re-reads the points from global memory in
-// every round: 16 dependent global round trips + 16 more in the scatter = most of the ~50 us it takes for 8 clouds, measured as
-// "B = 1, C = 0: 79 us per call" in profiles/r04_query_and_group_sweep.md).  A chunk is one round = 1024 consecutive indices
-// (chunk_shift 10).  The bucket ranges are laid out in the order (thread, slice) -- thread t owns buckets t, t + 1024, ... --
-// so that the scan reads LDS conflict-free; the query reads a bucket's (start, length) pair, the layout order is free.
-template <int PPT>
-__global__ __launch_bounds__(DB) void dense_build_reg_kernel(int n, unsigned mask, double inv_s, const float *__restrict__ xyz,
-                                                             int2 *__restrict__ range, float4 *__restrict__ sorted)
-{
-    extern __shared__ int cnt[];               // H counters, then the buckets' start offsets
-    __shared__ int wsum[DB / 64];
-    const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
-    const int H = (int)mask + 1;
-    const float *__restrict__ pts = xyz + (long)b * n * 3;
-    float px[PPT], py[PPT], pz[PPT];
-#pragma unroll
-    for (int j = 0; j < PPT; ++j) {
-        const int k = j * DB + t;
-        px[j] = py[j] = pz[j] = 0.f;
-        if (k < n) { px[j] = pts[3 * k]; py[j] = pts[3 * k + 1]; pz[j] = pts[3 * k + 2]; }
-    }
+    Source src;
+    src.load(xyz + (long)b * n * 3, n);
     int4 *cnt4 = reinterpret_cast<int4 *>(cnt);
     for (int c = t; c < H / 4; c += DB) cnt4[c] = make_int4(0, 0, 0, 0);
-    int kr[PPT];                               // bucket << 16 | rank inside the bucket (rank < 16384, bucket < 32768)
-#pragma unroll
-    for (int j = 0; j < PPT; ++j)
-        kr[j] = (int)(dcell_hash(dcell_coord(px[j], inv_s), dcell_coord(pz[j], inv_s), mask) << 16);
+    auto key_of = [&](float x, float z) { return cell_hash(cell_coord(x, inv_s), cell_coord(z, inv_s), mask); };
+    src.note([&](float x, float z) { return (int)(key_of(x, z) << 16); });
     __syncthreads();
-#pragma unroll
-    for (int j = 0; j < PPT; ++j) {            // round j = index chunk j: a bucket's records end up sorted by chunk
-        if (j * DB + t < n) kr[j] |= atomicAdd(&cnt[(unsigned)kr[j] >> 16], 1);
-        if ((j + 1) * DB < n + DB) __syncthreads();
-    }
-    // exclusive scan of the H counts in the order (thread, slice): thread t owns buckets t + 1024 i
-    const int per = H / DB;                    // H is a power of two >= 2048
-    int sum = 0;
-    for (int i = 0; i < per; ++i) sum += cnt[i * DB + t];
-    int incl = sum;
-    for (int off = 1; off < 64; off <<= 1) {
-        const int v = __shfl_up(incl, off);
-        if (lane >= off) incl += v;
-    }
-    if (lane == 63) wsum[w] = incl;
-    __syncthreads();
-    int run = incl - sum;
-    for (int i = 0; i < w; ++i) run += wsum[i];
+    // slots inside a bucket are handed out chunk by chunk in index order: a bucket's records end up sorted by chunk
+    src.each_chunk(chunk, [&](int k, float x, float, float z, int &memo) {
+        if (Source::REG) memo |= atomicAdd(&cnt[(unsigned)memo >> 16], 1);
+        else rk[k] = (unsigned short)atomicAdd(&cnt[key_of(x, z)], 1);
+    });
     int2 *__restrict__ st = range + (long)b * H;
-    for (int i = 0; i < per; ++i) {
-        const int c = i * DB + t;
-        const int v = cnt[c];
-        cnt[c] = run;
-        st[c] = make_int2(run, v);
-        run += v;
-    }
+    cell_scan<DB, Source::REG>(cnt, H, H / DB, wsum, false, [&](int c, int start, int count) { st[c] = make_int2(start, count); });
     __syncthreads();
     float4 *__restrict__ so = sorted + (long)b * n;
-#pragma unroll
-    for (int j = 0; j < PPT; ++j) {
-        const int k = j * DB + t;
-        if (k < n) so[cnt[(unsigned)kr[j] >> 16] + (kr[j] & 0xffff)] = make_float4(px[j], py[j], pz[j], __int_as_float(k));
-    }
+    src.each([&](int k, float x, float y, float z, int &memo) {
+        const int at = Source::REG ? cnt[(unsigned)memo >> 16] + (memo & 0xffff) : cnt[key_of(x, z)] + (int)rk[k];
+        so[at] = make_float4(x, y, z, __int_as_float(k));
+    });
 }
 
 constexpr int DQ_WAVES = 4;     // centres per query workgroup (one wave each)
@@ -176,14 +87,14 @@ __global__ __launch_bounds__(64 * DQ_WAVES) void dense_query_kernel(
     if (p >= m) return;
     const float *c = new_xyz + ((long)b * m + p) * 3;
     const float cx = c[0], cy = c[1], cz = c[2];
-    const int ix = dcell_coord(cx, inv_s), iz = dcell_coord(cz, inv_s);
+    const int ix = cell_coord(cx, inv_s), iz = cell_coord(cz, inv_s);
     const int2 *__restrict__ st = range + (long)b * (mask + 1);
     const float4 *__restrict__ so = sorted + (long)b * n;
 
     // lanes 0..8: the nine buckets of the 3 x 3 cell neighbourhood, own cell first; a bucket reached twice is read once
     const int q = lane < 9 ? lane : 0;
     const int order = q == 0 ? 4 : (q <= 4 ? q - 1 : q);               // 4, 0, 1, 2, 3, 5, 6, 7, 8
-    const unsigned key = dcell_hash(ix + order / 3 - 1, iz + order % 3 - 1, mask);
+    const unsigned key = cell_hash(ix + order / 3 - 1, iz + order % 3 - 1, mask);
     bool dup = lane >= 9;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
@@ -261,8 +172,6 @@ __global__ __launch_bounds__(64 * DQ_WAVES) void dense_query_kernel(
     if (lane < nsample) out[lane] = lane < cnt ? best : lowest;
 }
 
-static size_t dalign(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // Returns PRCNN_OK, or an error; *used = 0 when this path declines (the caller falls back).
 int ball_query_dense(int b, int n, int m, float radius, int nsample, const float *new_xyz, const float *xyz,
                      int *idx, int write_empty, hipStream_t st, int *used)
@@ -275,29 +184,24 @@ int ball_query_dense(int b, int n, int m, float radius, int nsample, const float
     int chunk_shift = fast ? 10 : 6;                                     // fast: a chunk = a round of 1024 indices; generic: 16 chunks
     while (!fast && (1 << chunk_shift) * 16 < n) ++chunk_shift;
     const int chunk = 1 << chunk_shift;
-    const size_t o_range = 0;
-    const size_t o_sorted = dalign((size_t)b * H * sizeof(int2));
-    const size_t o_rank = o_sorted + dalign((size_t)b * n * sizeof(float4));
-    const size_t need = o_rank + (fast ? 0 : dalign((size_t)b * n * sizeof(unsigned short)));
-    char *base = scratch_for(st, need, 9);
-    if (!base) { set_error("ball_query: cannot allocate %zu bytes of grid scratch", need); return PRCNN_ELAUNCH; }
+    ScratchPlan plan;
+    const size_t o_range = plan.take((size_t)b * H * sizeof(int2));
+    const size_t o_sorted = plan.take((size_t)b * n * sizeof(float4));
+    const size_t o_rank = plan.take(fast ? 0 : (size_t)b * n * sizeof(unsigned short));
+    char *base = scratch_for(st, plan.need, 9);
+    if (!base) { set_error("ball_query: cannot allocate %zu bytes of grid scratch", plan.need); return PRCNN_ELAUNCH; }
     int2 *range = (int2 *)(base + o_range);
     float4 *sorted = (float4 *)(base + o_sorted);
     unsigned short *rank = (unsigned short *)(base + o_rank);
     const double inv_s = 1.0 / ((double)radius * 1.001);
     const size_t lds = (size_t)H * sizeof(int);
-    const void *build = fast ? (n <= 4 * DB ? (const void *)dense_build_reg_kernel<4> : (const void *)dense_build_reg_kernel<16>)
-                             : (const void *)dense_build_kernel;
+    auto *build = !fast ? dense_build_kernel<GlobalPoints<DB>>
+                        : (n <= 4 * DB ? dense_build_kernel<RegPoints<DB, 4>> : dense_build_kernel<RegPoints<DB, 16>>);
     if (lds > 48 * 1024) {
-        const int rc = ensure_dynamic_lds(build, lds, "ball_query(dense build)");
+        const int rc = ensure_dynamic_lds((const void *)build, lds, "ball_query(dense build)");
         if (rc != PRCNN_OK) return rc;
     }
-    if (!fast)
-        hipLaunchKernelGGL(dense_build_kernel, dim3(b), dim3(DB), lds, st, n, H - 1, inv_s, chunk, xyz, range, sorted, rank);
-    else if (n <= 4 * DB)
-        hipLaunchKernelGGL(dense_build_reg_kernel<4>, dim3(b), dim3(DB), lds, st, n, H - 1, inv_s, xyz, range, sorted);
-    else
-        hipLaunchKernelGGL(dense_build_reg_kernel<16>, dim3(b), dim3(DB), lds, st, n, H - 1, inv_s, xyz, range, sorted);
+    hipLaunchKernelGGL(build, dim3(b), dim3(DB), lds, st, n, H - 1, inv_s, chunk, xyz, range, sorted, rank);
     hipLaunchKernelGGL(dense_query_kernel, dim3(ceil_div(m, DQ_WAVES), b), dim3(64 * DQ_WAVES), 0, st, n, m, H - 1, inv_s,
                        radius * radius, nsample, chunk_shift, new_xyz, range, sorted, idx, write_empty);
     *used = 1;

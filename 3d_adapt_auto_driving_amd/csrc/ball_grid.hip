@@ -16,22 +16,9 @@
 // Cell coordinates are computed in f64 and the cell edge carries a 0.1 % margin, so a point with
 // d^2 < r^2 can never fall outside the 3x3 neighbourhood through rounding.  Hash collisions only add
 // candidates; a bucket reached through two neighbour cells is visited once.
-#include "common.hpp"
-#include <math.h>
+#include "cell_sort.hpp"
 
 namespace prcnn {
-
-__device__ __forceinline__ unsigned cell_hash(int ix, int iz, unsigned mask)
-{
-    return (((unsigned)ix * 73856093u) ^ ((unsigned)iz * 19349663u)) & mask;
-}
-
-__device__ __forceinline__ int cell_coord(float v, double inv_s)
-{
-    double c = floor((double)v * inv_s);
-    c = fmin(fmax(c, -1.0e9), 1.0e9);
-    return (int)c;
-}
 
 // head[b][bucket] = index of the most recently inserted point (-1 = empty, set by the memset 0xFF)
 __global__ __launch_bounds__(256) void grid_link_kernel(int n, unsigned mask, double inv_s,
@@ -106,8 +93,6 @@ __global__ __launch_bounds__(QT) void grid_query_kernel(
     for (int l = 0; l < nsample; ++l) out[l] = l < cnt ? mine[l * QT] : lowest;
 }
 
-static size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // Returns PRCNN_OK, or an error; *used = 0 when the grid path declines (caller falls back).
 int ball_query_grid(int b, int n, int m, float radius, int nsample, const float *new_xyz, const float *xyz,
                     int *idx, int write_empty, hipStream_t st, int *used)
@@ -116,11 +101,11 @@ int ball_query_grid(int b, int n, int m, float radius, int nsample, const float 
     if (!(radius > 0.f) || !isfinite(radius) || n < 4096 || m < 64 || nsample > 128 || b > 65535) return PRCNN_OK;
     unsigned H = 1;
     while (H < 2u * (unsigned)n) H <<= 1;
-    const size_t o_head = 0;
-    const size_t o_node = align_up((size_t)b * H * sizeof(int));
-    const size_t need = o_node + align_up((size_t)b * n * sizeof(float4));
-    char *base = scratch_for(st, need);
-    if (!base) { set_error("ball_query: cannot allocate %zu bytes of grid scratch", need); return PRCNN_ELAUNCH; }
+    ScratchPlan plan;
+    const size_t o_head = plan.take((size_t)b * H * sizeof(int));
+    const size_t o_node = plan.take((size_t)b * n * sizeof(float4));
+    char *base = scratch_for(st, plan.need);
+    if (!base) { set_error("ball_query: cannot allocate %zu bytes of grid scratch", plan.need); return PRCNN_ELAUNCH; }
     int *head = (int *)(base + o_head);
     float4 *node = (float4 *)(base + o_node);
 

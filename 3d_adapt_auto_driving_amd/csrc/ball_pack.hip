@@ -277,12 +277,7 @@ __global__ __launch_bounds__(256) void ball_pack_write_kernel(int n, int m, int 
     // exclusive offsets of this chunk's centres (one wave)
     if (tid < 64) {
         const int v = tid < nc ? cnts[(long)gb * m + c0 + tid] : 0;
-        int incl = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int o = __shfl_up(incl, d, 64);
-            if (tid >= d) incl += o;
-        }
+        const int incl = wave_incl_scan(v, tid);
         s_off[tid] = incl - v;
         if (tid == 63) s_off[PK_CH] = incl;
     }

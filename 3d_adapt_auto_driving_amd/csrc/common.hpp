@@ -202,4 +202,15 @@ __device__ __forceinline__ float4 affine_relu4(const float4 base, const float4 w
 
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
 
+// inclusive scan of v across the wave: lane l gets the sum of lanes 0 .. l
+__device__ __forceinline__ int wave_incl_scan(int v, const int lane)
+{
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int o = __shfl_up(v, d, 64);
+        if (lane >= d) v += o;
+    }
+    return v;
+}
+
 }  // namespace prcnn

@@ -13,6 +13,7 @@
 // Here: the register-resident kernels, the Morton ordering, the any-n fallback and the dispatch.  The speculative kernels of large
 // clouds are in fps_spec.hip, the nested-sampling check in fps_prefix.hip, what they all share in fps_common.hpp.
 #include "fps_common.hpp"
+#include "cell_sort.hpp"
 
 namespace prcnn {
 
@@ -159,51 +160,25 @@ __global__ __launch_bounds__(1024) void fps_order_kernel(int n, const float *__r
     __shared__ int wsum[16];
     const int b = blockIdx.x, t = threadIdx.x;
     if (rejected && rejected[b] == 0) return;                         // (fps_reg_kernel: the cloud's sampling is skipped, nobody reads its order)
-    const float *__restrict__ cloud = xyz + (long)b * n * 3;
-    float x0 = INFINITY, x1 = -INFINITY, z0 = INFINITY, z1 = -INFINITY;
-    for (int k = t; k < n; k += 1024) {
-        const float x = cloud[3 * k], z = cloud[3 * k + 2];
-        x0 = fminf(x0, x); x1 = fmaxf(x1, x); z0 = fminf(z0, z); z1 = fmaxf(z1, z);
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        x0 = fminf(x0, __shfl_xor(x0, d, 64)); x1 = fmaxf(x1, __shfl_xor(x1, d, 64));
-        z0 = fminf(z0, __shfl_xor(z0, d, 64)); z1 = fmaxf(z1, __shfl_xor(z1, d, 64));
-    }
-    if ((t & 63) == 0) { red[0][t >> 6] = x0; red[1][t >> 6] = x1; red[2][t >> 6] = z0; red[3][t >> 6] = z1; }
+    GlobalPoints<1024> cloud;
+    cloud.load(xyz + (long)b * n * 3, n);
+    RectXZ r;
+    cloud.each([&](int, float x, float, float z, int &) { r.add(x, z); });
+    rect_wave_reduce<1024>(r, red);
     for (int i = t; i < 4096; i += 1024) cnt[i] = 0;
     __syncthreads();
-    x0 = red[0][0]; x1 = red[1][0]; z0 = red[2][0]; z1 = red[3][0];
-    for (int w = 1; w < 16; ++w) {
-        x0 = fminf(x0, red[0][w]); x1 = fmaxf(x1, red[1][w]); z0 = fminf(z0, red[2][w]); z1 = fmaxf(z1, red[3][w]);
-    }
-    const float sx = x1 > x0 ? 64.f / (x1 - x0) : 0.f, sz = z1 > z0 ? 64.f / (z1 - z0) : 0.f;
-    auto code_of = [&](int k) {
-        float fx = (cloud[3 * k] - x0) * sx, fz = (cloud[3 * k + 2] - z0) * sz;
+    r = rect_total<1024>(red);
+    const float x0 = r.x0, z0 = r.z0;
+    const float sx = r.x1 > x0 ? 64.f / (r.x1 - x0) : 0.f, sz = r.z1 > z0 ? 64.f / (r.z1 - z0) : 0.f;
+    auto code_of = [&](float x, float z) {
+        float fx = (x - x0) * sx, fz = (z - z0) * sz;
         fx = fx == fx ? fx : 0.f; fz = fz == fz ? fz : 0.f;            // NaN-safe
         const int cx = min(63, max(0, (int)fx)), cz = min(63, max(0, (int)fz));
         return (int)(part1by1((unsigned)cx) | (part1by1((unsigned)cz) << 1));
     };
-    for (int k = t; k < n; k += 1024) atomicAdd(&cnt[code_of(k)], 1);
-    __syncthreads();
-    // exclusive scan of the 4096 counters: 4 per thread
-    int local = 0, c4[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { c4[i] = cnt[4 * t + i]; local += c4[i]; }
-    int incl = local;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(incl, d, 64);
-        if ((t & 63) >= d) incl += o;
-    }
-    if ((t & 63) == 63) wsum[t >> 6] = incl;
-    __syncthreads();
-    int run = incl - local;
-    for (int w = 0; w < (t >> 6); ++w) run += wsum[w];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { cnt[4 * t + i] = run; run += c4[i]; }
-    __syncthreads();
-    for (int k = t; k < n; k += 1024) perm[(long)b * n + atomicAdd(&cnt[code_of(k)], 1)] = k;
+    // 4096 counters, four per thread
+    cell_sort<1024>(cloud, cnt, 4096, 4, wsum, false, code_of, [](int, int, int) {},
+                    [&](int pos, int k, float, float, float) { perm[(long)b * n + pos] = k; });
 }
 
 // Any-n fallback: running minima stay in `temp` (global), one 1024-thread block per cloud.

@@ -208,16 +208,6 @@ struct RgPacks {
     // tilecloud): no padded last tile per cloud
 };
 
-__device__ __forceinline__ int wave_incl_scan(int v, const int lane)
-{
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(v, d, 64);
-        if (lane >= d) v += o;
-    }
-    return v;
-}
-
 // One cloud's list: centre c (c = lane: keep_lo / tot_lo, c = lane + 64: keep_hi / tot_hi; M centres) lists keep[c] rows -- 0 for a
 // centre that copies an earlier one, else max(hits, 1) -- row p of it = hit p of its staged list (point 0 of an empty ball), in centre
 // order, cut into 64-row tiles drawn from the list's counter; the last tile is filled with copies of centre M - 1's first row (as

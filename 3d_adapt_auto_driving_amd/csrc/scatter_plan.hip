@@ -56,7 +56,7 @@ __global__ __launch_bounds__(256) void sp_scan_kernel(int n, int *__restrict__ c
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = k0 + e < n ? c[k0 + e] : 0;
         const int sum = v[0] + v[1] + v[2] + v[3];
-        int inc = sum;
+        int inc = sum;                           // wave_incl_scan (common.hpp) as text: through the call the kernel's setup is scheduled differently
 #pragma unroll
         for (int d = 1; d < 64; d <<= 1) {
             const int up = __shfl_up(inc, d);

@@ -41,7 +41,7 @@ __device__ __forceinline__ int tile_exclusive_scan(int *a, int n, int stride, in
     for (int i0 = 0; i0 < n; i0 += THREADS) {
         const int i = i0 + threadIdx.x;
         const int v = i < n ? a[(long)stride * i] : 0;
-        int inc = v;
+        int inc = v;                             // wave_incl_scan (common.hpp) as text: through the call the scan kernels schedule differently
         for (int d = 1; d < WAVE; d <<= 1) { const int o = __shfl_up(inc, d, 64); if (lane >= d) inc += o; }
         __syncthreads();
         if (lane == WAVE - 1) wsum[w] = inc;

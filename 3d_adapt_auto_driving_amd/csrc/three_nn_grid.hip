@@ -25,8 +25,7 @@
 // counting-sorted by cell as well (same workgroup, same histogram memory) and served in that order, so the lanes of a wave sit
 // in the same or neighbouring cells, walk the same ranges and their candidate loads coalesce into one or two cache lines;
 // (3) candidates are fetched four at a time.  Results are written at the query's original position: same bits as before.
-#include "common.hpp"
-#include <math.h>
+#include "cell_sort.hpp"
 #include <stdlib.h>
 
 namespace prcnn {
@@ -47,6 +46,13 @@ __device__ __forceinline__ int grid_coord(float v, double o, double inv_s, int g
     return (int)c;
 }
 
+// The build: the grid of the known points, then both clouds counting-sorted by cell (cell_sort.hpp).  Known / Queries say where
+// the clouds are.  GlobalPoints: the known points are read three times and the queries twice from global memory, each time as a loop
+// of dependent (load -> LDS atomic) rounds.  RegPoints<4> / <16> (round 4; m <= 4 * 1024 known points, n <= 16 * 1024 queries: every
+// FP level of the backbone): every coordinate is loaded once, all loads in flight together, and the rest is LDS and ALU work.  Same
+// cell assignment, same counting sort: the query kernel sees the same tables up to the order of points INSIDE a cell (atomics), which
+// the (d, index) insertion makes irrelevant.
+template <class Known, class Queries>
 __global__ __launch_bounds__(TB) void tnn_build_kernel(int m, int g, const float *__restrict__ known,
                                                        GridParams *__restrict__ params, int *__restrict__ cell_start,
                                                        float4 *__restrict__ sorted, int n, const float *__restrict__ unknown,
@@ -56,251 +62,47 @@ __global__ __launch_bounds__(TB) void tnn_build_kernel(int m, int g, const float
     __shared__ float red[4][TB / 64];
     __shared__ int wsum[TB / 64];
     __shared__ GridParams gp;
-    const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
-    const float *__restrict__ kn = known + (long)b * m * 3;
+    const int b = blockIdx.x, t = threadIdx.x;
     const int cells = g * g;
+    Known kn;
+    kn.load(known + (long)b * m * 3, m);
+    Queries un;
+    un.load(unknown + (long)b * n * 3, n);
 
-    // bounding rectangle of the finite points
-    float xmin = INFINITY, xmax = -INFINITY, zmin = INFINITY, zmax = -INFINITY;
-    for (int k = t; k < m; k += TB) {
-        const float x = kn[3 * k], z = kn[3 * k + 2];
-        if (isfinite(x)) { xmin = fminf(xmin, x); xmax = fmaxf(xmax, x); }
-        if (isfinite(z)) { zmin = fminf(zmin, z); zmax = fmaxf(zmax, z); }
-    }
-    for (int off = 32; off >= 1; off >>= 1) {
-        xmin = fminf(xmin, __shfl_xor(xmin, off)); xmax = fmaxf(xmax, __shfl_xor(xmax, off));
-        zmin = fminf(zmin, __shfl_xor(zmin, off)); zmax = fmaxf(zmax, __shfl_xor(zmax, off));
-    }
-    if (lane == 0) { red[0][w] = xmin; red[1][w] = xmax; red[2][w] = zmin; red[3][w] = zmax; }
-    for (int c = t; c < cells; c += TB) hist[c] = 0;
-    __syncthreads();
-    if (t == 0) {
-        for (int i = 1; i < TB / 64; ++i) {
-            xmin = fminf(xmin, red[0][i]); xmax = fmaxf(xmax, red[1][i]);
-            zmin = fminf(zmin, red[2][i]); zmax = fmaxf(zmax, red[3][i]);
-        }
-        if (!(xmin <= xmax)) { xmin = 0.f; xmax = 0.f; }
-        if (!(zmin <= zmax)) { zmin = 0.f; zmax = 0.f; }
-        double ext = fmax((double)xmax - (double)xmin, (double)zmax - (double)zmin);
-        if (!(ext > 1e-6)) ext = 1e-6;
-        const double s = ext / g * (1.0 + 1e-9);
-        gp.x0 = xmin; gp.z0 = zmin; gp.inv_s = 1.0 / s; gp.s = (float)s; gp.g = g;
-        params[b] = gp;
-    }
-    __syncthreads();
-    const double x0 = gp.x0, z0 = gp.z0, inv_s = gp.inv_s;
-
-    for (int k = t; k < m; k += TB) {
-        const int c = grid_coord(kn[3 * k + 2], z0, inv_s, g) * g + grid_coord(kn[3 * k], x0, inv_s, g);
-        atomicAdd(&hist[c], 1);
-    }
-    __syncthreads();
-
-    // exclusive scan of the cell counts: each thread owns a contiguous chunk
-    const int per = (cells + TB - 1) / TB;
-    const int lo = t * per, hi = min(lo + per, cells);
-    int sum = 0;
-    for (int c = lo; c < hi; ++c) sum += hist[c];
-    int incl = sum;
-    for (int off = 1; off < 64; off <<= 1) {
-        const int v = __shfl_up(incl, off);
-        if (lane >= off) incl += v;
-    }
-    if (lane == 63) wsum[w] = incl;
-    __syncthreads();
-    int base = incl - sum;
-    for (int i = 0; i < w; ++i) base += wsum[i];
-    int *__restrict__ cs = cell_start + (long)b * (TG_MAX * TG_MAX + 1);
-    for (int c = lo; c < hi; ++c) {
-        const int cnt = hist[c];
-        cs[c] = base;
-        hist[c] = base;                    // becomes the scatter cursor
-        base += cnt;
-    }
-    if (t == TB - 1) cs[cells] = m;
-    __syncthreads();
-
-    float4 *__restrict__ so = sorted + (long)b * m;
-    for (int k = t; k < m; k += TB) {
-        const float x = kn[3 * k], y = kn[3 * k + 1], z = kn[3 * k + 2];
-        const int c = grid_coord(z, z0, inv_s, g) * g + grid_coord(x, x0, inv_s, g);
-        const int pos = atomicAdd(&hist[c], 1);
-        so[pos] = make_float4(x, y, z, __int_as_float(k));
-    }
-    if (!order) return;
-
-    // the queries, counting-sorted by the cell they fall into (clamped like the ring search clamps them): order[b][0..n)
-    __syncthreads();
-    const float *__restrict__ un = unknown + (long)b * n * 3;
-    for (int c = t; c < cells; c += TB) hist[c] = 0;
-    __syncthreads();
-    for (int k = t; k < n; k += TB) {
-        const int c = grid_coord(un[3 * k + 2], z0, inv_s, g) * g + grid_coord(un[3 * k], x0, inv_s, g);
-        atomicAdd(&hist[c], 1);
-    }
-    __syncthreads();
-    sum = 0;
-    for (int c = lo; c < hi; ++c) sum += hist[c];
-    incl = sum;
-    for (int off = 1; off < 64; off <<= 1) {
-        const int v = __shfl_up(incl, off);
-        if (lane >= off) incl += v;
-    }
-    __syncthreads();                           // wsum is rewritten
-    if (lane == 63) wsum[w] = incl;
-    __syncthreads();
-    base = incl - sum;
-    for (int i = 0; i < w; ++i) base += wsum[i];
-    for (int c = lo; c < hi; ++c) {
-        const int cnt = hist[c];
-        hist[c] = base;
-        base += cnt;
-    }
-    __syncthreads();
-    int *__restrict__ od = order + (long)b * n;
-    for (int k = t; k < n; k += TB) {
-        const int c = grid_coord(un[3 * k + 2], z0, inv_s, g) * g + grid_coord(un[3 * k], x0, inv_s, g);
-        od[atomicAdd(&hist[c], 1)] = k;
-    }
-}
-
-// The same build with both clouds in the workgroup's REGISTERS (round 4; n <= 16 * 1024 queries, m <= 4 * 1024 known points:
-// every FP level of the backbone).  The kernel above reads the known points three times and the queries twice from global memory,
-// each time as a loop of dependent (load -> LDS atomic) rounds; here every coordinate is loaded once, all loads in flight
-// together, and the rest is LDS and ALU work.  Same cell assignment, same counting sort: the query kernel sees the same tables
-// up to the order of points INSIDE a cell (atomics), which the (d, index) insertion makes irrelevant.
-template <int NK, int NQ>
-__global__ __launch_bounds__(TB) void tnn_build_reg_kernel(int m, int g, const float *__restrict__ known,
-                                                           GridParams *__restrict__ params, int *__restrict__ cell_start,
-                                                           float4 *__restrict__ sorted, int n, const float *__restrict__ unknown,
-                                                           int *__restrict__ order)
-{
-    extern __shared__ int hist[];          // g*g counters, then cursors
-    __shared__ float red[4][TB / 64];
-    __shared__ int wsum[TB / 64];
-    __shared__ GridParams gp;
-    const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
-    const float *__restrict__ kn = known + (long)b * m * 3;
-    const float *__restrict__ un = unknown + (long)b * n * 3;
-    const int cells = g * g;
-    float kx[NK], ky[NK], kz[NK], qx[NQ], qz[NQ];
-#pragma unroll
-    for (int j = 0; j < NK; ++j) {
-        const int k = j * TB + t;
-        kx[j] = ky[j] = kz[j] = 0.f;
-        if (k < m) { kx[j] = kn[3 * k]; ky[j] = kn[3 * k + 1]; kz[j] = kn[3 * k + 2]; }
-    }
-    if (order) {
-#pragma unroll
-        for (int j = 0; j < NQ; ++j) {
-            const int k = j * TB + t;
-            qx[j] = qz[j] = 0.f;
-            if (k < n) { qx[j] = un[3 * k]; qz[j] = un[3 * k + 2]; }
-        }
-    }
     // bounding rectangle of the finite known points
-    float xmin = INFINITY, xmax = -INFINITY, zmin = INFINITY, zmax = -INFINITY;
-#pragma unroll
-    for (int j = 0; j < NK; ++j) {
-        if (j * TB + t >= m) continue;
-        if (isfinite(kx[j])) { xmin = fminf(xmin, kx[j]); xmax = fmaxf(xmax, kx[j]); }
-        if (isfinite(kz[j])) { zmin = fminf(zmin, kz[j]); zmax = fmaxf(zmax, kz[j]); }
-    }
-    for (int off = 32; off >= 1; off >>= 1) {
-        xmin = fminf(xmin, __shfl_xor(xmin, off)); xmax = fmaxf(xmax, __shfl_xor(xmax, off));
-        zmin = fminf(zmin, __shfl_xor(zmin, off)); zmax = fmaxf(zmax, __shfl_xor(zmax, off));
-    }
-    if (lane == 0) { red[0][w] = xmin; red[1][w] = xmax; red[2][w] = zmin; red[3][w] = zmax; }
+    RectXZ r;
+    kn.each([&](int, float x, float, float z, int &) { r.add_finite(x, z); });
+    rect_wave_reduce<TB>(r, red);
     for (int c = t; c < cells; c += TB) hist[c] = 0;
     __syncthreads();
     if (t == 0) {
-        for (int i = 1; i < TB / 64; ++i) {
-            xmin = fminf(xmin, red[0][i]); xmax = fmaxf(xmax, red[1][i]);
-            zmin = fminf(zmin, red[2][i]); zmax = fmaxf(zmax, red[3][i]);
-        }
-        if (!(xmin <= xmax)) { xmin = 0.f; xmax = 0.f; }
-        if (!(zmin <= zmax)) { zmin = 0.f; zmax = 0.f; }
-        double ext = fmax((double)xmax - (double)xmin, (double)zmax - (double)zmin);
+        r = rect_total<TB>(red);
+        if (!(r.x0 <= r.x1)) { r.x0 = 0.f; r.x1 = 0.f; }
+        if (!(r.z0 <= r.z1)) { r.z0 = 0.f; r.z1 = 0.f; }
+        double ext = fmax((double)r.x1 - (double)r.x0, (double)r.z1 - (double)r.z0);
         if (!(ext > 1e-6)) ext = 1e-6;
         const double s = ext / g * (1.0 + 1e-9);
-        gp.x0 = xmin; gp.z0 = zmin; gp.inv_s = 1.0 / s; gp.s = (float)s; gp.g = g;
+        gp.x0 = r.x0; gp.z0 = r.z0; gp.inv_s = 1.0 / s; gp.s = (float)s; gp.g = g;
         params[b] = gp;
     }
     __syncthreads();
     const double x0 = gp.x0, z0 = gp.z0, inv_s = gp.inv_s;
-    int kc[NK];
-#pragma unroll
-    for (int j = 0; j < NK; ++j) {
-        kc[j] = grid_coord(kz[j], z0, inv_s, g) * g + grid_coord(kx[j], x0, inv_s, g);
-        if (j * TB + t < m) atomicAdd(&hist[kc[j]], 1);
-    }
-    __syncthreads();
-    // exclusive scan of the cell counts: each thread owns a contiguous chunk (cells of a grid row must stay contiguous)
-    const int per = (cells + TB - 1) / TB;
-    const int lo = min(t * per, cells), hi = min(lo + per, cells);
-    int sum = 0;
-    for (int c = lo; c < hi; ++c) sum += hist[c];
-    int incl = sum;
-    for (int off = 1; off < 64; off <<= 1) {
-        const int v = __shfl_up(incl, off);
-        if (lane >= off) incl += v;
-    }
-    if (lane == 63) wsum[w] = incl;
-    __syncthreads();
-    int base = incl - sum;
-    for (int i = 0; i < w; ++i) base += wsum[i];
+    auto cell_of = [&](float x, float z) { return grid_coord(z, z0, inv_s, g) * g + grid_coord(x, x0, inv_s, g); };
+    const int per = (cells + TB - 1) / TB;     // contiguous: the cells of a grid row must stay contiguous
+
     int *__restrict__ cs = cell_start + (long)b * (TG_MAX * TG_MAX + 1);
-    for (int c = lo; c < hi; ++c) {
-        const int cnt = hist[c];
-        cs[c] = base;
-        hist[c] = base;                    // becomes the scatter cursor
-        base += cnt;
-    }
-    if (t == TB - 1) cs[cells] = m;
-    __syncthreads();
     float4 *__restrict__ so = sorted + (long)b * m;
-#pragma unroll
-    for (int j = 0; j < NK; ++j) {
-        const int k = j * TB + t;
-        if (k < m) so[atomicAdd(&hist[kc[j]], 1)] = make_float4(kx[j], ky[j], kz[j], __int_as_float(k));
-    }
-    if (!order) return;
+    if (t == TB - 1) cs[cells] = m;
+    cell_sort<TB>(kn, hist, cells, per, wsum, false, cell_of, [&](int c, int start, int) { cs[c] = start; },
+                  [&](int pos, int k, float x, float y, float z) { so[pos] = make_float4(x, y, z, __int_as_float(k)); });
 
     // the queries, counting-sorted by the cell they fall into (clamped like the ring search clamps them): order[b][0..n)
     __syncthreads();
     for (int c = t; c < cells; c += TB) hist[c] = 0;
     __syncthreads();
-    int qc[NQ];
-#pragma unroll
-    for (int j = 0; j < NQ; ++j) {
-        qc[j] = grid_coord(qz[j], z0, inv_s, g) * g + grid_coord(qx[j], x0, inv_s, g);
-        if (j * TB + t < n) atomicAdd(&hist[qc[j]], 1);
-    }
-    __syncthreads();
-    sum = 0;
-    for (int c = lo; c < hi; ++c) sum += hist[c];
-    incl = sum;
-    for (int off = 1; off < 64; off <<= 1) {
-        const int v = __shfl_up(incl, off);
-        if (lane >= off) incl += v;
-    }
-    __syncthreads();                           // wsum is rewritten
-    if (lane == 63) wsum[w] = incl;
-    __syncthreads();
-    base = incl - sum;
-    for (int i = 0; i < w; ++i) base += wsum[i];
-    for (int c = lo; c < hi; ++c) {
-        const int cnt = hist[c];
-        hist[c] = base;
-        base += cnt;
-    }
-    __syncthreads();
     int *__restrict__ od = order + (long)b * n;
-#pragma unroll
-    for (int j = 0; j < NQ; ++j) {
-        const int k = j * TB + t;
-        if (k < n) od[atomicAdd(&hist[qc[j]], 1)] = k;
-    }
+    cell_sort<TB>(un, hist, cells, per, wsum, true, cell_of, [](int, int, int) {},
+                  [&](int pos, int k, float, float, float) { od[pos] = k; });
 }
 
 // one query against one cloud's tables (cs: cell starts, so: known points sorted by cell) -- in global memory or staged in LDS
@@ -374,7 +176,7 @@ __global__ __launch_bounds__(256) void tnn_query_kernel(int n, int m, const floa
     const int b = blockIdx.y;
     const int slot = blockIdx.x * 256 + threadIdx.x;
     if (slot >= n) return;
-    const int p = order ? order[(long)b * n + slot] : slot;       // queries in cell order: a wave's lanes are neighbours
+    const int p = order[(long)b * n + slot];                      // queries in cell order: a wave's lanes are neighbours
     const GridParams gp = params[b];
     const float *u = unknown + ((long)b * n + p) * 3;
     float b1, b2, b3;
@@ -407,15 +209,13 @@ __global__ __launch_bounds__(1024) void tnn_query_lds_kernel(int n, int m, const
     __syncthreads();
     const int slot = blockIdx.x * 1024 + t;
     if (slot >= n) return;
-    const int p = order ? order[(long)b * n + slot] : slot;
+    const int p = order[(long)b * n + slot];
     const float *u = unknown + ((long)b * n + p) * 3;
     float b1, b2, b3;
     int i1, i2, i3;
     tnn_search(gp, u[0], u[1], u[2], lcs, lpts, b1, b2, b3, i1, i2, i3);
     tnn_store(b, n, p, b1, b2, b3, i1, i2, i3, dist2, idx, weight);
 }
-
-static size_t align_up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // Returns PRCNN_OK or an error; *used = 0 when the grid path declines (caller runs the brute-force scan).
 int three_nn_grid(int b, int n, int m, const float *unknown, const float *known, float *dist2, int *idx,
@@ -426,27 +226,22 @@ int three_nn_grid(int b, int n, int m, const float *unknown, const float *known,
     static const double cells_per_point = [] { const char *e = getenv("PRCNN_TNN_CELLS"); const double v = e ? atof(e) : 0.0; return v > 0.0 ? v : 2.0; }();
     int g = (int)ceil(sqrt((double)m * cells_per_point));          // round 2: sqrt(m / 2) (PRCNN_TNN_CELLS=0.5)
     if (g > TG_MAX) g = TG_MAX;
-    const bool ordered = true;           // queries served in cell order (round 6: switches PRCNN_TNN_UNORDERED / PRCNN_TNN_NO_LDS removed)
-    const size_t o_par = 0;
-    const size_t o_cs = align_up256((size_t)b * sizeof(GridParams));
-    const size_t o_sorted = o_cs + align_up256((size_t)b * (TG_MAX * TG_MAX + 1) * sizeof(int));
-    const size_t o_order = o_sorted + align_up256((size_t)b * m * sizeof(float4));
-    const size_t need = o_order + align_up256((size_t)b * n * sizeof(int));
-    char *base = scratch_for(st, need, 4);
-    if (!base) { set_error("three_nn: cannot allocate %zu bytes of grid scratch", need); return PRCNN_ELAUNCH; }
+    ScratchPlan plan;
+    const size_t o_par = plan.take((size_t)b * sizeof(GridParams));
+    const size_t o_cs = plan.take((size_t)b * (TG_MAX * TG_MAX + 1) * sizeof(int));
+    const size_t o_sorted = plan.take((size_t)b * m * sizeof(float4));
+    const size_t o_order = plan.take((size_t)b * n * sizeof(int));
+    char *base = scratch_for(st, plan.need, 4);
+    if (!base) { set_error("three_nn: cannot allocate %zu bytes of grid scratch", plan.need); return PRCNN_ELAUNCH; }
     GridParams *params = (GridParams *)(base + o_par);
     int *cs = (int *)(base + o_cs);
     float4 *sorted = (float4 *)(base + o_sorted);
-    int *order = ordered ? (int *)(base + o_order) : nullptr;
-    if (m <= 4 * TB && n <= 16 * TB)
-        hipLaunchKernelGGL((tnn_build_reg_kernel<4, 16>), dim3(b), dim3(TB), (size_t)g * g * sizeof(int), st, m, g, known, params, cs,
-                           sorted, n, unknown, order);
-    else
-        hipLaunchKernelGGL(tnn_build_kernel, dim3(b), dim3(TB), (size_t)g * g * sizeof(int), st, m, g, known, params, cs, sorted,
-                           n, unknown, order);
+    int *order = (int *)(base + o_order);                          // queries are served in cell order
+    auto *build = m <= 4 * TB && n <= 16 * TB ? tnn_build_kernel<RegPoints<TB, 4>, RegPoints<TB, 16>>
+                                              : tnn_build_kernel<GlobalPoints<TB>, GlobalPoints<TB>>;
+    hipLaunchKernelGGL(build, dim3(b), dim3(TB), (size_t)g * g * sizeof(int), st, m, g, known, params, cs, sorted, n, unknown, order);
     const size_t qlds = (size_t)m * sizeof(float4) + ((size_t)g * g + 1) * sizeof(int);
-    const bool no_lds = false;
-    if (!no_lds && qlds <= 128 * 1024 && n >= 2 * m) {
+    if (qlds <= 128 * 1024 && n >= 2 * m) {
         const int rc = ensure_dynamic_lds((const void *)tnn_query_lds_kernel, qlds, "three_nn(query)");
         if (rc != PRCNN_OK) return rc;
         hipLaunchKernelGGL(tnn_query_lds_kernel, dim3(ceil_div(n, 1024), b), dim3(1024), qlds, st, n, m, unknown, params, cs,

@@ -129,16 +129,23 @@ def test_ball_query_matches_oracle(ext, oracle, n, m, r, ns):
     assert (want[0, 0] == -7).all()  # empty ball: row untouched
 
 
+# the shapes that select what no other op-level case reaches in csrc/ball_dense.hip: the global-source build (n > 16384) at its
+# smallest n (H = 32768 counters, chunk shift 11), at an n that is no multiple of the chunk and at the upper edge of the u16 rank
+# and of nsample; the 16-points-per-thread register source with 15 of its 16 slots mostly empty (the barrier rule of its rounds)
+DENSE_BUILD_EDGES = [(16385, 64, 3.0, 16), (20000, 100, 3.0, 32), (65535, 64, 1.5, 64), (4097, 64, 6.0, 16)]
+
+
 @pytest.mark.parametrize("n,m,r,ns", [(16384, 4096, 0.1, 16), (16384, 4096, 0.2, 32), (16384, 4096, 0.5, 32),
-                                      (8192, 1000, 1.0, 64), (4096, 1024, 3.0, 16), (16384, 300, 0.05, 8)])
+                                      (8192, 1000, 1.0, 64), (4096, 1024, 3.0, 16), (16384, 300, 0.05, 8)] + DENSE_BUILD_EDGES)
 def test_ball_query_grid_equals_brute_force(ext, oracle, n, m, r, ns):
     """The bucket-sorted grid with a wave per centre (mode 0, automatic for n >= 2048: csrc/ball_dense.hip), the brute-force
     scan (mode 1) and round 1's linked-list grid (mode 2) return the same bits, also on a cloud with duplicated points,
-    far-away centres and coordinates on cell boundaries."""
+    far-away centres and coordinates on cell boundaries.  The DENSE_BUILD_EDGES cases must also exercise both branches of the
+    query and full as well as partly filled balls (asserted on the oracle's result)."""
     import importlib
     lib = importlib.import_module("3d_adapt_auto_driving_amd._lib")
     xyz = scenes(2, n, seed0=n + m)
-    xyz[1, n // 2:] = xyz[1, :n // 2]                                  # duplicates
+    xyz[1, n - n // 2:] = xyz[1, :n // 2]                              # duplicates
     xyz[0, :64, 0] = np.round(xyz[0, :64, 0] / np.float32(r * 1.001)) * np.float32(r * 1.001)   # on cell edges
     new_xyz = centres(oracle, xyz, m)
     new_xyz[0, 1] = [1e6, 0, -1e6]
@@ -153,6 +160,16 @@ def test_ball_query_grid_equals_brute_force(ext, oracle, n, m, r, ns):
     want = np.full((2, m, ns), -3, np.int32)
     oracle.ball_query_into(r, ns, xyz, new_xyz, want)
     assert np.array_equal(res[0], want)
+    if (n, m, r, ns) in DENSE_BUILD_EDGES:
+        full = (want[..., -1] != want[..., 0]).mean()
+        # candidates of a centre: the points in the 3 x 3 cells of edge 1.001 r around its own (the query's 192-candidate branch)
+        inv_s = 1.0 / (float(np.float32(r)) * 1.001)
+        cell = lambda a: np.floor(a[..., [0, 2]].astype(np.float64) * inv_s)
+        near = (np.abs(cell(new_xyz)[:, :, None] - cell(xyz)[:, None]) <= 1).all(-1).sum(-1)
+        above = (near > 192).mean()
+        print("n=%d: %.1f %% of the balls full, %.1f %% of the centres above 192 candidates" % (n, 100 * full, 100 * above))
+        assert 0.05 <= full < 1.0
+        assert 0.2 <= above <= 0.8
 
 
 def test_ball_query_rcnn_shape(ext, oracle):
@@ -376,6 +393,40 @@ def test_three_nn_grid_edge_cases(ext, oracle):
         wd2, widx = oracle.three_nn(unknown, known)
         assert np.array_equal(idx.cpu().numpy(), widx)
         assert np.array_equal(d2.cpu().numpy(), wd2)
+
+
+@pytest.mark.parametrize("n,m", [(1024, 1024), (1024, 4097), (16385, 1024), (2048, 5000)])
+def test_three_nn_grid_build_and_query_forms(ext, oracle, n, m):
+    """Every build / query pairing of csrc/three_nn_grid.hip by name: the smallest grid path (register source, global query), the
+    smallest m on the global source (m > 4096, global query), the smallest n on the global source (n > 16384: LDS query), and a
+    grid edge capped at TG_MAX (m = 5000).  Unrelated clouds (m may exceed n), an exact tie, one known cloud half duplicates.
+    dist2 and idx bit-exact vs the brute-force oracle."""
+    unknown = scenes(2, n, seed0=300 + n)
+    known = scenes(2, m, seed0=700 + m)
+    known[0, 1] = known[0, 0]                                          # exact tie: lowest index must win
+    known[1, m - m // 2:] = known[1, :m // 2]
+    d2 = torch.full((2, n, 3), float("nan"), device=DEV)
+    idx = torch.full((2, n, 3), -1, dtype=torch.int32, device=DEV)
+    ext.pointnet2.three_nn_wrapper(2, n, m, T(unknown), T(known), d2, idx)
+    wd2, widx = oracle.three_nn(unknown, known)
+    assert np.array_equal(idx.cpu().numpy(), widx)
+    assert np.array_equal(d2.cpu().numpy(), wd2)
+
+
+@pytest.mark.parametrize("n", [64, 4096, 65536])
+def test_point_groups_order_is_a_permutation(ext, n):
+    """fps_order_kernel through prcnn_point_groups: the order is any permutation by contract (arrival order inside a cell), so what is
+    pinned is that it IS one -- lane 3 of pxyz holds every index once per cloud, lanes 0-2 the point it names -- and that every
+    group's box contains its 64 points.  One cloud has all points equal (degenerate rectangle: every point in cell 0)."""
+    xyz = scenes(2, n, seed0=n)
+    xyz = np.concatenate([xyz, np.broadcast_to(xyz[0, :1], (1, n, 3))], 0)
+    pxyz, aabb = ext.roipool3d.point_groups(T(xyz))
+    pxyz, aabb = pxyz.cpu().numpy(), aabb.cpu().numpy()
+    index = np.ascontiguousarray(pxyz[..., 3]).view(np.int32)
+    assert np.array_equal(np.sort(index, 1), np.broadcast_to(np.arange(n, dtype=np.int32), (3, n)))
+    assert np.array_equal(pxyz[..., :3], np.take_along_axis(xyz, index.astype(np.int64)[..., None].repeat(3, -1), 1))
+    pts = pxyz[..., :3].reshape(3, n // 64, 64, 3)
+    assert (aabb[:, :, 0, None, :3] <= pts).all() and (pts <= aabb[:, :, 1, None, :3]).all()
 
 
 def test_roipool3d(ext, oracle):
