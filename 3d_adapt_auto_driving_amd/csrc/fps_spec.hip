@@ -49,30 +49,41 @@ namespace prcnn {
 // ---------------------------------------------------------------------------------------------
 constexpr int FS_RMAX = 16;     // picks per round at most
 
-// v of lane `src`: the header's __shfl(v, src, 64) with its address arithmetic written out -- (src & 63) + wbase, where wbase is
-// the caller's `lane id & ~63`, computed ONCE per kernel.  The header's function is a plain inline one that the compiler specialises,
-// before it inlines it, according to every call of it in the translation unit: with it the instructions of fps_spec_kernel<8> and
-// <16> depended on which other kernels the file held.  (wbase is 0 in a wave of 64 lanes; the term is what the header computes and
-// what these kernels have always executed -- dropping it is a change to measure, not a tidy-up.)
-__device__ __forceinline__ float fs_shfl(float v, int src, int wbase)
+// a value that every lane of the wave holds, as a wave-uniform one (v_readfirstlane: the compiler keeps it in an SGPR)
+__device__ __forceinline__ float fs_uniform(float v)
 {
-    const int index = (src & (WAVE - 1)) + wbase;
-    return __int_as_float(__builtin_amdgcn_ds_bpermute(index << 2, __float_as_int(v)));
+    return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
+}
+__device__ __forceinline__ float fs_readlane(float v, int l)
+{
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
 }
 
-// coordinates of point (lane l, slot) -- both wave-uniform -- as three v_readlane behind a scalar compare ladder.  (Indexing the
-// register arrays with the uniform slot made the compiler keep scratch copies of px / py / pz once the kernel was at its 128-VGPR
-// limit; a per-lane select chain would cost 3 x PPT VALU instructions per rebuild.)
-template <int PPT, int I = 0>
+// c <- the smallest key among the lanes `in`, m <- the lanes `in && also` that hold it.  Round 7: the lanes `in` are those whose value
+// equals a wave maximum -- ONE lane unless values tie exactly -- and then the key is that lane's, read with v_readlane: a ballot and
+// a population count in place of a cross-lane minimum (four DPP steps, four v_readlane) on the rebuild's dependent chain.
+__device__ __forceinline__ void fs_key_of(bool in, bool also, uint32_t lk, uint32_t &c, unsigned long long &m)
+{
+    const unsigned long long a = __ballot(in);
+    if (__popcll(a) == 1) c = (uint32_t)__builtin_amdgcn_readlane((int)lk, (int)__builtin_ctzll(a));
+    else c = wave_min_u32(in ? lk : 0xffffffffu);
+    m = a & __ballot(also && lk == c);
+}
+
+// coordinates of point (lane l, slot) -- both wave-uniform -- as three v_readlane behind scalar compares: a binary tree over the slot,
+// log2(PPT) compare-and-branch (round 7; until then a ladder `slot == 0, == 1, ...`, up to PPT of them).  (Indexing the register arrays
+// with the uniform slot made the compiler keep scratch copies of px / py / pz once the kernel was at its 128-VGPR limit; a per-lane
+// select chain would cost 3 x PPT VALU instructions per rebuild.)
+template <int PPT, int LO = 0, int N = PPT>
 __device__ __forceinline__ void fs_pick3(const float (&px)[PPT], const float (&py)[PPT], const float (&pz)[PPT], int slot, int l,
                                          float &x, float &y, float &z)
 {
-    if (slot == I) {
-        x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(px[I]), l));
-        y = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(py[I]), l));
-        z = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pz[I]), l));
-    } else if constexpr (I + 1 < PPT) {
-        fs_pick3<PPT, I + 1>(px, py, pz, slot, l, x, y, z);
+    if constexpr (N == 1) {
+        x = fs_readlane(px[LO], l); y = fs_readlane(py[LO], l); z = fs_readlane(pz[LO], l);
+    } else if (slot < LO + N / 2) {
+        fs_pick3<PPT, LO, N / 2>(px, py, pz, slot, l, x, y, z);
+    } else {
+        fs_pick3<PPT, LO + N / 2, N / 2>(px, py, pz, slot, l, x, y, z);
     }
 }
 
@@ -105,6 +116,7 @@ __global__ __launch_bounds__(1024) void fps_spec_kernel(
     float px[PPT], py[PPT], pz[PPT], pt[PPT];
     uint32_t pc[PPT];                                                 // (tie key << SB) | slot; ~0 for a slot beyond the cloud
     float bx0 = INFINITY, bx1 = -INFINITY, by0 = INFINITY, by1 = -INFINITY, bz0 = INFINITY, bz1 = -INFINITY;
+    float wx0 = INFINITY, wx1 = -INFINITY, wy0 = INFINITY, wy1 = -INFINITY, wz0 = INFINITY, wz1 = -INFINITY;
 #pragma unroll
     for (int i = 0; i < PPT; ++i) {
         // position in Morton order: a wave = 1024 consecutive positions.  (Round 6, measured and not kept: tiles or tile PAIRS dealt
@@ -130,14 +142,14 @@ __global__ __launch_bounds__(1024) void fps_spec_kernel(
             z0 = fmin_raw(z0, __shfl_xor(z0, d, 64)); z1 = fmax_raw(z1, __shfl_xor(z1, d, 64));
         }
         if (lane == i) { bx0 = x0; bx1 = x1; by0 = y0; by1 = y1; bz0 = z0; bz1 = z1; }
+        wx0 = fmin_raw(wx0, x0); wx1 = fmax_raw(wx1, x1); wy0 = fmin_raw(wy0, y0); wy1 = fmax_raw(wy1, y1);
+        wz0 = fmin_raw(wz0, z0); wz1 = fmax_raw(wz1, z1);
     }
+    // the wave's OWN box, the union of its tile boxes (round 7): six wave-uniform values, held in SGPRs -- see wave_hit
+    wx0 = fs_uniform(wx0); wx1 = fs_uniform(wx1); wy0 = fs_uniform(wy0); wy1 = fs_uniform(wy1); wz0 = fs_uniform(wz0); wz1 = fs_uniform(wz1);
 
-    // every group of PPT lanes holds the PPT tile boxes (lane -> tile lane % PPT): 64 / PPT pivots are box-tested per pass
-    constexpr int GP = 64 / PPT;
-    const int wbase = (int)__lane_id() & ~(WAVE - 1);               // see fs_shfl
-    bx0 = fs_shfl(bx0, lane & (PPT - 1), wbase); bx1 = fs_shfl(bx1, lane & (PPT - 1), wbase);
-    by0 = fs_shfl(by0, lane & (PPT - 1), wbase); by1 = fs_shfl(by1, lane & (PPT - 1), wbase);
-    bz0 = fs_shfl(bz0, lane & (PPT - 1), wbase); bz1 = fs_shfl(bz1, lane & (PPT - 1), wbase);
+    // lane i < PPT holds the box of tile i: ONE pivot, its coordinates wave-uniform, is tested against the PPT tile boxes at a time
+    // (rounds 4-6: every group of PPT lanes held the boxes and 64 / PPT pivots were tested per pass; fps_spec2_kernel still does)
     // pivots against the registers: tile boxes prune against `bound`, an upper bound of every running minimum of this wave
     // `touched`: one of the tiles that hold this wave's two PUBLISHED points went through an update -- only then are its entries rebuilt
     // (round 5).  A pivot that changes other points of the wave leaves the published points, their values and keys as they are, and
@@ -147,13 +159,29 @@ __global__ __launch_bounds__(1024) void fps_spec_kernel(
     // themselves 481 / 742 against 480 / 742.
     unsigned long long touched = 0ull, etiles = ~0ull;
     float bound = INFINITY;
-    // which tiles can a pivot (per lane group: ox, oy, oz differ by group) change?  bit g * PPT + i: tile i, the group's pivot
+    // which tiles can the pivot change?  bit i: tile i (live: lane < PPT)
     auto box_mask = [&](float ox, float oy, float oz, bool live) __attribute__((always_inline)) {
         const float dx = fmax_raw(fmax_raw(bx0 - ox, ox - bx1), 0.f);
         const float dy = fmax_raw(fmax_raw(by0 - oy, oy - by1), 0.f);
         const float dz = fmax_raw(fmax_raw(bz0 - oz, oz - bz1), 0.f);
         const float lb = dx * dx + dy * dy + dz * dz;
         return __ballot(live && !(lb * 0.99999f >= bound));           // empty boxes give lb = +inf
+    };
+    // WAVE-LEVEL CULL (round 7): can the point (ox, oy, oz) -- per lane -- change ANY point of this wave?  The same test as box_mask,
+    // same margin, same `bound`, against the wave's own box.  Exact: the wave box contains every tile box, so each of dx, dy, dz and
+    // with them lb (sums and products of non-negative terms, every rounding monotone) is no larger than the tile's -- a point that fails
+    // here fails box_mask for every tile.  It runs in the merge, where lane e already HOLDS entry e's coordinates, in front of
+    // barrier A2 (whose wait hides it): the round's pivots are then known per wave as a set of entry lanes, and phase 4 box-tests
+    // only those, one by one, reading their coordinates with v_readlane.  Rounds 4-6 sent every pivot through the tile tests of
+    // every wave -- ceil(r / 4) passes of 3 ds_bpermute + ~15 VALU + a ballot at the head of the busiest wave's chain
+    // (profiles/r06_fps_round_stamps.txt) -- behind three ds_permute that put pivot q into lanes 3 q .. 3 q + 2 of one register;
+    // a wave a sixteenth of the cloud sees 1-3 of a round's 8.5 pivots, and neither permute is needed to find them.
+    auto wave_hit = [&](float ox, float oy, float oz) __attribute__((always_inline)) {
+        const float dx = fmax_raw(fmax_raw(wx0 - ox, ox - wx1), 0.f);
+        const float dy = fmax_raw(fmax_raw(wy0 - oy, oy - wy1), 0.f);
+        const float dz = fmax_raw(fmax_raw(wz0 - oz, oz - wz1), 0.f);
+        const float lb = dx * dx + dy * dy + dz * dz;
+        return !(lb * 0.99999f >= bound);
     };
     auto update = [&](float ox, float oy, float oz, unsigned long long mask) __attribute__((always_inline)) {
         if (mask != 0ull) {
@@ -212,13 +240,13 @@ __global__ __launch_bounds__(1024) void fps_spec_kernel(
             }
             // best lane, best of the other lanes, third value
             const float v1 = wave_max_f32(bv);
-            const uint32_t c1 = wave_min_u32(bv == v1 ? lk : 0xffffffffu);
-            const unsigned long long m1 = __ballot(bv == v1 && lk == c1);
+            uint32_t c1; unsigned long long m1;
+            fs_key_of(bv == v1, true, lk, c1, m1);
             const int l1 = m1 ? (int)__builtin_ctzll(m1) : 0;
             const float bv2 = lane == l1 ? -INFINITY : bv;
             const float v2 = wave_max_f32(bv2);
-            const uint32_t c2 = wave_min_u32(bv2 == v2 ? lk : 0xffffffffu);
-            const unsigned long long m2 = __ballot(lane != l1 && bv2 == v2 && lk == c2);
+            uint32_t c2; unsigned long long m2;
+            fs_key_of(bv2 == v2, lane != l1, lk, c2, m2);
             const int l2 = m2 ? (int)__builtin_ctzll(m2) : l1;
             const float v3 = wave_max_f32((lane == l1 || lane == l2) ? -INFINITY : bv);
             const float s1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sv), l1));
@@ -248,8 +276,8 @@ __global__ __launch_bounds__(1024) void fps_spec_kernel(
         // does e precede i in the order (value desc, key asc), and does it lie closer to i than i's running minimum?  Entry i's RANK
         // (how many precede it) and its BLOCKED bit are a population count / a test of one half of a ballot: wave-uniform, written by
         // one lane.  Behind the second barrier EVERY wave reads the 32 ranks and derives the verdict itself -- the picks of the round
-        // are the ranks 0 .. r-1 up to the first rank that fails -- so nobody waits for wave 0 and a third barrier; a forward
-        // permute (ds_permute: lane e sends to lane rank(e)) puts pivot q's coordinates into lane q of every wave.
+        // are the ranks 0 .. r-1 up to the first rank that fails -- so nobody waits for wave 0 and a third barrier; the pivots stay
+        // in their entry lanes (round 6 permuted pivot q into lane q of every wave: ds_permute, lane e sends to lane rank(e)).
         // (Rounds 4-5: lane = entry i, wave = entry e, ranks summed through LDS atomics, the verdict by wave 0 into s_res, barrier B:
         // pairs 540 + verdict 760 + the barrier ~ 1500 of a round's 8200 cycles, profiles/r05_fps_round_stamps.txt.  History before that:
         // every wave merging the whole table by sequential extraction -- issue-bound, 5.2 ms; one wave walking its half of the table,
@@ -275,10 +303,12 @@ __global__ __launch_bounds__(1024) void fps_spec_kernel(
                 s_blk[i] = (unsigned)(h ? (kb >> 32) : kb) != 0u;
             }
         }
+        const bool valid = !(ck == 0xffffffffu || !(cv > -1.0f));      // (reference: best starts at -1, besti at 0)
+        // should entry e become a pivot of this round: does it reach this wave?  (an invalid first entry stands for point 0: always)
+        const bool hit = wave_hit(cx, cy, cz) || !valid;
         lds_barrier();                                                // A2: every entry has its rank
         const int rank = s_rank[e];
         const bool blocked = s_blk[e] != 0;
-        const bool valid = !(ck == 0xffffffffu || !(cv > -1.0f));      // (reference: best starts at -1, besti at 0)
         const bool pass = rank == 0 ? true : ((cv > gB) && (cv > 0.f) && valid && !blocked);
         // a round ends behind an invalid first entry (the reference then picks index 0: every running minimum is below -1 / NaN)
         const bool stop = !pass || (rank == 0 && !valid);
@@ -290,35 +320,20 @@ __global__ __launch_bounds__(1024) void fps_spec_kernel(
             sel[j + rank] = valid ? kc.decode(ck) : 0;
             if (nxyz) { nxyz[3 * (j + rank)] = ox_; nxyz[3 * (j + rank) + 1] = oy_; nxyz[3 * (j + rank) + 2] = oz_; }
         }
-        // pivot q -> lanes 3 q, 3 q + 1, 3 q + 2 of ONE register (x, y, z): lane e (first half) sends its three coordinates to the lanes
-        // of its rank; whatever is no pivot goes to lane 63, which nobody reads; lanes nobody writes read 0, so the three answers OR
-        // together.  (Three registers, lane q = pivot q, spilled fps_spec_kernel<16> at its 128-register limit.)
-        const int dst = (h == 0 && rank < FS_RMAX) ? 3 * rank : 63;
-        const float rv = __int_as_float(__builtin_amdgcn_ds_permute(dst << 2, __float_as_int(ox_)) |
-                                        __builtin_amdgcn_ds_permute(min(dst + 1, 63) << 2, __float_as_int(oy_)) |
-                                        __builtin_amdgcn_ds_permute(min(dst + 2, 63) << 2, __float_as_int(oz_)));
         // ---- 4. running minima against this round's pivots (the last pick of the whole run does not update them: sampling_gpu.cu)
+        // The pivots stay where they are, in the entry lanes (first half, rank < apply_n); this wave's share of them is one ballot.
+        // In which order a wave applies them is free: a running minimum is a min over the pivots, `touched` an OR.
+        // (Rounds 4-6 permuted pivot q into lanes 3 q .. 3 q + 2 of one register; three registers, lane q = pivot q, spilled
+        // fps_spec_kernel<16> at its 128-register limit THEN -- the three here replace that register and the permutes' operands.)
         j += r;
         const int apply_n = j >= m ? r - 1 : r;
         touched = 0ull;
-        for (int q0 = 0; q0 < apply_n; q0 += GP) {
-            // lane group g tests pivot q0 + g against the PPT tile boxes
-            const int qg = q0 + lane / PPT;
-            const int src = 3 * min(qg, FS_RMAX - 1);
-            const float gx = fs_shfl(rv, src, wbase), gy = fs_shfl(rv, src + 1, wbase), gz = fs_shfl(rv, src + 2, wbase);
-            const unsigned long long masks = box_mask(gx, gy, gz, qg < apply_n);
-            if (masks == 0ull) continue;
-#pragma unroll
-            for (int g = 0; g < GP; ++g) {
-                const unsigned long long mk = (masks >> (g * PPT)) & ((PPT == 64) ? ~0ull : ((1ull << PPT) - 1ull));
-                if (mk != 0ull) {
-                    const int q = q0 + g;
-                    const float ox = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rv), 3 * q));
-                    const float oy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rv), 3 * q + 1));
-                    const float oz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rv), 3 * q + 2));
-                    update(ox, oy, oz, mk);
-                }
-            }
+        unsigned mine = (unsigned)__ballot(h == 0 && rank < apply_n && hit);
+        while (mine != 0u) {
+            const int l = __builtin_ctz(mine);
+            mine &= mine - 1u;
+            const float ox = fs_readlane(ox_, l), oy = fs_readlane(oy_, l), oz = fs_readlane(oz_, l);
+            update(ox, oy, oz, box_mask(ox, oy, oz, lane < PPT));
         }
     }
     if (mind) {
@@ -396,12 +411,19 @@ __global__ __launch_bounds__(1024) void fps_spec2_kernel(
     const int t = threadIdx.x, lane = t & 63, w = t >> 6, gw = 16 * half + w;       // gw: this wave among the cloud's 32
     __builtin_amdgcn_s_setprio(3);
 
-    // COPIES of fps_spec_kernel<16>'s blocks (keep them in step; the comments are there): tile load and box reduction, box_mask, update,
-    // the rebuild of the wave's entries.  The differences: the wave's first Morton position is gw's, not w's, and `touched |= mask`
-    // without `& etiles` -- on purpose: this kernel keeps its entries in LDS and rebuilds on any touch.
+    // COPIES of fps_spec_kernel<16>'s blocks (keep them in step; the comments are there): tile load and box reduction (the wave's own box
+    // with it), box_mask, wave_hit, update, the rebuild of the wave's entries.  The differences: the wave's first Morton position is
+    // gw's, not w's; `touched |= mask` without `& etiles` -- on purpose: this kernel keeps its entries in LDS and rebuilds on any touch;
+    // and the wave-level cull runs behind barrier B on the round's pivots as wave 0 left them in s_res (lane q = pivot q, rank order),
+    // not on the entries in front of A2: here ONE wave holds the verdict, the others never see the ranks.  A surviving pivot's
+    // coordinates are read from s_res again (a broadcast read), not kept in three registers over the loop: this kernel spills
+    // (12 registers; 14 with the three, and 8 x (32768 -> 4096) then takes 3.06 / 7.30 ms against 2.92 / 6.97 ms uniform /
+    // LiDAR-shaped -- before round 7: 2.97 / 6.95 ms).  Any change here is measured at that shape: the rebuild's key shortcut alone,
+    // with the pivot passes of round 6, ALSO spilled 14 and ran 3.15 / 7.8 ms.
     float px[PPT], py[PPT], pz[PPT], pt[PPT];
     uint32_t pc[PPT];
     float bx0 = INFINITY, bx1 = -INFINITY, by0 = INFINITY, by1 = -INFINITY, bz0 = INFINITY, bz1 = -INFINITY;
+    float wx0 = INFINITY, wx1 = -INFINITY, wy0 = INFINITY, wy1 = -INFINITY, wz0 = INFINITY, wz1 = -INFINITY;
 #pragma unroll
     for (int i = 0; i < PPT; ++i) {
         const int s = gw * (64 * PPT) + i * 64 + lane;
@@ -424,12 +446,10 @@ __global__ __launch_bounds__(1024) void fps_spec2_kernel(
             z0 = fmin_raw(z0, __shfl_xor(z0, d, 64)); z1 = fmax_raw(z1, __shfl_xor(z1, d, 64));
         }
         if (lane == i) { bx0 = x0; bx1 = x1; by0 = y0; by1 = y1; bz0 = z0; bz1 = z1; }
+        wx0 = fmin_raw(wx0, x0); wx1 = fmax_raw(wx1, x1); wy0 = fmin_raw(wy0, y0); wy1 = fmax_raw(wy1, y1);
+        wz0 = fmin_raw(wz0, z0); wz1 = fmax_raw(wz1, z1);
     }
-    constexpr int GP = 64 / PPT;
-    const int wbase = (int)__lane_id() & ~(WAVE - 1);               // see fs_shfl
-    bx0 = fs_shfl(bx0, lane & (PPT - 1), wbase); bx1 = fs_shfl(bx1, lane & (PPT - 1), wbase);
-    by0 = fs_shfl(by0, lane & (PPT - 1), wbase); by1 = fs_shfl(by1, lane & (PPT - 1), wbase);
-    bz0 = fs_shfl(bz0, lane & (PPT - 1), wbase); bz1 = fs_shfl(bz1, lane & (PPT - 1), wbase);
+    wx0 = fs_uniform(wx0); wx1 = fs_uniform(wx1); wy0 = fs_uniform(wy0); wy1 = fs_uniform(wy1); wz0 = fs_uniform(wz0); wz1 = fs_uniform(wz1);
     unsigned long long touched = 0ull;
     float bound = INFINITY;
     auto box_mask = [&](float ox, float oy, float oz, bool live) __attribute__((always_inline)) {
@@ -438,6 +458,13 @@ __global__ __launch_bounds__(1024) void fps_spec2_kernel(
         const float dz = fmax_raw(fmax_raw(bz0 - oz, oz - bz1), 0.f);
         const float lb = dx * dx + dy * dy + dz * dz;
         return __ballot(live && !(lb * 0.99999f >= bound));
+    };
+    auto wave_hit = [&](float ox, float oy, float oz) __attribute__((always_inline)) {
+        const float dx = fmax_raw(fmax_raw(wx0 - ox, ox - wx1), 0.f);
+        const float dy = fmax_raw(fmax_raw(wy0 - oy, oy - wy1), 0.f);
+        const float dz = fmax_raw(fmax_raw(wz0 - oz, oz - wz1), 0.f);
+        const float lb = dx * dx + dy * dy + dz * dz;
+        return !(lb * 0.99999f >= bound);
     };
     auto update = [&](float ox, float oy, float oz, unsigned long long mask) __attribute__((always_inline)) {
         if (mask != 0ull) {
@@ -493,13 +520,13 @@ __global__ __launch_bounds__(1024) void fps_spec2_kernel(
                 lk = c < lk ? c : lk;
             }
             const float v1 = wave_max_f32(bv);
-            const uint32_t c1 = wave_min_u32(bv == v1 ? lk : 0xffffffffu);
-            const unsigned long long m1 = __ballot(bv == v1 && lk == c1);
+            uint32_t c1; unsigned long long m1;
+            fs_key_of(bv == v1, true, lk, c1, m1);
             const int l1 = m1 ? (int)__builtin_ctzll(m1) : 0;
             const float bv2 = lane == l1 ? -INFINITY : bv;
             const float v2 = wave_max_f32(bv2);
-            const uint32_t c2 = wave_min_u32(bv2 == v2 ? lk : 0xffffffffu);
-            const unsigned long long m2 = __ballot(lane != l1 && bv2 == v2 && lk == c2);
+            uint32_t c2; unsigned long long m2;
+            fs_key_of(bv2 == v2, lane != l1, lk, c2, m2);
             const int l2 = m2 ? (int)__builtin_ctzll(m2) : l1;
             const float v3 = wave_max_f32((lane == l1 || lane == l2) ? -INFINITY : bv);
             const float s1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sv), l1));
@@ -603,28 +630,20 @@ __global__ __launch_bounds__(1024) void fps_spec2_kernel(
             if (lane == 0) s_res[0] = __int_as_float(r);
         }
         lds_barrier();                                                // B
-        const float rv = s_res[lane];
-        const int r = __builtin_amdgcn_readfirstlane(__float_as_int(rv));
+        // the round's result: r, and pivot q's coordinates into lane q (s_res is rewritten behind the NEXT round's barrier A2)
+        const int r = __float_as_int(s_res[0]);
+        const int q3 = 1 + 3 * min(lane, FS_RMAX - 1);
+        const float ox_ = s_res[q3], oy_ = s_res[q3 + 1], oz_ = s_res[q3 + 2];
         j += r;
         const int apply_n = j >= m ? r - 1 : r;
         touched = 0ull;
-        for (int q0 = 0; q0 < apply_n; q0 += GP) {
-            const int qg = q0 + lane / PPT;
-            const int src = 1 + 3 * min(qg, FS_RMAX - 1);
-            const float gx = fs_shfl(rv, src, wbase), gy = fs_shfl(rv, src + 1, wbase), gz = fs_shfl(rv, src + 2, wbase);
-            const unsigned long long masks = box_mask(gx, gy, gz, qg < apply_n);
-            if (masks == 0ull) continue;
-#pragma unroll
-            for (int g = 0; g < GP; ++g) {
-                const unsigned long long mk = (masks >> (g * PPT)) & ((1ull << PPT) - 1ull);
-                if (mk != 0ull) {
-                    const int q = q0 + g;
-                    const float ox = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rv), 1 + 3 * q));
-                    const float oy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rv), 2 + 3 * q));
-                    const float oz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rv), 3 + 3 * q));
-                    update(ox, oy, oz, mk);
-                }
-            }
+        // the wave-level cull of fps_spec_kernel: lane q tests pivot q against the wave's own box, the survivors go through the tile tests
+        unsigned mine = (unsigned)__ballot(lane < apply_n && wave_hit(ox_, oy_, oz_));
+        while (mine != 0u) {
+            const int l = __builtin_ctz(mine);
+            mine &= mine - 1u;
+            const float ox = fs_uniform(s_res[1 + 3 * l]), oy = fs_uniform(s_res[2 + 3 * l]), oz = fs_uniform(s_res[3 + 3 * l]);
+            update(ox, oy, oz, box_mask(ox, oy, oz, lane < PPT));
         }
         ++round;
     }

@@ -4,8 +4,9 @@ into profiles/_exp/libprcnn_hip_fps_stamps.so; the product library is not touche
 
   python profiles/fps_stamps.py build               (build container: hipcc)
   python profiles/fps_stamps.py run [uniform|lidar] (GPU box): 16384 -> 4096, B = 8; per wave: rounds, and cycles per round spent in
-      rebuild + publish | waiting at barrier A | the pair tests of the merge | waiting at barrier A2 | the verdict + the pivot permute
-      (every wave since round 6: no barrier B) | - | distance updates"""
+      rebuild + publish | waiting at barrier A | the pair tests of the merge | waiting at barrier A2 | the verdict + the ballot of
+      this wave's share of the pivots (every wave since round 6: no barrier B; round 7: no pivot permute) | - | distance updates, the
+      tile tests of the wave's share in them"""
 import ctypes, importlib, os, subprocess, sys
 import numpy as np
 
@@ -36,7 +37,7 @@ def instrument():
         "    if (mind) {\n#pragma unroll\n        for (int i = 0; i < PPT; ++i)\n            if (pc[i] != 0xffffffffu) mind[kc.decode(pc[i] >> SB)] = pt[i];\n    }\n"
         "    if (blockIdx.x == 0 && lane == 0) for (int i = 0; i < %d; ++i) g_fps_acc[w * %d + i] = acc_[i];\n}" % (NPH, NPH))
     # the update phase ends at the bottom of the while loop: stamp right before its closing brace = before 'if (mind)'
-    put("                    update(ox, oy, oz, mk);\n                }\n            }\n        }\n    }\n", "                    update(ox, oy, oz, mk);\n                }\n            }\n        }\n        PH(6)\n    }\n")
+    put("            update(ox, oy, oz, box_mask(ox, oy, oz, lane < PPT));\n        }\n    }\n", "            update(ox, oy, oz, box_mask(ox, oy, oz, lane < PPT));\n        }\n        PH(6)\n    }\n")
     k = "__device__ unsigned long long g_fps_acc[16 * %d];\n" % NPH + k
     s = s[:a] + k + s[b:]
     s += ('\nextern "C" int prcnn_debug_fps_acc(unsigned long long *dst)\n{\n    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(prcnn::g_fps_acc), '
@@ -77,7 +78,7 @@ def run(kind):
     a = np.array(buf, dtype=np.float64).reshape(16, NPH)
     rounds = a[:, 7]
     print("%s scenes, cloud 0, 16384 -> 4096: %d rounds; s_memtime cycles per round by wave" % (kind, int(rounds[0])))
-    print("wave | rebuild+publish | wait A | pairs | wait A2 | verdict + permute (every wave, round 6) | - | updates | sum")
+    print("wave | rebuild+publish | wait A | pairs | wait A2 | verdict + own pivots (every wave, round 7) | - | updates | sum")
     for w in range(16):
         v = a[w, :7] / rounds[w]
         print("%4d | " % w + " | ".join("%7.1f" % x for x in v) + " | %7.1f" % v.sum())
