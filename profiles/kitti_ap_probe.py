@@ -3,17 +3,17 @@ synthetic annotations (profiles/kitti_ap_probe.md): per configuration both paths
 of 7.  Every stage is host time; the device path's stages end in a device synchronise (so its total carries six synchronises the
 uninstrumented call does not make; the last rows give the uninstrumented calls).
 
-  host stages   : parse (both sides' lines -> annotations), _Split (18 of them: 3 kinds x 6 difficulties), overlaps, pass 1,
-                  thresholds, pass 2, rest (curves, mAP, text)
+  host stages   : parse (both sides' lines -> annotations), table + flags (SplitTable, HostStats's columns, split_flags of the six
+                  difficulties), overlaps, pass 1, thresholds, pass 2, rest (curves, mAP, text)
   device stages : parse (the same), table (SplitTable + uploads + the host-made cosine terms), flags, overlaps, pass 1,
                   sort + thresholds, pass 2, read (+ curves, mAP, text)
 
   python profiles/kitti_ap_probe.py [--images 512 3769] [--dense 512] [--rounds 7] [--warmup 3] [--out FILE.json]"""
-import argparse, ctypes, importlib, json, os, statistics, sys, time
+import argparse, importlib, json, os, statistics, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 PKG = "3d_adapt_auto_driving_amd"
-KE = importlib.import_module(PKG + ".kitti_eval"); L = importlib.import_module(PKG + "._lib")
+KE = importlib.import_module(PKG + ".kitti_eval")
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--images", type=int, nargs="*", default=[512, 3769]); ap.add_argument("--dense", type=int, nargs="*", default=[512])
@@ -71,42 +71,33 @@ def min_overlaps(dense):
     return np.stack([o7, o5] + extra, 0)[:, :, [0]]
 
 
-P = lambda x: x.ctypes.data_as(ctypes.c_void_p)
 DIFFS = [0, 1, 2, 3, 4, 5]
 
 
 def host_path(gl, dl, dense):
-    t, t0 = {k: 0.0 for k in ("parse", "_Split", "overlaps", "pass 1", "thresholds", "pass 2")}, clock()
+    t, t0 = {k: 0.0 for k in ("parse", "table + flags", "overlaps", "pass 1", "thresholds", "pass 2")}, clock()
     gt, dt = [KE.annos_from_lines(x) for x in gl], [KE.annos_from_lines(x) for x in dl]
-    t["parse"] = clock() - t0
-    mo, n_img = min_overlaps(dense), len(gt)
+    t1 = clock(); t["parse"] = t1 - t0
+    hs = KE.HostStats(KE.SplitTable(gt, dt))
+    flags = hs.flags(0, "kitti", DIFFS, "new")
+    t["table + flags"] = clock() - t1
+    mo = min_overlaps(dense)
     curves = []
     for kind in (0, 1, 2):
         s = clock()
-        ov = KE.calculate_iou(dt, gt, kind)
-        flat = np.ascontiguousarray(np.concatenate([o.reshape(-1) for o in ov]), dtype=np.float64)
-        t["overlaps"] += clock() - s
+        ov, lev = hs.overlaps(kind), mo[:, kind, 0]
+        s1 = clock(); t["overlaps"] += s1 - s
+        scores = hs.scores(flags, ov, kind, lev)
+        s2 = clock(); t["pass 1"] += s2 - s1
+        thr = hs.thresholds(scores, flags[2])
+        s3 = clock(); t["thresholds"] += s3 - s2
+        pr = hs.pr(flags, ov, kind, lev, thr, kind == 0)
+        t["pass 2"] += clock() - s3
         shape = [1, 6, len(mo), 41]
         prec, rec, aos = np.zeros(shape), np.zeros(shape), np.zeros(shape)
-        for l, d in enumerate(DIFFS):
-            s = clock()
-            sp = KE._Split(gt, dt, 0, "kitti", d, "new")
-            t["_Split"] += clock() - s
-            for k, lev in enumerate(mo[:, kind, 0]):
-                s = clock()
-                scores, n = np.zeros((max(1, int(sp.gt_nums.sum())),)), ctypes.c_longlong(0)
-                L.call("prcnn_kitti_collect_scores", n_img, P(sp.gt_nums), P(sp.dt_nums), P(flat), P(sp.gt_datas), P(sp.dt_datas),
-                       P(sp.ignored_gts), P(sp.ignored_dets), kind, float(lev), P(scores), ctypes.cast(ctypes.pointer(n), ctypes.c_void_p))
-                s1 = clock(); t["pass 1"] += s1 - s
-                thr = np.array(KE.get_thresholds(scores[:n.value], sp.num_valid_gt), dtype=np.float64)
-                s2 = clock(); t["thresholds"] += s2 - s1
-                pr = np.zeros([len(thr), 4])
-                if len(thr):
-                    L.call("prcnn_kitti_accumulate_pr", n_img, P(sp.gt_nums), P(sp.dt_nums), P(sp.dc_nums), P(flat), P(sp.gt_datas),
-                           P(sp.dt_datas), P(sp.dontcares), P(sp.ignored_gts), P(sp.ignored_dets), kind, float(lev), P(thr), len(thr),
-                           int(kind == 0), P(pr))
-                t["pass 2"] += clock() - s2
-                KE._fill_curves(prec[0, l, k], rec[0, l, k], aos[0, l, k], pr, kind == 0)
+        for g, rows in enumerate(pr):
+            l, k = divmod(g, len(mo))
+            KE._fill_curves(prec[0, l, k], rec[0, l, k], aos[0, l, k], rows, kind == 0)
         curves.append((prec, aos))
     t["total"] = clock() - t0
     t["rest"] = t["total"] - sum(v for k, v in t.items() if k != "total")

@@ -127,27 +127,21 @@ def _p(a):
 
 
 def host_stages(KE, gt, dt, current_class, kind, levels, difficultys, overlaps, dataset="kitti", metric="new", compute_aos=False):
-    """The host path of eval_class, stage by stage, for one class: per (difficulty index, level index) a dict with the pass-1
-    scores sorted descending, num_valid_gt, the thresholds and pr (n_thresholds, 4) -- from the library's host entries."""
-    import ctypes
-    L = KE._lib
+    """The host path of eval_class, stage by stage (KE.HostStats), for one class: per (difficulty index, level index) a dict with the
+    pass-1 scores sorted descending, num_valid_gt, the thresholds, pr (n_thresholds, 4) and the two flag vectors."""
+    hs = KE.HostStats(KE.SplitTable(gt, dt))
     flat = np.ascontiguousarray(np.concatenate([np.asarray(o, dtype=np.float64).reshape(-1) for o in overlaps]), dtype=np.float64)
+    levels = np.asarray(levels, dtype=np.float64)
+    flags = hs.flags(current_class, dataset, difficultys, metric)
+    scores = hs.scores(flags, flat, kind, levels)
+    thr = hs.thresholds(scores, flags[2])
+    pr = hs.pr(flags, flat, kind, levels, thr, compute_aos)
     out = {}
-    for l, difficulty in enumerate(difficultys):
-        sp = KE._Split(gt, dt, current_class, dataset, difficulty, metric)
-        for k, level in enumerate(levels):
-            scores = np.zeros((max(1, int(sp.gt_nums.sum())),), dtype=np.float64)
-            n = ctypes.c_longlong(0)
-            L.call("prcnn_kitti_collect_scores", len(gt), _p(sp.gt_nums), _p(sp.dt_nums), _p(flat), _p(sp.gt_datas), _p(sp.dt_datas),
-                   _p(sp.ignored_gts), _p(sp.ignored_dets), int(kind), float(level), _p(scores), ctypes.cast(ctypes.pointer(n), ctypes.c_void_p))
-            thr = np.array(KE.get_thresholds(scores[:n.value], sp.num_valid_gt), dtype=np.float64)
-            pr = np.zeros([len(thr), 4])
-            if len(thr):
-                L.call("prcnn_kitti_accumulate_pr", len(gt), _p(sp.gt_nums), _p(sp.dt_nums), _p(sp.dc_nums), _p(flat), _p(sp.gt_datas),
-                       _p(sp.dt_datas), _p(sp.dontcares), _p(sp.ignored_gts), _p(sp.ignored_dets), int(kind), float(level), _p(thr),
-                       len(thr), int(bool(compute_aos)), _p(pr))
-            out[(l, k)] = {"scores": np.sort(scores[:n.value])[::-1], "num_valid_gt": sp.num_valid_gt, "thresholds": thr, "pr": pr,
-                           "ignored_gt": sp.ignored_gts, "ignored_dt": sp.ignored_dets}
+    for l in range(len(difficultys)):
+        for k in range(len(levels)):
+            g = l * len(levels) + k
+            out[(l, k)] = {"scores": np.sort(scores[g])[::-1], "num_valid_gt": int(flags[2][l]), "thresholds": thr[g], "pr": pr[g],
+                           "ignored_gt": flags[0][l], "ignored_dt": flags[1][l]}
     return out
 
 

@@ -159,8 +159,9 @@ def test_defaults_reproduce_the_plain_evaluator(oracle):
         for diff in range(6):
             p, q = KE.clean_data(g, d, 0, "kitti", diff), KE.clean_data(g, d, 0, "kitti", diff, metric="new")
             assert p[0] == q[0] and all(np.array_equal(x, y) for x, y in zip(p[1:], q[1:]))
-    s = KE._Split(gt, dt, 0, "kitti", 1)
-    assert s.num_valid_gt == KE._Split(gt, dt, 0, "kitti", 1, "new").num_valid_gt
+    table = KE.SplitTable(gt, dt)
+    assert KE.split_flags(table, 0, "kitti", 1)[2] == KE.split_flags(table, 0, "kitti", 1, "new")[2]
+    assert KE.HostStats(table).flags(0, "kitti", [1])[2].tolist() == KE.HostStats(table).flags(0, "kitti", [1], "new")[2].tolist()
     E = pkg("eval_rcnn")
     import inspect
     assert inspect.signature(E.evaluate_detections).parameters["metric"].default == "new"

@@ -1,6 +1,8 @@
-"""The split table of the device AP path and its two numpy definitions (kitti_eval.SplitTable, split_flags, thresholds_loop), the
-pair-cosine host entry, and -- with the host entries only -- that the helper split (ap_split.py) reaches every branch the GPU
-test is meant to pin: a GPU test shows nothing about a branch no input takes.  CPU; needs the built library."""
+"""The split table of both AP paths and its two numpy definitions (kitti_eval.SplitTable, split_flags, thresholds_loop), the
+pair-cosine host entry, the host path on that table (HostStats: its columns, its pr rows against the per-image definition, its
+eval_class against its own recorded output, PreparedGT), and -- with the host entries only -- that the helper split (ap_split.py)
+reaches every branch the GPU test is meant to pin: a GPU test shows nothing about a branch no input takes.  CPU; needs the built
+library."""
 import functools
 import os
 
@@ -166,3 +168,85 @@ def test_stats_device_cuda_without_a_device_raises_by_name(monkeypatch):
     with pytest.raises(ValueError, match="stats_device"):
         KE.get_official_eval_result(gt[:4], dt[:4], 0, stats_device="gpu")
     assert "stats_device" in R.evaluate_detections.__code__.co_varnames and "prepared_gt" in R.evaluate_detections.__code__.co_varnames
+
+
+# ---------------------------------------------------------------------------------------------------
+# the host path on the shared table (kitti_ap.HostStats)
+# ---------------------------------------------------------------------------------------------------
+def test_host_pr_is_the_image_order_sum_of_the_per_image_definition():
+    """Row t of a group's pr is the sum, in image order, of prcnn_kitti_image_stats at threshold t with the columns and flags that
+    ap_split.image_stats builds PER IMAGE from clean_data -- the check that does not go through the shared table.  tp / fp / fn are
+    added as doubles, the similarity only where it is not -1 (the rule of the library's pass-2 entry)."""
+    KE = pkg("kitti_eval")
+    gt, dt = helper_split()
+    hs = KE.HostStats(KE.SplitTable(gt, dt))
+    ov = [KE.image_box_overlap(d["bbox"], g["bbox"]) for g, d in zip(gt, dt)]
+    diffs, n_thr = [0, 1, 5], {}
+    for cls, level in ((0, 0.7), (1, 0.5), (2, 0.5)):
+        flags, lev = hs.flags(cls, "kitti", diffs, "new"), np.array([level])
+        thr = hs.thresholds(hs.scores(flags, hs.overlaps(0), 0, lev), flags[2])
+        pr = hs.pr(flags, hs.overlaps(0), 0, lev, thr, True)
+        for g, difficulty in enumerate(diffs):
+            want = np.zeros((len(thr[g]), 4))
+            for t, thresh in enumerate(thr[g]):
+                for i in range(len(gt)):
+                    tp, fp, fn, sim, _ = ap_split.image_stats(KE, gt[i], dt[i], ov[i], cls, difficulty, 0, level, thresh, 1, compute_aos=True)
+                    want[t, 0] += float(tp)
+                    want[t, 1] += float(fp)
+                    want[t, 2] += float(fn)
+                    if sim != -1:
+                        want[t, 3] += sim
+            assert pr[g].shape == want.shape and np.array_equal(pr[g], want), (cls, difficulty)
+            n_thr[(cls, difficulty)] = len(thr[g])
+    assert len(n_thr) == 9 and n_thr[(2, 0)] == 41 and n_thr[(2, 5)] == 0
+
+
+@pytest.mark.parametrize("which", ["g10", "helper"])
+def test_host_columns_are_the_per_image_concatenation(which):
+    KE = pkg("kitti_eval")
+    gt, dt = fixture_split() if which == "g10" else helper_split()
+    hs = KE.HostStats(KE.SplitTable(gt, dt))
+    cat = lambda parts, w: np.concatenate([np.asarray(p, dtype=np.float64).reshape(-1, w) for p in parts], 0)
+    want_gt = cat([np.concatenate([g["bbox"], g["alpha"][..., None]], 1) for g in gt], 5)                       # as image_stats builds them
+    want_dt = cat([np.concatenate([d["bbox"], d["alpha"][..., None], d["score"][..., None]], 1) for d in dt], 6)
+    dcs = [KE.clean_data(g, d, 0, "kitti", 0)[3] for g, d in zip(gt, dt)]
+    for got, want in ((hs.gt_datas, want_gt), (hs.dt_datas, want_dt), (hs.dontcares, cat(dcs, 4))):
+        assert got.dtype == np.float64 and got.flags["C_CONTIGUOUS"] and got.shape == want.shape and np.array_equal(got, want)
+    for got, want in ((hs.gt_nums, [len(g["name"]) for g in gt]), (hs.dt_nums, [len(d["name"]) for d in dt]), (hs.dc_nums, [len(x) for x in dcs])):
+        assert got.dtype == np.int64 and got.flags["C_CONTIGUOUS"] and got.tolist() == want
+    for annos in (gt, dt):
+        side = KE.SplitSide(annos)
+        bev = np.concatenate([KE._bev_boxes(a) for a in annos], 0).astype(np.float32)
+        assert side.bev.dtype == np.float32 and np.array_equal(side.bev, bev)
+        assert side.box3d.dtype == np.float64 and np.array_equal(side.box3d, np.concatenate([KE._d3_boxes(a) for a in annos], 0))
+        assert side.off32.dtype == np.int32 and np.array_equal(side.off32, side.off)
+
+
+@pytest.mark.parametrize("which", ["g10", "helper"])
+def test_host_eval_class_is_what_it_was(which, oracle):
+    """Against this project's own host output recorded before the host path moved onto the table (golden/make_golden_ap_host.py)"""
+    KE = pkg("kitti_eval")
+    gt, dt = fixture_split() if which == "g10" else helper_split()
+    z = np.load(os.path.join(HERE, "golden", "g25_ap_host_ref.npz"))
+    levels = np.array([[[0.7, 0.5, 0.5]] * 3, [[0.7, 0.5, 0.5], [0.5, 0.25, 0.25], [0.5, 0.25, 0.25]]])
+    ext_cpu = __import__("oracle.ext_cpu", fromlist=["x"])
+    for rule, dataset, diffs in (("new", "kitti", [0, 1, 2, 3, 4, 5]), ("old", "waymo", [0, 1, 2])):
+        for kind in (0, 1, 2):
+            with ext_cpu.patch_package():
+                r = KE.eval_class(gt, dt, [0, 1, 2], dataset, diffs, kind, levels, compute_aos=(kind == 0), difficulty_metric=rule)
+                assert KE.calculate_iou(dt[:2], gt[:2], 1)[0].dtype == np.float64                    # the rotated IoU runs without a GPU in here
+            want = z["%s_%s_%d" % (which, rule, kind)]
+            for c, key in enumerate(("precision", "recall", "orientation")):
+                assert r[key].shape == want[c].shape and np.array_equal(r[key], want[c], equal_nan=True), (rule, kind, key)
+            assert np.count_nonzero(want[0]) > 0
+
+
+def test_prepared_gt_serves_the_host_path(oracle):
+    KE = pkg("kitti_eval")
+    gt, dt = helper_split()
+    ext_cpu = __import__("oracle.ext_cpu", fromlist=["x"])
+    with ext_cpu.patch_package():
+        for kw in ({"metric": "new"}, {"metric": "old", "dataset": "waymo"}):
+            want, _ = KE.get_official_eval_result(gt, dt, [0, 1, 2], **kw)
+            text, _ = KE.get_official_eval_result(KE.PreparedGT(gt), dt, [0, 1, 2], **kw)
+            assert text == want and "aos" in want
