@@ -286,10 +286,14 @@ def rcnn_loss(cfg, ret_dict):
                   ret_dict["roi_boxes3d"] if spec.anchor_on_roi else None)
 
 
-def model_fn(cfg, model, data):
-    """The reference's model_fn for what this project runs: the RPN enabled and not fixed and / or the RCNN enabled with ROI_SAMPLE_JIT.
-    ``data`` holds tensors or numpy arrays (pts_input, gt_boxes3d, rpn_cls_label, rpn_reg_label with the RPN enabled; the RCNN stage's
-    inputs without it); they are moved to the model's device.  Glue: the two tb_dict() calls are its only host reads."""
+RPN_ROWS = ("rpn_cls", "rpn_reg", "rpn_cls_label", "rpn_reg_label")
+RCNN_ROWS = ("rcnn_cls", "rcnn_reg", "cls_label", "reg_valid_mask", "gt_of_rois", "roi_boxes3d")
+
+
+def forward_rows(cfg, model, data):
+    """The forward half of model_fn -> the rows the loss reads (RPN_ROWS and / or RCNN_ROWS), every one a tensor on the model's device
+    whose first dimension runs over the batch's rows.  ``data`` holds tensors or numpy arrays (pts_input, gt_boxes3d, rpn_cls_label,
+    rpn_reg_label with the RPN enabled; the RCNN stage's inputs without it); they are moved to the model's device."""
     import torch
     dev = next(model.parameters()).device
     to = lambda v, dtype=torch.float32: torch.as_tensor(v).to(device=dev, dtype=dtype)
@@ -303,16 +307,33 @@ def model_fn(cfg, model, data):
     else:
         input_data = {k: to(v).contiguous() for k, v in data.items() if k != "sample_id"}
     ret = model(input_data)
-    tb_dict, disp_dict, loss = {}, {}, 0
+    rows = {}
     if train_rpn:
-        res = rpn_loss(cfg, ret["rpn_cls"], ret["rpn_reg"], to(data["rpn_cls_label"], torch.int64), to(data["rpn_reg_label"]))
+        rows.update(rpn_cls=ret["rpn_cls"], rpn_reg=ret["rpn_reg"], rpn_cls_label=to(data["rpn_cls_label"], torch.int64),
+                    rpn_reg_label=to(data["rpn_reg_label"]))
+    if cfg.RCNN.ENABLED:
+        rows.update({k: ret[k] for k in RCNN_ROWS})
+    return rows
+
+
+def loss_of_rows(cfg, rows):
+    """The loss half of model_fn on forward_rows' dictionary -> ModelReturn.  Glue: the two tb_dict() calls are its only host reads."""
+    tb_dict, disp_dict, loss = {}, {}, 0
+    if "rpn_cls" in rows:
+        res = rpn_loss(cfg, rows["rpn_cls"], rows["rpn_reg"], rows["rpn_cls_label"], rows["rpn_reg_label"])
         tb_dict.update(res.tb_dict())
         disp_dict["rpn_loss"] = tb_dict["rpn_loss"]
         loss = loss + res.loss
-    if cfg.RCNN.ENABLED:
-        res = rcnn_loss(cfg, ret)
+    if "rcnn_cls" in rows:
+        res = rcnn_loss(cfg, rows)
         tb_dict.update(res.tb_dict())
         disp_dict["reg_fg_sum"] = tb_dict["rcnn_reg_fg"]
         loss = loss + res.loss
     disp_dict["loss"] = sum(tb_dict[k] for k in ("rpn_loss", "rcnn_loss") if k in tb_dict)
     return ModelReturn(loss, tb_dict, disp_dict)
+
+
+def model_fn(cfg, model, data):
+    """The reference's model_fn for what this project runs: the RPN enabled and not fixed and / or the RCNN enabled with ROI_SAMPLE_JIT;
+    forward_rows then loss_of_rows (data-parallel training gathers the rows over the ranks between the two: dist_train.py)."""
+    return loss_of_rows(cfg, forward_rows(cfg, model, data))

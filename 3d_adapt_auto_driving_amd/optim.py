@@ -27,6 +27,13 @@ CPU parameters run the checker, which is literally torch.nn.utils.clip_grad_norm
 torch.optim.Adam(foreach=False) driven as OptimWrapper drives them; it is not a second product path and neither path falls back to the
 other.  The checker also accepts f64 parameters (the tests take the rounding scale of an output from an f32 and an f64 run of it).
 
+OneCycleAdam(..., group=dist_train.ReplicaGroup) is the data-parallel step: the grads are SUMMED over the group's ranks before the step
+above, and the clip norm is the sum's.  CUDA: the table gains the columns ``src`` (the tensors' own grads) and ``slot_start``, its grad
+column points into one flat f32 bucket, and step() is prcnn_grad_pack (csrc/grad_bucket.hip, one launch) -> ONE all-reduce of the bucket
+-> the same three launches reading the reduced grads from the bucket; ``p.grad`` stays the rank's own, and the bucket and table are
+rebuilt only with the signature.  CPU: every ``p.grad`` is all-reduced in place before the checker's step.  A group that is not active
+(a world of 1) changes nothing.
+
 state_dict() has the layout torch.optim.Adam gives under the reference's wrapper -- two param_groups (non-BatchNorm, BatchNorm) with the
 installed Adam's keys, lr, betas = (mom, betas2), weight_decay = 0; state[i] = {step, exp_avg, exp_avg_sq} keyed by the parameter's
 index over both groups -- so a checkpoint written here resumes under the reference's load_checkpoint and the other way round.
@@ -109,9 +116,37 @@ def group_names(model):
     return [[name[id(p)] for p in g] for g in layer_groups(model)]
 
 
+# ---------------------------------------------------------------------------------------------------------------------- chunk table
+def chunks_of(numel, used):
+    """The per-chunk columns of csrc/optim.hip's table: numel (T,) i64, used (T,) bool -> (chunk_tensor i32, chunk_start i64); every
+    used tensor is cut into chunks of at most CHUNK consecutive elements, in tensor order"""
+    counts = np.where(used, (numel + CHUNK - 1) // CHUNK, 0)
+    first = np.cumsum(counts) - counts
+    chunk_tensor = np.repeat(np.arange(len(numel), dtype=np.int32), counts)
+    chunk_start = (np.arange(len(chunk_tensor), dtype=np.int64) - np.repeat(first, counts)) * CHUNK
+    return chunk_tensor, chunk_start
+
+
+def upload_sections(sections, device):
+    """[(name, array)] -> (ONE device byte buffer holding every array at an 8-byte aligned offset, {name: device address}): one upload"""
+    import torch
+    blob, offset = [], {}
+    at = 0
+    for name, a in sections:
+        raw = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+        pad = (-len(raw)) % 8
+        offset[name] = at
+        blob += [raw, np.zeros(pad, dtype=np.uint8)]
+        at += len(raw) + pad
+    buf = torch.from_numpy(np.concatenate(blob)).to(device)
+    base = buf.data_ptr()
+    return buf, {name: base + off for name, off in offset.items()}
+
+
 # ------------------------------------------------------------------------------------------------------------------------ optimizer
 class OneCycleAdam:
-    def __init__(self, model, total_steps, lr_max, moms, div_factor, pct_start, wd, grad_norm_clip, betas2=0.99, eps=1e-8, device=None):
+    def __init__(self, model, total_steps, lr_max, moms, div_factor, pct_start, wd, grad_norm_clip, betas2=0.99, eps=1e-8, device=None,
+                 group=None):
         import torch
         self.model = model
         self.total_steps, self.lr_max, self.moms = int(total_steps), float(lr_max), [float(m) for m in moms]
@@ -126,6 +161,8 @@ class OneCycleAdam:
         own = {id(p) for p in self.params}
         self._others = [p for p in model.parameters() if id(p) not in own]                       # clipped with the rest, never stepped
         self.device = torch.device(device) if device is not None else self.params[0].device
+        self.group = group if group is not None and group.active else None                       # dist_train.ReplicaGroup: grads are summed over its ranks
+        self._bucket, self._layout_checked, self.table_uploads = None, None, 0
         self._check()
         self.lr, self.mom = self.lr_max / self.div_factor, self.moms[0]
         self.steps_done = 0
@@ -175,6 +212,12 @@ class OneCycleAdam:
 
     def _step_cpu(self):
         from torch.nn.utils import clip_grad_norm_
+        if self.group is not None:                           # the checker's exchange: every grad summed over the ranks, in place
+            tensors = self.params + self._others
+            self._check_layout(tensors, [p.grad for p in tensors])
+            for p in tensors:
+                if p.grad is not None:
+                    self.group.all_reduce_bucket(p.grad)
         self.total_norm = clip_grad_norm_(self.params + self._others, self.grad_norm_clip)       # Trainer._train_it
         for g in self._adam.param_groups:                                                        # OptimWrapper.step, true_wd and bn_wd
             for p in g["params"]:
@@ -195,14 +238,44 @@ class OneCycleAdam:
             out.append(g if g is None or g.is_contiguous() else g.contiguous())
         return out
 
+    def _check_layout(self, tensors, grads):
+        """With a group: the set of tensors that have a grad must be the same on every rank (the ranks exchange slots of one layout); its
+        hash is all-gathered whenever it changes"""
+        layout = tuple((i, p.numel()) for i, (p, g) in enumerate(zip(tensors, grads)) if g is not None)
+        if layout != self._layout_checked:
+            self.group.check_layout(layout)
+            self._layout_checked = layout
+
+    def _build_bucket(self, tensors, grads):
+        """The flat f32 bucket of the tensors that have a grad (dist_train.bucket_layout; padding zeroed here and never written)
+        -> (slot_start (T,) i64, the bucket)"""
+        import torch
+        from .dist_train import bucket_layout
+        has = [i for i, g in enumerate(grads) if g is not None]
+        starts, total = bucket_layout([tensors[i].numel() for i in has])
+        slot_start = np.zeros(len(tensors), dtype=np.int64)
+        slot_start[has] = starts
+        if self._bucket is None or self._bucket.numel() != max(total, 1):
+            self._bucket = torch.zeros((max(total, 1),), dtype=torch.float32, device=self.device)
+        else:
+            self._bucket.zero_()                              # another layout of the same size: what was a slot may now be padding
+        return slot_start, self._bucket
+
     def _build_table(self, tensors, grads):
         """The chunk table of csrc/optim.hip as ONE device byte buffer (one upload): per tensor param / grad / exp_avg / exp_avg_sq
-        addresses, numel, step, flags; per chunk tensor index and start.  -> dict of section addresses, n_tensors, n_chunks"""
+        addresses, numel, step, flags; per chunk tensor index and start.  -> dict of section addresses, n_tensors, n_chunks.
+        With a group the grad column points into the bucket and two columns are added: src (the tensors' own grads) and slot_start."""
         import torch
         n_own = len(self.params)
         T = len(tensors)
         addr = np.zeros((4, T), dtype=np.uint64)
         numel = np.array([p.numel() for p in tensors], dtype=np.int64)
+        extra = []
+        if self.group is not None:
+            slot_start, bucket = self._build_bucket(tensors, grads)
+            src = np.array([0 if g is None else g.data_ptr() for g in grads], dtype=np.uint64)
+            extra = [("src", src), ("slot_start", slot_start)]
+            grads = [None if g is None else bucket[int(s):int(s) + g.numel()] for g, s in zip(grads, slot_start)]
         flags, steps = np.zeros(T, dtype=np.uint8), np.zeros(T, dtype=np.int32)
         for i, (p, g) in enumerate(zip(tensors, grads)):
             addr[0, i] = p.data_ptr()
@@ -217,24 +290,12 @@ class OneCycleAdam:
                     flags[i] |= FLAG_ADAM
                     addr[2, i], addr[3, i], steps[i] = st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), st["step"]
         used = (flags != 0) | (addr[1] != 0)
-        counts = np.where(used, (numel + CHUNK - 1) // CHUNK, 0)
-        first = np.cumsum(counts) - counts
-        chunk_tensor = np.repeat(np.arange(T, dtype=np.int32), counts)
-        chunk_start = (np.arange(len(chunk_tensor), dtype=np.int64) - np.repeat(first, counts)) * CHUNK
+        chunk_tensor, chunk_start = chunks_of(numel, used)
         sections = [("param", addr[0]), ("grad", addr[1]), ("exp_avg", addr[2]), ("exp_avg_sq", addr[3]), ("numel", numel),
-                    ("chunk_start", chunk_start), ("steps", steps), ("chunk_tensor", chunk_tensor), ("flags", flags)]   # 8-byte columns first
-        blob, offset = [], {}
-        at = 0
-        for name, a in sections:
-            raw = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
-            pad = (-len(raw)) % 8
-            offset[name] = at
-            blob += [raw, np.zeros(pad, dtype=np.uint8)]
-            at += len(raw) + pad
-        buf = torch.from_numpy(np.concatenate(blob)).to(self.device)
-        base = buf.data_ptr()
-        return {"buf": buf, "n_tensors": T, "n_chunks": int(len(chunk_tensor)), "adam": np.nonzero(flags & FLAG_ADAM)[0],
-                **{name: base + off for name, off in offset.items()}}
+                    ("chunk_start", chunk_start)] + extra + [("steps", steps), ("chunk_tensor", chunk_tensor), ("flags", flags)]   # 8-byte columns first
+        buf, at = upload_sections(sections, self.device)
+        self.table_uploads += 1
+        return {"buf": buf, "n_tensors": T, "n_chunks": int(len(chunk_tensor)), "adam": np.nonzero(flags & FLAG_ADAM)[0], **at}
 
     def _step_device(self):
         import torch
@@ -242,6 +303,8 @@ class OneCycleAdam:
         grads = self._grads()
         signature = tuple((p.data_ptr(), p.requires_grad, None if g is None else g.data_ptr()) for p, g in zip(tensors, grads))
         if signature != self._signature:
+            if self.group is not None:
+                self._check_layout(tensors, grads)
             self._table = self._build_table(tensors, grads)
             need = _lib.call("prcnn_optim_workspace", self._table["n_chunks"])
             if self._work is None or self._work.numel() < need:
@@ -254,6 +317,10 @@ class OneCycleAdam:
             return
         stream = C.c_void_p(_lib.current_stream(self._work))
         nt, nc, work = t["n_tensors"], t["n_chunks"], self._work.data_ptr()
+        if self.group is not None:                            # the table's grad column points into the bucket: pack, one exchange, then the step
+            _lib.call("prcnn_grad_pack", t["src"], t["numel"], t["slot_start"], t["chunk_tensor"], t["chunk_start"], nt, nc,
+                      self._bucket.data_ptr(), self._bucket.numel(), stream)
+            self.group.all_reduce_bucket(self._bucket)
         _lib.call("prcnn_optim_sumsq", t["grad"], t["numel"], t["chunk_tensor"], t["chunk_start"], nt, nc, work, stream)
         _lib.call("prcnn_optim_finish", t["flags"], t["steps"], nt, nc, self.grad_norm_clip, work, stream)
         _lib.call("prcnn_optim_update", t["param"], t["grad"], t["exp_avg"], t["exp_avg_sq"], t["numel"], t["flags"], t["steps"], t["chunk_tensor"],

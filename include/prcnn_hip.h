@@ -1080,6 +1080,20 @@ int prcnn_optim_update(const unsigned long long *param_addr, const unsigned long
                        const int *chunk_tensor, const long long *chunk_start, int n_tensors, int n_chunks, double lr, double beta1,
                        double beta2, double eps, double wd, const double *work, void *stream);
 
+/* Data-parallel training's two kernels over the same chunk table with one more per-tensor column (csrc/grad_bucket.hip, dist_train.py):
+ * slot_start (n_tensors) i64, the tensor's first element in a flat layout whose slots are in table order and start at multiples of
+ * PRCNN_BUCKET_ALIGN elements (dist_train.bucket_layout).  Device pointers; a tensor whose address is 0 has no slot and is skipped.
+ * prcnn_grad_pack: bucket[slot_start[t] + j] = src[t][j] for every tensor, in ONE launch; src addresses of contiguous f32 data that need
+ *   not be 16-byte aligned, bucket 16-byte aligned with bucket_numel elements; a chunk that would end past bucket_numel writes nothing;
+ *   the padding between slots is never written.
+ * prcnn_param_digest: work[0] = sum over every element of bits(p[j]) * (2 (slot_start[t] + j) + 1) mod 2^64, bits the element's 32 bits as
+ *   an unsigned integer; work holds 1 + n_chunks words (work[1 + chunk] are the per-chunk partials).  Integers only. */
+enum { PRCNN_BUCKET_ALIGN = 64 };
+int prcnn_grad_pack(const unsigned long long *src_addr, const long long *numel, const long long *slot_start, const int *chunk_tensor,
+                    const long long *chunk_start, int n_tensors, int n_chunks, float *bucket, long long bucket_numel, void *stream);
+int prcnn_param_digest(const unsigned long long *param_addr, const long long *numel, const long long *slot_start, const int *chunk_tensor,
+                       const long long *chunk_start, int n_tensors, int n_chunks, unsigned long long *work, void *stream);
+
 /* Road-plane estimation for a batch of ragged LiDAR sweeps (csrc/road_planes.hip, road_planes.py): candidates in
  * the x / z range compacted in point order, RANSAC over host-drawn triples, two least-squares refits, the final inlier count and rms,
  * all in ONE call with no host read inside.  Device pointers.  pt_off / tile_off (n_scenes + 1) i32 and velo (sum n, 4) f32 as in
