@@ -566,6 +566,9 @@ def build_parser():
                     help="--ap_metric old: whose focal length scales the 40 / 25 / 25 px height caps")
     ap.add_argument("--ap_stats_device", type=str, default="cpu", choices=["cpu", "cuda"],
                     help="--eval_ap: flags, matching and PR sums on the host (default) or on the GPU; the same numbers")
+    ap.add_argument("--ap_parse_device", type=str, default=None, choices=["cuda", "cpu"],
+                    help="--eval_ap: parse the scenes' result texts (and a tree's label files) in one call on the GPU (cuda) or by its "
+                         "Python checker (cpu) instead of the host parser (default); the same numbers")
     ap.add_argument("--recall", action="store_true", help="RoI / refined-box recall vs the ground truth (the reference's statistics without --test)")
     ap.add_argument("--save_result", action="store_true", help="--eval_mode rpn: write detections/data and seg_result")
     ap.add_argument("--save_rpn_feature", action="store_true", help="--eval_mode rpn: also write the backbone features (features/)")
@@ -658,7 +661,8 @@ def evaluate_model(args, model, cfg, device, source, my_ids, rank, output_dir, r
             t1 = time.perf_counter()
             text, ap = evaluate_detections(table, counts, labels if labels is not None else source, dataset=args.ap_dataset,
                                            device_id=device.index or 0, metric=args.ap_metric,
-                                           stats_device=getattr(args, "ap_stats_device", "cpu"), prepared_gt=prepared_gt)
+                                           stats_device=getattr(args, "ap_stats_device", "cpu"), prepared_gt=prepared_gt,
+                                           parse_device=getattr(args, "ap_parse_device", None))
             timings["ap"] = time.perf_counter() - t1
             res["ap"] = ap
             print(text)

@@ -156,7 +156,8 @@ def sweep(args, model, cfg, device, source, my_ids, rank=0, world=1):
         labels = _LabelCache(source)
         prepared_gt = None             # the device AP path: the labels' half of the split table, built once for every checkpoint
         if rank == 0 and args.eval_ap and args.eval_mode != "rpn" and getattr(args, "ap_stats_device", "cpu") == "cuda":
-            prepared_gt = E.prepare_gt(labels, sorted(source.ids))
+            prepared_gt = E.prepare_gt(labels, sorted(source.ids), parse_device=getattr(args, "ap_parse_device", None),
+                                       device_id=device.index or 0)
         runner = None
         failed = {}                    # path -> modification time at the failed attempt: tried again only once the file has changed
         clock = time.perf_counter

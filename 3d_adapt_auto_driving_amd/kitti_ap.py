@@ -121,11 +121,11 @@ def thresholds_loop(sorted_scores, num_gt, num_sample_pts=N_SAMPLE_PTS):
 class SplitTable:
     """Both sides of a split and what pairs them: per-image offsets of ground truth, detections, DontCare rows and (n_dt x n_gt)
     pair blocks; ``dc_rows``: the ground-truth rows named DontCare, in order.  Built in whole-array numpy, once per evaluation,
-    for either backend; ``gt_annos`` may be a PreparedGT."""
+    for either backend; ``gt_annos`` may be a PreparedGT, and either side a SplitSide (kitti_annos.parse_texts makes one)."""
 
     def __init__(self, gt_annos, dt_annos):
-        self.gt = gt_annos.side if isinstance(gt_annos, PreparedGT) else SplitSide(gt_annos)
-        self.dt = SplitSide(dt_annos)
+        self.gt = gt_annos.side if isinstance(gt_annos, PreparedGT) else gt_annos if isinstance(gt_annos, SplitSide) else SplitSide(gt_annos)
+        self.dt = dt_annos if isinstance(dt_annos, SplitSide) else SplitSide(dt_annos)
         if self.gt.n_img != self.dt.n_img:
             raise ValueError("SplitTable: %d label images but %d detection images" % (self.gt.n_img, self.dt.n_img))
         self.n_img = self.gt.n_img

@@ -5,6 +5,7 @@ import io
 
 import numpy as np
 
+from .kitti_annos import SplitSide, _check_parse_device, parse_texts
 from .kitti_ap import CLASS_TO_NAME, DeviceStats, HostStats, SplitTable, _difficulties
 
 
@@ -13,8 +14,19 @@ def _check_stats_device(stats_device):
         raise ValueError("stats_device %r is neither 'cpu' nor 'cuda'" % (stats_device,))
 
 
-def _backend(gt_annos, dt_annos, stats_device, device_id):
+def _sides(gt_annos, dt_annos, parse_device, device_id):
+    """``parse_device`` of the entry points below: a side given as TEXTS (one str / bytes per image, a file's content each) is parsed
+    by kitti_annos.parse_texts on that device -> its SplitSide; annotation dicts, a SplitSide or a PreparedGT pass as they are"""
+    _check_parse_device(parse_device)
+    texts = lambda side: isinstance(side, (list, tuple)) and len(side) > 0 and all(isinstance(t, (str, bytes)) for t in side)
+    if parse_device is None:
+        return gt_annos, dt_annos
+    return tuple(parse_texts(side, parse_device, device_id=device_id) if texts(side) else side for side in (gt_annos, dt_annos))
+
+
+def _backend(gt_annos, dt_annos, stats_device, device_id, parse_device=None):
     _check_stats_device(stats_device)
+    gt_annos, dt_annos = _sides(gt_annos, dt_annos, parse_device, device_id)
     return (DeviceStats if stats_device == "cuda" else HostStats)(SplitTable(gt_annos, dt_annos), device_id)
 
 
@@ -35,15 +47,15 @@ def _fill_curves(precision, recall, aos, pr, compute_aos):
 
 
 def eval_class(gt_annos, dt_annos, current_classes, dataset, difficultys, metric, min_overlaps, compute_aos=False,
-               device_id=0, overlaps=None, difficulty_metric="new", stats_device="cpu", split=None):
+               device_id=0, overlaps=None, difficulty_metric="new", stats_device="cpu", split=None, parse_device=None):
     """-> dict(recall, precision, orientation), each [num_class, num_difficulty, num_minoverlap, 41]
     (eval2.py:460-569).  min_overlaps: [num_minoverlap, metric, num_class].  ``metric`` is the overlap kind (0 image box / 1 BEV /
     2 3D) as in the reference; the difficulty rule ("new" | "old", the ``metric`` keyword everywhere else) is ``difficulty_metric``.
     stats_device "cpu": the host entries of csrc/kitti_stats.hip; "cuda": flags, overlaps, both passes, thresholds and sums on the
     device (csrc/kitti_ap.hip) with one read at the end -- the same bits.  ``split``: a HostStats / DeviceStats of these
-    annotations to reuse; when given, IT is the backend and stats_device / device_id are not looked at."""
+    annotations to reuse; when given, IT is the backend and stats_device / device_id are not looked at.  ``parse_device``: _sides."""
     if split is None:
-        split = _backend(gt_annos, dt_annos, stats_device, device_id)
+        split = _backend(gt_annos, dt_annos, stats_device, device_id, parse_device)
     pr, n_thr = split.eval_class(current_classes, dataset, difficultys, metric, min_overlaps, compute_aos, overlaps, difficulty_metric)
     precision, recall, aos = np.zeros(pr.shape[:4]), np.zeros(pr.shape[:4]), np.zeros(pr.shape[:4])
     for m, l, k in np.ndindex(*n_thr.shape):
@@ -57,10 +69,11 @@ def get_mAP(prec):
     return np.cumsum(prec[..., ::4], axis=-1)[..., -1] / 11 * 100
 
 
-def do_eval(gt_annos, dt_annos, current_classes, dataset, min_overlaps, compute_aos=False, device_id=0, metric="new", stats_device="cpu"):
+def do_eval(gt_annos, dt_annos, current_classes, dataset, min_overlaps, compute_aos=False, device_id=0, metric="new", stats_device="cpu",
+            parse_device=None):
     difficultys = _difficulties(metric)
     # either path builds the split table (and its uploads) once; the three overlap kinds share it and the flags
-    more = {"difficulty_metric": metric, "split": _backend(gt_annos, dt_annos, stats_device, device_id)}
+    more = {"difficulty_metric": metric, "split": _backend(gt_annos, dt_annos, stats_device, device_id, parse_device)}
     ret = eval_class(gt_annos, dt_annos, current_classes, dataset, difficultys, 0, min_overlaps, compute_aos, **more)
     mAP_bbox = get_mAP(ret["precision"])
     mAP_aos = get_mAP(ret["orientation"]) if compute_aos else None
@@ -83,6 +96,8 @@ def _class_ids(current_classes):
 
 
 def _alpha_is_valid(dt_annos):
+    if isinstance(dt_annos, SplitSide):                # the first row of the first image that has one
+        return bool(len(dt_annos) and dt_annos.alpha[0] != -10)
     for anno in dt_annos:
         if anno["alpha"].shape[0] != 0:
             return bool(anno["alpha"][0] != -10)
@@ -90,9 +105,10 @@ def _alpha_is_valid(dt_annos):
 
 
 def get_official_eval_result(gt_annos, dt_annos, current_classes, dataset="kitti", dense_sample=False, device_id=0, metric="new",
-                             stats_device="cpu"):
+                             stats_device="cpu", parse_device=None):
     """-> (result text, dict) in the reference's format (eval2.py:629-722; metric="old": eval_old.py:619-695, three numbers per
-    line and no dense sampling)."""
+    line and no dense sampling).  ``parse_device``: _sides."""
+    gt_annos, dt_annos = _sides(gt_annos, dt_annos, parse_device, device_id)
     overlap_0_7 = np.array([[0.7, 0.5, 0.5, 0.7, 0.5], [0.7, 0.5, 0.5, 0.7, 0.5], [0.7, 0.5, 0.5, 0.7, 0.5]])
     overlap_0_5 = np.array([[0.7, 0.5, 0.5, 0.7, 0.5], [0.5, 0.25, 0.25, 0.5, 0.25], [0.5, 0.25, 0.25, 0.5, 0.25]])
     extra = []
@@ -130,7 +146,7 @@ COCO_RANGE = {0: [0.5, 0.95, 10], 1: [0.25, 0.7, 10], 2: [0.25, 0.7, 10], 3: [0.
 
 
 def do_coco_style_eval(gt_annos, dt_annos, current_classes, overlap_ranges, compute_aos, dataset="kitti", device_id=0, metric="new",
-                       stats_device="cpu"):
+                       stats_device="cpu", parse_device=None):
     """mAP averaged over ten overlap thresholds (eval2.py:611-626).  overlap_ranges: [lo / hi / count, overlap kind, num_class].
     The reference's call of do_eval is one argument short since ``dataset`` joined its signature; this passes it."""
     min_overlaps = np.zeros([10, *overlap_ranges.shape[1:]])
@@ -139,12 +155,14 @@ def do_coco_style_eval(gt_annos, dt_annos, current_classes, overlap_ranges, comp
             lo, hi, num = overlap_ranges[:, i, j]
             min_overlaps[:, i, j] = np.linspace(lo, hi, int(num))
     mAP_bbox, mAP_bev, mAP_3d, mAP_aos = do_eval(gt_annos, dt_annos, current_classes, dataset, min_overlaps, compute_aos, device_id,
-                                                 metric, stats_device)
+                                                 metric, stats_device, parse_device)
     return mAP_bbox.mean(-1), mAP_bev.mean(-1), mAP_3d.mean(-1), None if mAP_aos is None else mAP_aos.mean(-1)
 
 
-def get_coco_eval_result(gt_annos, dt_annos, current_classes, dataset="kitti", device_id=0, metric="new", stats_device="cpu"):
-    """-> result text (eval2.py:725-784): three numbers per line for either metric."""
+def get_coco_eval_result(gt_annos, dt_annos, current_classes, dataset="kitti", device_id=0, metric="new", stats_device="cpu",
+                         parse_device=None):
+    """-> result text (eval2.py:725-784): three numbers per line for either metric.  ``parse_device``: _sides."""
+    gt_annos, dt_annos = _sides(gt_annos, dt_annos, parse_device, device_id)
     current_classes = _class_ids(current_classes)
     overlap_ranges = np.zeros([3, 3, len(current_classes)])
     for i, curcls in enumerate(current_classes):

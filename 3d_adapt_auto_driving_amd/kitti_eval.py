@@ -29,17 +29,21 @@ Both statistic paths read one table of the split's columns (SplitTable) and run 
 matching passes, thresholds and PR sums.  ``stats_device="cpu"`` (the default) is HostStats, the host entries above;
 ``stats_device="cuda"`` is DeviceStats, kernels of csrc/kitti_ap.hip with one read at the end.  Both give the same bits.
 
+The table's columns come from annotation dicts (the host parser, one Python float() per token: the definition) or, with
+``parse_device``, straight from the files' text (kitti_annos.parse_texts: csrc/kitti_parse.hip, or its Python checker) -- the same bits;
+a file outside the parser's grammar is read by the host parser.
+
 This module is the driver and the command line.  The parts: kitti_annos.py (label files, annotation dicts, their columns),
 kitti_overlaps.py (the three overlap kinds, best match), kitti_ap.py (protocol, table, the two backends), kitti_ap_result.py
 (curves, mAP, result texts), kitti_transforms.py (the output transformations).  Every name of theirs is reachable here.
 
-Command line:  python -m 3d_adapt_auto_driving_amd.kitti_eval --result_path ... --dataset_path ... [--metric old] [--align_size] [--stats_device cuda] ...
+Command line:  python -m 3d_adapt_auto_driving_amd.kitti_eval --result_path ... --dataset_path ... [--metric old] [--align_size] [--stats_device cuda] [--parse_device cuda] ...
 """
 import os
 
 from . import _lib
-from .kitti_annos import (CLASS_CODE, PreparedGT, SplitSide, _bev_boxes, _d3_boxes, annos_from_lines, filter_annos_low_score, get_label_anno,
-                          get_label_annos, save_labels, to_kitti_format)
+from .kitti_annos import (CLASS_CODE, ParseDeviceError, PreparedGT, SplitSide, _bev_boxes, _check_parse_device, _d3_boxes, annos_from_lines,
+                          filter_annos_low_score, get_label_anno, get_label_annos, parse_texts, read_texts, save_labels, to_kitti_format)
 from .kitti_overlaps import best_match, calculate_iou, image_box_overlap, rotate_iou_segmented
 from .kitti_ap import (CLASS_NAMES, CLASS_TO_NAME, DIST_BOUNDARY, FOCAL, MAX_OCCLUSION, MAX_TRUNCATION, N_SAMPLE_PTS, OLD_MAX_OCCLUSION,
                        OLD_MAX_TRUNCATION, REG_DETS, SIBLING_CODE, DeviceStats, HostStats, SplitTable, StatsDeviceError, clean_data,
@@ -57,18 +61,28 @@ _TRANSFORMS = {"rescale_pred": rescale_pred, "align_size": align_size, "align_fr
 def evaluate(result_path, label_path, image_ids, current_class=0, dataset="kitti", score_thresh=-1, device_id=0, metric="new",
              coco=False, toground=False, rescale_pred=None, align_size=False, align_front=False, reverse_align=False,
              dense_sample=False, direct_save=False, output_iou=False, adapted=False, planes_path=None, src_stats=None,
-             dst_stats=None, scale_map="regular", device="cuda", stats_device="cpu"):
+             dst_stats=None, scale_map="regular", device="cuda", stats_device="cpu", parse_device=None):
     """Result folder + label folder + id list -> (result text, dict); the text alone with ``coco``; None with ``output_iou``
     (evaluate.py:84-275, the switches in the reference's order of application).  The transformed labels go where the reference
     puts them: grounded/, align_size/, align_front/, reverse_align/, with_iou/, with_iou_gt/ beside the result folder.
     planes_path defaults to <label folder>/../planes; reverse_align reads its two statistics from src_stats / dst_stats.
     ``device`` selects how best matches and alignment are computed ("cuda": csrc/eval_match.hip, "cpu": numpy); ``stats_device`` where
-    the AP statistics run ("cpu": csrc/kitti_stats.hip's host entries, "cuda": csrc/kitti_ap.hip)."""
+    the AP statistics run ("cpu": csrc/kitti_stats.hip's host entries, "cuda": csrc/kitti_ap.hip).  ``parse_device``: None reads both
+    folders with the host parser; "cuda" / "cpu" read them through kitti_annos.parse_texts (csrc/kitti_parse.hip / its Python checker)
+    -- the same annotations; the statistics then take the parsed columns as they are, a transformation takes the dicts built from them."""
     _check_stats_device(stats_device)
+    _check_parse_device(parse_device)
     g = _TRANSFORMS
     image_ids = list(image_ids)
     parent = os.path.dirname(result_path)
-    dt_annos = get_label_annos(result_path, image_ids)
+    plain = not (score_thresh > 0 or toground or rescale_pred is not None or output_iou or align_size or align_front or reverse_align)
+
+    def read(folder):
+        if parse_device is None:
+            return get_label_annos(folder, image_ids)
+        side = parse_texts(read_texts(folder, image_ids), parse_device, device_id=device_id)
+        return side if plain else side.annos
+    dt_annos = read(result_path)
     if score_thresh > 0:
         dt_annos = filter_annos_low_score(dt_annos, score_thresh)
     if toground:
@@ -76,7 +90,7 @@ def evaluate(result_path, label_path, image_ids, current_class=0, dataset="kitti
         save_labels(dt_annos, os.path.join(parent, "grounded"), image_ids)
     if rescale_pred is not None:
         dt_annos = g["rescale_pred"](dt_annos, rescale_pred)
-    gt_annos = get_label_annos(label_path, image_ids)
+    gt_annos = read(label_path)
     if output_iou:
         write_with_iou(dt_annos, gt_annos, parent, image_ids, device, device_id)
     if align_size:
@@ -132,6 +146,9 @@ def main(argv=None):
     ap.add_argument("--device", type=str, default="cuda", choices=["cuda", "cpu"], help="best match / alignment: fused HIP launch or numpy")
     ap.add_argument("--stats_device", type=str, default="cpu", choices=["cpu", "cuda"],
                     help="AP statistics (flags, matching, PR sums): host entries or the device kernels; the same numbers")
+    ap.add_argument("--parse_device", type=str, default=None, choices=["cuda", "cpu"],
+                    help="read the label and result files through the text parser on the GPU (cuda) or its Python checker (cpu); "
+                         "default: the host parser; the same numbers")
     args = vars(ap.parse_args(argv))
     dataset_path = args.pop("dataset_path")
     split_file, label_path = args.pop("label_split_file"), args.pop("label_path")

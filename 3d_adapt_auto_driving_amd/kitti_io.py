@@ -160,9 +160,13 @@ class KittiSource:
     def calib_and_shape(self, idx):
         return Calibration(os.path.join(self.dir, "calib", "%06d.txt" % idx)), self.image_shape(idx)
 
+    def label_file(self, idx):
+        """Path of a scene's label_2 file (what the text parser reads instead of label_lines)."""
+        return os.path.join(self.dir, "label_2", "%06d.txt" % idx)
+
     def label_lines(self, idx):
         """Ground-truth label_2 lines of a scene (for the AP evaluator)."""
-        with open(os.path.join(self.dir, "label_2", "%06d.txt" % idx)) as f:
+        with open(self.label_file(idx)) as f:
             return [l for l in f.read().split("\n") if l.strip()]
 
     def gt_boxes3d(self, idx, train_mode=False):

@@ -51,35 +51,57 @@ def save_kitti_format(sample_id, calib, bbox3d, kitti_output_dir, scores, img_sh
     return text.count("\n")
 
 
-def detections_to_annos(table, counts, source, cls_name="Car"):
+def detections_to_annos(table, counts, source, cls_name="Car", parse_device=None, device_id=0):
     """Gathered detection table [S, M, 9] (+ counts) -> (scene ids, KITTI annotation dicts), through the same
-    %.4f text form the result files carry, so the in-memory AP equals the AP of the written files."""
+    %.4f text form the result files carry, so the in-memory AP equals the AP of the written files.  With ``parse_device`` the scenes'
+    texts are parsed in ONE call of kitti_annos.parse_texts and the second item is its SplitSide (``.annos``: the same dicts)."""
     from . import kitti_eval
+    kitti_eval._check_parse_device(parse_device)
     ids, annos = [], []
     tb, ct = table.numpy(), counts.numpy()
     for s in np.argsort(tb[:, 0, 8], kind="stable"):
         sid, n = int(tb[s, 0, 8]), int(ct[s])
         calib, shape = source.calib_and_shape(sid)
         ids.append(sid)
-        annos.append(kitti_eval.annos_from_lines(kitti_result_lines(calib, tb[s, :n, 0:7], tb[s, :n, 7], shape, cls_name)))
+        if parse_device is None:
+            annos.append(kitti_eval.annos_from_lines(kitti_result_lines(calib, tb[s, :n, 0:7], tb[s, :n, 7], shape, cls_name)))
+        else:
+            annos.append(kitti_result_text(calib, tb[s, :n, 0:7], tb[s, :n, 7], shape, cls_name))
+    if parse_device is not None:
+        return ids, kitti_eval.parse_texts(annos, parse_device, skip_blank=True, device_id=device_id)
     return ids, annos
 
 
-def prepare_gt(source, ids):
+def _gt_annos(source, ids, parse_device, device_id):
+    """The labels of scenes ``ids``: annotation dicts by the host parser, or with ``parse_device`` and a source over label FILES
+    (``label_file(id)``) their parsed SplitSide; a source that makes its label lines keeps the host parser."""
+    from . import kitti_eval
+    kitti_eval._check_parse_device(parse_device)
+    label_file = getattr(source, "label_file", None)
+    if parse_device is None or label_file is None:
+        return [kitti_eval.annos_from_lines(source.label_lines(i)) for i in ids]
+    def read(i):
+        with open(label_file(i), "rb") as f:
+            return f.read()
+    return kitti_eval.parse_texts([read(i) for i in ids], parse_device, skip_blank=True, device_id=device_id)
+
+
+def prepare_gt(source, ids, parse_device=None, device_id=0):
     """The labels of scenes ``ids`` (in that order) parsed and tabulated once, for evaluate_detections(prepared_gt=...)."""
     from . import kitti_eval
-    return kitti_eval.PreparedGT([kitti_eval.annos_from_lines(source.label_lines(i)) for i in ids], ids)
+    return kitti_eval.PreparedGT(_gt_annos(source, ids, parse_device, device_id), ids)
 
 
 def evaluate_detections(table, counts, source, current_class=0, dataset="kitti", device_id=0, metric="new", stats_device="cpu",
-                        prepared_gt=None):
+                        prepared_gt=None, parse_device=None):
     """Rank-0 tail of the sharded evaluation: AP of the gathered detections against the source's labels
     (tools/eval_rcnn.py:706-713 -> evaluate/evaluate.py).  Returns (result text, dict).  stats_device: where the AP statistics run
-    (kitti_eval.eval_class); prepared_gt: prepare_gt(source, ids) of the same scenes, instead of parsing the labels again."""
+    (kitti_eval.eval_class); prepared_gt: prepare_gt(source, ids) of the same scenes, instead of parsing the labels again;
+    parse_device: None for the host parser, "cuda" / "cpu" for kitti_annos.parse_texts over the scenes' result texts in one call."""
     from . import kitti_eval
-    ids, dt_annos = detections_to_annos(table, counts, source)
+    ids, dt_annos = detections_to_annos(table, counts, source, parse_device=parse_device, device_id=device_id)
     if prepared_gt is None:
-        gt_annos = [kitti_eval.annos_from_lines(source.label_lines(i)) for i in ids]
+        gt_annos = _gt_annos(source, ids, parse_device, device_id)
     elif prepared_gt.ids != ids:
         raise ValueError("evaluate_detections: prepared_gt was made for other scenes than the gathered table holds")
     else:

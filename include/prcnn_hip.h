@@ -818,6 +818,39 @@ int prcnn_ap_pr(const long long *split, const char *ignored_gt, const char *igno
                 const double *pair_cos, unsigned long long *counts, double *sim_img, double *pr,
                 unsigned long long *workspace, long long workspace_words, void *stream);
 
+/* ---- evaluate/kitti_common.py:306-360: the label / result TEXT of one split side to columns (csrc/kitti_parse.hip; DEVICE pointers) ----
+ *
+ * text (n_bytes <= PRCNN_PARSE_MAX_BYTES) holds the bytes of all files, one behind the other; file_off (n_files + 1) i64.  A line is
+ * what readlines() yields, stripped of spaces at both ends.  A file is REGULAR when it is empty or every line of it has the same
+ * 15 or 16 tokens divided by single spaces, every byte is '\n', a space or 0x21 .. 0x7e, token 2 is [+-]?[0-9]{1,15} and tokens 1,
+ * 3 .. 15 are [+-]?([0-9]+(\.[0-9]*)?|\.[0-9]+)([eE][+-]?[0-9]{1,9})? with at most 15 digits from the first non-zero one to the
+ * last one written and |k| <= 22, k = exponent - fraction digits.  Such a token's value is the digits as an integer w times 10^k
+ * (k >= 0) or over 10^-k: one correctly rounded f64 operation on exact operands, sign last -- Python's float(token), bit for bit.
+ * Every other file is FLAGGED, its rows are not to be used, and the host parser reads it.  With skip_blank a line of spaces
+ * alone is a row with row_tok 0 that the caller drops; without, it flags its file.
+ * Columns of a row, in f64: */
+enum { PRCNN_PARSE_OCCLUDED = 0, PRCNN_PARSE_TRUNCATED, PRCNN_PARSE_ALPHA, PRCNN_PARSE_BBOX, PRCNN_PARSE_LOCATION = 7,
+       PRCNN_PARSE_DIMENSIONS = 10 /* l, h, w from file order h, w, l */, PRCNN_PARSE_ROTATION_Y = 13,
+       PRCNN_PARSE_SCORE /* 0 in a 15-token row */, PRCNN_PARSE_COLS };
+enum { PRCNN_PARSE_CHUNK = 4096, PRCNN_PARSE_MAX_BYTES = 2147483647 };
+/* file_flag bits; a file is regular when its word is 0 (no row), PRCNN_PARSE_SAW15 or PRCNN_PARSE_SAW16 */
+enum { PRCNN_PARSE_SAW15 = 1, PRCNN_PARSE_SAW16 = 2, PRCNN_PARSE_BAD = 4 };
+
+/* Scan: -> row_off (n_files + 1) i64, the lines of the files as prefix sums (the caller reads them back: row_off[n_files] sizes the
+ * outputs of prcnn_kitti_parse_rows).  Scratch that the second call reads again: start_flag (n_bytes) u8 and chunk_rows
+ * (ceil(n_bytes / PRCNN_PARSE_CHUNK) + 1) i32. */
+int prcnn_kitti_parse_scan(long long n_bytes, int n_files, const unsigned char *text, const long long *file_off,
+                           unsigned char *start_flag, int *chunk_rows, long long *row_off, void *stream);
+
+/* Parse: n_rows = row_off[n_files].  -> row_start (n_rows) i32 scratch; vals (n_rows, PRCNN_PARSE_COLS) f64; name_span (n_rows, 2) i32 =
+ * offset in text and length of the name token; code (n_rows) i8 class code of the lower-cased name (the split table's codes);
+ * is_dc (n_rows) u8: the name is exactly "DontCare"; row_tok (n_rows) u8: 15, 16, or 0 for a row that is blank or not regular
+ * (its other columns are zero); file_flag (n_files) i32 (cleared here). */
+int prcnn_kitti_parse_rows(long long n_bytes, int n_files, long long n_rows, int skip_blank, const unsigned char *text,
+                           const long long *file_off, const unsigned char *start_flag, const int *chunk_rows,
+                           const long long *row_off, int *row_start, double *vals, int *name_span, char *code,
+                           unsigned char *is_dc, unsigned char *row_tok, int *file_flag, void *stream);
+
 /* Statistical normalization (stat_norm/norm.py:186-330 rescale_ptc) over a batch of ragged scenes (csrc/stat_norm.hip).
  * Device pointers; offsets are prefix sums over the scenes (n_scenes + 1 entries).  Points: velo (sum n, 4) f32 raw .bin rows,
  * pt_off; 64-point tiles: tile_off; rescaled boxes: box_off, boxd (n_box, PRCNN_SN_BOXD) f64 records, boxi (n_box, PRCNN_SN_BOXI) i32 state (zeroed),
