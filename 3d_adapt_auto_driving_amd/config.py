@@ -82,7 +82,10 @@ _LIBRARY_DEFAULTS = {
               # the weight step and the loop (optim.py, train_rcnn.py; lib/config.py:147-168)
               "OPTIMIZER": "adam", "LR": 0.002, "WEIGHT_DECAY": 0.0, "MOMS": [0.95, 0.85], "DIV_FACTOR": 10.0, "PCT_START": 0.4,
               "GRAD_NORM_CLIP": 1.0, "BN_MOMENTUM": 0.9, "BN_DECAY": 0.5, "BNM_CLIP": 0.01,
-              "BN_DECAY_STEP_LIST": [50, 100, 150, 200, 250, 300]},
+              "BN_DECAY_STEP_LIST": [50, 100, 150, 200, 250, 300],
+              # lib/config.py:152, read by the warm-up scheduler of 'adam' / 'sgd' only (out of scope); here so that the two keys the
+              # reference's default_waymo_finetune.yaml changes (LR, WARMUP_MIN) can be --set as they stand
+              "WARMUP_MIN": 0.0002},
     "TEST": {"SPLIT": "val", "RPN_PRE_NMS_TOP_N": 9000, "RPN_POST_NMS_TOP_N": 300,
              "RPN_NMS_THRESH": 0.7, "RPN_DISTANCE_BASED_PROPOSE": True},
 }

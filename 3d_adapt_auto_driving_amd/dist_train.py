@@ -255,6 +255,15 @@ class ReplicaGroup:
             raise RuntimeError("dist_train: replica drift: the ranks' parameter digests differ (%s)" % ["%016x" % h for h in got])
         return mine
 
+    def broadcast_object(self, obj):
+        """Rank 0's picklable ``obj`` to every rank (small host-side things: a sample list); the other ranks' argument is unread"""
+        import torch.distributed as dist
+        if not self.active:
+            return obj
+        box = [obj if self.rank == 0 else None]
+        dist.broadcast_object_list(box, src=0, device=None if self.backend == "gloo" else self.device)
+        return box[0]
+
     def broadcast_model(self, model):
         """Rank 0's parameters and buffers to every rank (once, after the checkpoints are loaded)"""
         import torch

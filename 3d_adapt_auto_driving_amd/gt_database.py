@@ -26,7 +26,6 @@ import contextlib
 import ctypes as C
 import os
 import pickle
-import random
 import sys
 import types
 
@@ -34,7 +33,7 @@ import numpy as np
 
 from . import _lib, kitti_io
 from .kitti_io import Object3d
-from .scene_batch import MAX_IO_WORKERS, TILE, as_calib, boxes_of_labels, check_device, class_whitelist, cum, offsets_to_device, pack_scenes, to_device  # noqa: F401
+from .scene_batch import MAX_IO_WORKERS, TILE, as_calib, boxes_of_labels, check_device, class_whitelist, cum, offsets_to_device, pack_scenes, sample_id_list, to_device  # noqa: F401
 CLASS_TUPLES = {"Car": ("Background", "Car"), "People": ("Background", "Pedestrian", "Cyclist"),
                 "Pedestrian": ("Background", "Pedestrian"), "Cyclist": ("Background", "Cyclist")}
 VALID_LEVELS = ("Easy", "Moderate", "Hard")
@@ -238,29 +237,6 @@ def filtrate_objects(obj_list, classes):
             continue
         out.append(obj)
     return out
-
-
-def sample_id_list(root, split="train", subsample=-1, shuffle_subsample=None):
-    """kitti_dataset.py:18-33.  With ``subsample > 0`` on ``train`` the list is train_car1.txt, or train_car1_<shuffle_subsample>.txt,
-    cut to the first ``subsample`` ids.  A missing train_car1_<shuffle_subsample>.txt is written from an UNSEEDED random.shuffle of
-    train_car1.txt, as the reference does: its order is not reproducible (keep the file to keep the list)."""
-    sets = os.path.join(root, "KITTI", "ImageSets")
-    if subsample > 0 and split == "train":
-        if shuffle_subsample is not None:
-            path = os.path.join(sets, "train_car1_{}.txt".format(shuffle_subsample))
-            if not os.path.isfile(path):
-                with open(os.path.join(sets, "train_car1.txt")) as f:
-                    temp = [x.strip() for x in f.readlines()]
-                random.shuffle(temp)
-                with open(path, "w") as f:
-                    for item in temp:
-                        f.write("{}\n".format(item))
-        else:
-            path = os.path.join(sets, "train_car1.txt")
-        with open(path) as f:
-            return [x.strip() for x in f.readlines()][:subsample]
-    with open(os.path.join(sets, split + ".txt")) as f:
-        return [x.strip() for x in f.readlines()]
 
 
 def database_file_name(save_dir, split, class_name):

@@ -317,12 +317,14 @@ def _host_anno(text, skip_blank):
     return annos_from_lines(lines) if skip_blank else _anno_from_rows([line.strip().split(" ") for line in lines])
 
 
-def parse_texts(texts, device, skip_blank=False, device_id=0):
+def parse_texts(texts, device, skip_blank=False, device_id=0, host_anno=None):
     """The text of every file of one side of a split (bytes or str, in image order) -> SplitSide, without a Python float() per token.
     device "cuda": the kernels of csrc/kitti_parse.hip (no usable GPU raises ParseDeviceError: nothing falls back silently); "cpu":
     the same grammar and value rule in Python, the checker.  File semantics by default (get_label_anno: a blank line is an error of
     the host parser); skip_blank: annos_from_lines semantics, blank lines are dropped.  A file outside the regular grammar goes to the
-    host parser, whole, and raises there what it raises today; ``parse_stats["host_files"]`` counts them."""
+    host parser, whole, and raises there what it raises today; ``parse_stats["host_files"]`` counts them.  ``host_anno(text,
+    skip_blank)`` stands in for the host parser on those files (car_split.py: its rule accepts lines that _anno_from_rows rejects, so it
+    passes one that returns no rows and decides the files named by the side's host annotations itself)."""
     if device not in ("cpu", "cuda"):
         raise ValueError("parse device %r is neither 'cpu' nor 'cuda'" % (device,))
     texts = list(texts)
@@ -347,7 +349,7 @@ def parse_texts(texts, device, skip_blank=False, device_id=0):
     irregular = ((flag & _lib.PRCNN_PARSE_BAD) != 0) | ((flag & both) == both) | np.array(too_long, dtype=bool)
     file_of_row = np.repeat(np.arange(n_files), raw["rows"])
     keep = ~irregular[file_of_row] & (raw["row_tok"] != 0)
-    host = {int(f): _host_anno(texts[f], skip_blank) for f in np.flatnonzero(irregular)}
+    host = {int(f): (host_anno or _host_anno)(texts[f], skip_blank) for f in np.flatnonzero(irregular)}
     host_sides = {f: SplitSide([anno]) for f, anno in host.items()}
     nums = np.bincount(file_of_row[keep], minlength=n_files).astype(np.int64)
     for f, side in host_sides.items():

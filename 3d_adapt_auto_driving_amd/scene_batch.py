@@ -1,7 +1,10 @@
 """What the ragged-scene data modules share on the host (gt_database.py, stat_norm.py, aug_scene.py, train_input.py, road_planes.py; the device side is
 csrc/scene_tiles.hpp and csrc/placement.hpp): a batch of scenes packed back to back with its offsets and 64-point tiles, the
-valid-point filter of the reference's loaders in numpy, and the small box / database / label helpers of object placement.
+valid-point filter of the reference's loaders in numpy, the small box / database / label helpers of object placement, and the sample
+list of a split (with the few-shot --subsample rule).
 """
+import os
+import random
 import types
 
 import numpy as np
@@ -127,3 +130,31 @@ def class_whitelist(classes, include_similar=False, sitting_with=("Pedestrian",)
         if any(c in classes for c in sitting_with):
             white.append("Person_sitting")
     return white
+
+
+def sample_list_file(root, split="train", subsample=-1, shuffle_subsample=None):
+    """The file sample_id_list reads: ImageSets/<split>.txt, or with ``subsample > 0`` on ``train`` train_car1.txt (car_split.py writes
+    it) or train_car1_<shuffle_subsample>.txt"""
+    sets = os.path.join(root, "KITTI", "ImageSets")
+    if subsample > 0 and split == "train":
+        return os.path.join(sets, "train_car1.txt" if shuffle_subsample is None else "train_car1_{}.txt".format(shuffle_subsample))
+    return os.path.join(sets, split + ".txt")
+
+
+def sample_id_list(root, split="train", subsample=-1, shuffle_subsample=None):
+    """kitti_dataset.py:18-33.  With ``subsample > 0`` on ``train`` the list is train_car1.txt, or train_car1_<shuffle_subsample>.txt,
+    cut to the first ``subsample`` ids.  A missing train_car1_<shuffle_subsample>.txt is written from an UNSEEDED random.shuffle of
+    train_car1.txt, as the reference does: its order is not reproducible (keep the file to keep the list)."""
+    path = sample_list_file(root, split, subsample, shuffle_subsample)
+    if subsample > 0 and split == "train":
+        if shuffle_subsample is not None and not os.path.isfile(path):
+            with open(sample_list_file(root, split, subsample)) as f:
+                temp = [x.strip() for x in f.readlines()]
+            random.shuffle(temp)
+            with open(path, "w") as f:
+                for item in temp:
+                    f.write("{}\n".format(item))
+        with open(path) as f:
+            return [x.strip() for x in f.readlines()][:subsample]
+    with open(path) as f:
+        return [x.strip() for x in f.readlines()]

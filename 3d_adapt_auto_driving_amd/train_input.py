@@ -3,8 +3,11 @@ apply_gt_aug_to_one_scene, the near / far sampler, data_augmentation (stage 1), 
 KITTI-format tree plus a GT database (gt_database.py) -> RPN training batches.  No loss, no optimizer, no backward pass.
 
   src = RpnTrainInput(root, cfg, gt_database_dir, split="train", classes="Car", npoints=16384, npoints_faraway=4000,
-                      with_replace=False, seed=None, device="cuda")
+                      with_replace=False, seed=None, device="cuda", subsample=-1, shuffle_subsample=None, sample_ids=None)
   len(src)                    the reference's sample_id_list after preprocess_rpn_training_data
+                              (the list is scene_batch.sample_id_list's: with ``subsample > 0`` on ``train`` the first ``subsample``
+                              ids of train_car1.txt or train_car1_<shuffle_subsample>.txt; ``sample_ids``, an explicit list, replaces
+                              the read -- what the ranks of a process group are handed; the object filter follows either)
   batch = src.batch(indices)  the dict collate_batch returns for [dataset[i] for i in indices]
 
 ``device="cuda"`` runs csrc/train_input.hip and csrc/rpn_labels.hip; the per-point entries are device tensors and never visit the host.
@@ -12,7 +15,8 @@ KITTI-format tree plus a GT database (gt_database.py) -> RPN training batches.  
 
 Command line:
   python -m 3d_adapt_auto_driving_amd.train_input --root R --gt_database_dir DB.pkl [--class_name Car] [--split train] [--npoints N]
-         [--batch_size B] [--epochs E] [--device cuda|cpu] [--save_dir D] [--cfg_file F] [--seed S]
+         [--batch_size B] [--epochs E] [--device cuda|cpu] [--save_dir D] [--cfg_file F] [--seed S] [--subsample N]
+         [--shuffle_subsample S]
 walks the split in order and prints scenes/s; with --save_dir one ``batch_%06d.npz`` per batch is written.
 
 The random stream.  The target is ONE process calling ``dataset[i]`` in order (num_workers=0); the reference's global np.random is a
@@ -49,7 +53,7 @@ from .aug_scene import road_plane
 from .gt_database import box_trig, class_tuple, load_gt_database
 from .kitti_io import Object3d, png_size
 from .scene_batch import (TILE, boxes_of_labels, check_device, check_pc_range, class_whitelist, cum, database_rows, enlarged,  # noqa: F401
-                          no_label_error, offsets_to_device, pack_scenes, place_on_plane, to_device, valid_points)
+                          no_label_error, offsets_to_device, pack_scenes, place_on_plane, sample_id_list, to_device, valid_points)
 
 MAX_CAND = 16                      # csrc/placement.hpp PLACE_MAX_CAND = prcnn_aug_max_candidates()
 TRY_TIMES = 100
@@ -244,7 +248,7 @@ _TrainBatch = _lib.struct("prcnn_train_batch")
 
 class RpnTrainInput:
     def __init__(self, root, cfg, gt_database_dir=None, split="train", classes="Car", npoints=16384, npoints_faraway=4000,
-                 with_replace=False, seed=None, device="cuda"):
+                 with_replace=False, seed=None, device="cuda", subsample=-1, shuffle_subsample=None, sample_ids=None):
         check_device(device)
         self.root, self.cfg, self.split, self.device = root, cfg, split, str(device)
         self.classes = class_tuple(classes)
@@ -259,9 +263,10 @@ class RpnTrainInput:
         self.aug_label_dir = os.path.join(aug_root, "aug_label")
         self.scope = np.asarray(cfg.PC_AREA_SCOPE, dtype=np.float64).reshape(3, 2)
         self.reduce = bool(_opt(cfg, "PC_REDUCE_BY_RANGE"))
-        with open(os.path.join(root, "KITTI", "ImageSets", split + ".txt")) as f:
-            ids = [int(x.strip()) for x in f.readlines()]
-        self.sample_id_list = [i for i in ids if len(self.filtrate_objects(self.labels(i))) > 0]
+        if sample_ids is None:                                # kitti_dataset.py:18-33, the few-shot cut included
+            sample_ids = sample_id_list(root, split, subsample, shuffle_subsample)
+        self.listed_ids = [int(x) for x in sample_ids]        # before the object filter
+        self.sample_id_list = [i for i in self.listed_ids if len(self.filtrate_objects(self.labels(i))) > 0]
         self.gt_aug = bool(_opt(cfg, "GT_AUG_ENABLED"))
         self.hard_ratio = float(_opt(cfg, "GT_AUG_HARD_RATIO"))
         self.db = None
@@ -580,13 +585,16 @@ def main(argv=None):
     ap.add_argument("--device", type=str, default="cuda")
     ap.add_argument("--save_dir", type=str, default=None)
     ap.add_argument("--seed", type=int, default=None)
+    ap.add_argument("--subsample", type=int, default=-1)
+    ap.add_argument("--shuffle_subsample", type=str, default=None)
     a = ap.parse_args(argv)
     cfg = config.make_cfg()
     if a.cfg_file:
         config.cfg_from_file(cfg, a.cfg_file)
     elif a.gt_database_dir:
         cfg["GT_AUG_ENABLED"], cfg["GT_AUG_RAND_NUM"], cfg["GT_AUG_APPLY_PROB"] = True, True, 1.0    # what the shipped yamls set
-    src = RpnTrainInput(a.root, cfg, a.gt_database_dir, a.split, a.class_name, a.npoints, a.npoints_faraway, seed=a.seed, device=a.device)
+    src = RpnTrainInput(a.root, cfg, a.gt_database_dir, a.split, a.class_name, a.npoints, a.npoints_faraway, seed=a.seed, device=a.device,
+                        subsample=a.subsample, shuffle_subsample=a.shuffle_subsample)
     if a.save_dir:
         os.makedirs(a.save_dir, exist_ok=True)
     done, t0, k = 0, time.perf_counter(), 0

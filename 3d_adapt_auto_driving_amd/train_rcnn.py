@@ -3,7 +3,8 @@ Trainer.train / checkpoint_state / load_checkpoint / load_part_ckpt): a KITTI-fo
 
   python -m 3d_adapt_auto_driving_amd.train_rcnn --train_mode rpn|rcnn --root R [--gt_database DB.pkl] [--cfg_file Y] [--batch_size 16]
          [--epochs 200] [--ckpt_save_interval 5] [--ckpt C] [--rpn_ckpt C] [--npoints_faraway 4000] [--output_dir D] [--seed S]
-         [--device cuda|cpu] [--ordered_backward] [--fused_layers] [--engine_rpn] [--set K V ...]
+         [--device cuda|cpu] [--ordered_backward] [--fused_layers] [--engine_rpn] [--subsample N] [--shuffle_subsample S]
+         [--with_replace] [--rcnn_ckpt C] [--set K V ...]
 
 ``rpn`` trains the first stage alone (RPN.ENABLED, RCNN off); ``rcnn`` trains the second stage on a fixed first one (RCNN.ENABLED,
 RPN.ENABLED = RPN.FIXED = True; the RPN's parameters are frozen AFTER the optimizer is built, so they keep their places in its groups).
@@ -42,6 +43,19 @@ tensors are broadcast once after --ckpt / --rpn_ckpt are loaded; the per-rank ra
 seed + rank, so a W-rank run is NOT the sample stream of a 1-rank run.  Without the launcher's variables, or with WORLD_SIZE=1, there is
 no process group and no file differs from what the loop wrote before.
 
+Few-shot fine-tuning (the reference's tools/train_rcnn.py:50-54; README "Few-shot fine-tuning" has the whole chain): --subsample N trains
+on the first N ids of KITTI/ImageSets/train_car1.txt (car_split.py writes it), or of train_car1_<S>.txt with --shuffle_subsample S, which
+scene_batch.sample_id_list writes from an UNSEEDED shuffle when it is missing; the object filter of the input stage follows, as on any
+list.  It needs TRAIN.SPLIT train: with another split the reference ignores the flag and trains on the full split, here that is a
+ValueError before anything is written.  Under a process group rank 0 alone resolves (and, if need be, writes) the list and every rank is
+handed rank 0's (resolve_sample_ids), so the replicas cannot train on different lists.  One more line in the Start logging block names
+the list file, the count after the cut, the count after the object filter and the ids.  Fewer samples than one batch is the error it
+always was (--subsample 10 --batch_size 16).  --with_replace is the near-point sampler's ``replace`` (RpnTrainInput with_replace).
+--rcnn_ckpt is load_part_ckpt, applied after --rpn_ckpt and before the broadcast and the engine fold: the keys the file shares with the
+model are taken from it, so a whole pretrained PointRCNN goes in through either flag.  (The reference's trainer names a
+load_rcnn_part_ckpt that does not exist, so the flag raises there as shipped; this is the meaning eval_rcnn gives it.)  The four flags
+are absent from the namespace unless given: a run without them writes the log_train.txt it always wrote.
+
 Out of scope, each raising NotImplementedError with its own name before anything is written: --mgpus (DataParallel inside one process;
 the launcher form above is its counterpart), --train_with_eval,
 --train_mode rcnn_offline, TRAIN.OPTIMIZER 'adam' and 'sgd' (with their LambdaLR and warm-up schedulers).
@@ -66,6 +80,13 @@ def load_part_ckpt(model, filename, log):
     own.update(update)
     model.load_state_dict(own)
     log.info("==> Done (loaded %d/%d)" % (len(update), len(own)))
+
+
+def load_part_ckpts(model, a, log):
+    """--rpn_ckpt, then --rcnn_ckpt: a key both files hold ends with the second file's value"""
+    for flag in ("rpn_ckpt", "rcnn_ckpt"):
+        if getattr(a, flag, None) is not None:
+            load_part_ckpt(model, getattr(a, flag), log)
 
 
 def load_checkpoint(model, optimizer, filename, log):
@@ -109,6 +130,10 @@ def build_parser():
     ap.add_argument("--engine_rpn", action="store_true")
     # (absent from the namespace unless given: a run without it logs the arguments it always logged)
     ap.add_argument("--dist_backend", type=str, default=argparse.SUPPRESS, choices=("nccl", "gloo"))
+    ap.add_argument("--subsample", type=int, default=argparse.SUPPRESS)
+    ap.add_argument("--shuffle_subsample", type=str, default=argparse.SUPPRESS)
+    ap.add_argument("--with_replace", action="store_true", default=argparse.SUPPRESS)
+    ap.add_argument("--rcnn_ckpt", type=str, default=argparse.SUPPRESS)
     ap.add_argument("--set", dest="set_cfgs", default=None, nargs=argparse.REMAINDER)
     return ap
 
@@ -144,10 +169,43 @@ def make_cfg(a):
         cfg.RPN.ENABLED = cfg.RPN.FIXED = True
     if cfg.TRAIN.OPTIMIZER != "adam_onecycle":
         raise NotImplementedError("train_rcnn: TRAIN.OPTIMIZER %r is out of scope (adam_onecycle is what this loop runs)" % (cfg.TRAIN.OPTIMIZER,))
+    if getattr(a, "subsample", -1) > 0 and cfg.TRAIN.SPLIT != "train":
+        raise ValueError("train_rcnn: --subsample %d cuts train_car1.txt, the few-shot list of the 'train' split, but TRAIN.SPLIT is %r "
+                         "(the reference would silently train on the full split)" % (a.subsample, cfg.TRAIN.SPLIT))
     if getattr(a, "engine_rpn", False):                       # what the configuration alone decides, before anything is written
         from .net import frozen_rpn
         frozen_rpn.check_cfg(cfg, "TRAIN")
     return cfg
+
+
+def logged_args(a):
+    """The (key, value) lines of the Start logging block.  The switches named here are logged by lines of their own, and only when set;
+    the few-shot flags are absent from the namespace unless given: a run without any of them writes what it always wrote."""
+    return [(k, v) for k, v in vars(a).items() if k not in ("ordered_backward", "fused_layers", "engine_rpn", "dist_backend")]
+
+
+def resolve_sample_ids(a, cfg, group=None):
+    """-> (the sample list of a --subsample run as RpnTrainInput's ``sample_ids``, the file it came from), or (None, None) without
+    --subsample.  Under an active process group rank 0 alone calls scene_batch.sample_id_list -- which WRITES a missing
+    train_car1_<S>.txt from an unseeded shuffle -- and every rank returns rank 0's list; a failure there raises on every rank."""
+    from .scene_batch import sample_id_list, sample_list_file
+    subsample, shuffle = getattr(a, "subsample", -1), getattr(a, "shuffle_subsample", None)
+    if subsample <= 0:
+        return None, None
+    path = sample_list_file(a.root, cfg.TRAIN.SPLIT, subsample, shuffle)
+    ids = error = None
+    if group is None or not group.active or group.rank == 0:
+        try:
+            ids = sample_id_list(a.root, cfg.TRAIN.SPLIT, subsample, shuffle)
+        except OSError as e:
+            if group is None or not group.active:
+                raise
+            error = "%s: %s" % (type(e).__name__, e)
+    if group is not None and group.active:
+        ids, error = group.broadcast_object((ids, error))
+        if error is not None:
+            raise RuntimeError("train_rcnn: rank 0 could not read the --subsample list %s (%s)" % (path, error))
+    return ids, path
 
 
 def main(argv=None):
@@ -178,9 +236,8 @@ def main(argv=None):
         log.addHandler(h)
     try:
         log.info("**********************Start logging**********************")
-        for key, val in vars(a).items():
-            if key not in ("ordered_backward", "fused_layers", "engine_rpn", "dist_backend"):   # logged below, and only when set: a run without them writes what it always wrote
-                log.info("{:16} {}".format(key, val))
+        for key, val in logged_args(a):
+            log.info("{:16} {}".format(key, val))
         if a.ordered_backward:
             log.info("ordered_backward True: grouping / gather / interpolate gradients are summed in a fixed order (no float atomics)")
         if a.fused_layers:
@@ -189,8 +246,13 @@ def main(argv=None):
         if group.active:
             log.info("world_size %d backend %s: data-parallel, one rank per GPU; --batch_size %d is the global batch, %d rows per rank; "
                      "gradients are summed in one packed exchange" % (world, group.backend, a.batch_size, a.batch_size // world))
+        sample_ids, list_file = resolve_sample_ids(a, cfg, group)
         src = RpnTrainInput(a.root, cfg, a.gt_database, split=cfg.TRAIN.SPLIT, classes=cfg.CLASSES, npoints=cfg.RPN.NUM_POINTS,
-                            npoints_faraway=a.npoints_faraway, seed=a.seed + rank if group.active else a.seed, device=a.device)
+                            npoints_faraway=a.npoints_faraway, with_replace=getattr(a, "with_replace", False),
+                            seed=a.seed + rank if group.active else a.seed, device=a.device, sample_ids=sample_ids)
+        if sample_ids is not None:
+            log.info("subsample %d: %s -> %d ids, %d after the object filter: %s" %
+                     (a.subsample, list_file, len(sample_ids), len(src), " ".join("%06d" % i for i in src.sample_id_list)))
         per_epoch = len(src) // a.batch_size
         if per_epoch < 1:
             raise ValueError("train_rcnn: the split holds %d samples, fewer than one batch of %d" % (len(src), a.batch_size))
@@ -206,8 +268,7 @@ def main(argv=None):
         if a.ckpt is not None:
             it, start_epoch = load_checkpoint(model, opt, a.ckpt, log)
             log.info("==> resumed at epoch %d, it %d" % (start_epoch, it))
-        if a.rpn_ckpt is not None:
-            load_part_ckpt(model, a.rpn_ckpt, log)
+        load_part_ckpts(model, a, log)
         if group.active:                                      # after the loads: every replica starts from rank 0's tensors
             group.broadcast_model(model)
             if cfg.RCNN.ENABLED:
