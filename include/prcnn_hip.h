@@ -1143,6 +1143,36 @@ int prcnn_road_planes(int n_scenes, int max_tiles, int iters, const int *pt_off,
                       double cos_tilt, int min_inliers, double default_height, int *tile_cnt, int *cand_n, float *cand,
                       double *hyp, int *part, int *scores, double *p0, double *mom, double *out, void *stream);
 
+/* Bird's-eye-view scene images (csrc/bev_render.hip, bev.py).  Device pointers.
+ * prcnn_bev_bin (plain pointers and scalars): a ragged batch of clouds, packed as in prcnn_sn_batch: pt_off / tile_off / box_off
+ *   (n_clouds + 1 entries i32), velo (sum n, 4) f32 raw .bin rows.  calib (n_clouds, PRCNN_BEV_CALIB) f64 = V2C (3, 4), R0 (3, 3) row-major; boxd (n_box, PRCNN_BEV_BOXD)
+ *   f64 = the first PRCNN_BEV_BOXD doubles of a stat_norm box record (PRCNN_SN_T, PRCNN_SN_R, PRCNN_SN_XLO ..): centre, rotation made on
+ *   the host, the five bounds.  A point is rect = R0 (V2C [p 1]) in f64, one rounding per operation, sums left to right; it is an object
+ *   point when strictly inside any box of its cloud (f = (rect - t) R).  image (n_clouds) i32: the image a cloud is drawn into;
+ *   layer_out / layer_in (sum n) u8: the layer of a point outside / inside the boxes (PRCNN_BEV_LAYERS or more: not drawn, not counted).
+ *   In f32 u = (x - x0) * inv, v = (z - z0) * inv; kept iff 0 <= u < width and 0 <= v < height; counts (n_images, PRCNN_BEV_LAYERS,
+ *   height, width) u32 [layer][height - 1 - floor(v)][floor(u)] += 1 and stats (n_images, PRCNN_BEV_LAYERS, 2) i32 = binned, dropped;
+ *   both are zeroed inside the call.  cls (sum n) u8 = 1 for an object point, else 0; may be null.  u32 atomic adds only: the same
+ *   input gives the same bits.  A cloud whose image is outside [0, n_images) is not drawn. */
+enum { PRCNN_BEV_LAYERS = 3, PRCNN_BEV_CALIB = 21, PRCNN_BEV_BOXD = 17, PRCNN_BEV_BOX_CHUNK = 64, PRCNN_BEV_MAX_SIDE = 2048 };
+int prcnn_bev_bin(int n_clouds, int max_tiles, int n_images, int height, int width, float x0, float z0, float inv, const int *pt_off,
+                  const int *tile_off, const int *box_off, const int *image, const float *velo, const double *calib, const double *boxd,
+                  const unsigned char *layer_out, const unsigned char *layer_in, unsigned int *counts, unsigned char *cls, int *stats,
+                  void *stream);
+/* prcnn_bev_compose: rgb (n_images, height, width, 3) u8, one result per pixel, no atomics.  segs (n_seg, PRCNN_BEV_SEG) i32 =
+ *   ax, ay, bx, by, palette row, in units of 1/8 pixel (column, row measured downward; the centre of pixel (r, c) is (8 c + 4, 8 r + 4)),
+ *   seg_off (n_images + 1) i32; palette (n_palette, 3) u8: row 0 the background, row 1 + 4 layer + step a layer's brightness step
+ *   min(floor(log2 count), 3), the rows behind them the outline colours.  A pixel takes the LAST segment of its image within 4 line_px
+ *   units of its centre (a row outside the palette is no segment), else the highest non-empty layer, else the background.
+ *   int64 bounds: every endpoint coordinate must lie in [PRCNN_BEV_COORD_LO, PRCNN_BEV_COORD_HI] (the caller drops other boxes) and a
+ *   pixel centre lies in [4, 16380], so a component of b - a is at most 2^15 in magnitude and one of p - a below 2^15; the dot product,
+ *   |b - a|^2 and the cross product are at most 2^31, cross^2 at most 2^62 and R^2 |b - a|^2 at most 2^41 (R <= 32): no product
+ *   leaves int64. */
+enum { PRCNN_BEV_SEG = 5, PRCNN_BEV_SEG_CHUNK = 256, PRCNN_BEV_COORD_LO = -8192, PRCNN_BEV_COORD_HI = 24576, PRCNN_BEV_PALETTE_MAX = 64,
+       PRCNN_BEV_MAX_LINE = 8 };
+int prcnn_bev_compose(int n_images, int height, int width, int line_px, int n_palette, const unsigned int *counts, const int *seg_off,
+                      const int *segs, const unsigned char *palette, unsigned char *rgb, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
