@@ -190,6 +190,37 @@ __global__ __launch_bounds__(256) void pooled_rows_kernel(int clouds, int rows_p
     }
 }
 
+// ... of the distinct rows only those that the set `used` names (words u32 per cloud, bit j = row j of the cloud; csrc/roi_geometry.hip's
+// used0: the pooled points that a kept row of SA level 1's list reads) -- in row order, compacted by ballot and prefix popcount
+__global__ __launch_bounds__(256) void pooled_rows_live_kernel(int clouds, int rows_per_cloud, int words, const int *__restrict__ cnt,
+                                                               const unsigned int *__restrict__ used, int *__restrict__ rowmap,
+                                                               unsigned int *__restrict__ hdr, const int *__restrict__ src, int *__restrict__ featmap)
+{
+    const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (c >= clouds) return;
+    const int n = min(max(cnt[c], 1), rows_per_cloud);
+    const unsigned int *__restrict__ u = used + (long)c * words;
+    int total = 0;
+    for (int j0 = 0; j0 < n; j0 += 64) {
+        const int j = j0 + lane;
+        total += (int)__builtin_popcountll(__ballot(j < n && ((u[j >> 5] >> (j & 31)) & 1u)));
+    }
+    int base = 0;
+    if (lane == 0) base = (int)atomicAdd(&hdr[1], (unsigned int)total);
+    base = __builtin_amdgcn_readfirstlane(base);
+    for (int j0 = 0; j0 < n; j0 += 64) {
+        const int j = j0 + lane;
+        const bool on = j < n && ((u[j >> 5] >> (j & 31)) & 1u);
+        const unsigned long long m = __ballot(on);
+        if (on) {
+            const int e = base + (int)__builtin_popcountll(m & ((1ull << lane) - 1ull));
+            rowmap[e] = c * rows_per_cloud + j;
+            if (featmap) featmap[e] = src[c * rows_per_cloud + j];
+        }
+        base += (int)__builtin_popcountll(m);
+    }
+}
+
 }  // namespace prcnn
 
 using namespace prcnn;
@@ -303,6 +334,23 @@ extern "C" int prcnn_pooled_rows_src(int clouds, int rows_per_cloud, const int *
     if (clouds == 0) return PRCNN_OK;
     hipLaunchKernelGGL(pooled_rows_kernel, dim3((clouds + 3) / 4), dim3(256), 0, st, clouds, rows_per_cloud, cnt, rowmap, hdr, src, featmap);
     return check_launch("pooled_rows");
+}
+
+// prcnn_pooled_rows_src over the LIVE rows only: used (clouds * ceil(rows_per_cloud / 32)) u32, bit j of a cloud's words = row j of it is
+// read (prcnn_rcnn_roi_geometry_live's used0 for clouds of 512 rows) -> the listed rows are those j < max(cnt[c], 1) whose bit is set, in
+// row order per cloud.  Same header protocol, same counter; a cloud whose set is empty lists nothing.
+extern "C" int prcnn_pooled_rows_src_live(int clouds, int rows_per_cloud, const int *cnt, const unsigned int *used, const int *src, int *rowmap,
+                                          int *featmap, unsigned int *hdr, int hdr_is_zero, void *stream)
+{
+    PRCNN_REQUIRE(clouds >= 0 && rows_per_cloud > 0 && (long)clouds * rows_per_cloud <= 0x7fffffffL, "pooled_rows_live: bad sizes");
+    PRCNN_REQUIRE(hdr && (clouds == 0 || (cnt && used && rowmap)), "pooled_rows_live: null pointer");
+    PRCNN_REQUIRE((src == nullptr) == (featmap == nullptr), "pooled_rows_live: src and featmap go together");
+    hipStream_t st = (hipStream_t)stream;
+    if (!hdr_is_zero && hipMemsetAsync(hdr, 0, 4 * sizeof(unsigned int), st) != hipSuccess) { set_error("pooled_rows_live: memset failed"); return PRCNN_ELAUNCH; }
+    if (clouds == 0) return PRCNN_OK;
+    hipLaunchKernelGGL(pooled_rows_live_kernel, dim3((clouds + 3) / 4), dim3(256), 0, st, clouds, rows_per_cloud, (rows_per_cloud + 31) / 32, cnt,
+                       used, rowmap, hdr, src, featmap);
+    return check_launch("pooled_rows_live");
 }
 
 extern "C" int prcnn_pooled_rows(int clouds, int rows_per_cloud, const int *cnt, int *rowmap, unsigned int *hdr, int hdr_is_zero, void *stream)

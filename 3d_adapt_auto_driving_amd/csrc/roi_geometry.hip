@@ -135,15 +135,20 @@ __device__ __forceinline__ int roi_fps_any(int n, int lim, int m, KeyCodec kc, c
 }
 
 // first `ns` in-range points (k < n_scan, index order) of CPL centres per lane among the PPT * 64 points in registers -> hit lists in
-// LDS, s_hits[slot * stride + centre], counts in cnt[] (returned in registers); lanes whose centres are all full stop the scan early together
-template <int PPT, int CPL>
-__device__ __forceinline__ void roi_ball_query(int n_scan, int ns, float r2, const float (&px)[PPT], const float (&py)[PPT],
-                                               const float (&pz)[PPT], const float (&cx)[CPL], const float (&cy)[CPL], const float (&cz)[CPL],
-                                               const bool (&live)[CPL], unsigned short *__restrict__ s_hits, int stride, int (&cnt)[CPL],
-                                               const int lane)
+// LDS, s_hits[slot * stride + centre], counts in cnt[] (returned in registers); lanes whose centres are all full stop the scan early together.
+// MASK: um[i] bit l <- point 64 i + l was staged by some live centre (the point of a scan step is wave-uniform: a ballot per step)
+template <int PPT, int CPL, bool MASK>
+__device__ __forceinline__ void roi_ball_query_any(int n_scan, int ns, float r2, const float (&px)[PPT], const float (&py)[PPT],
+                                                   const float (&pz)[PPT], const float (&cx)[CPL], const float (&cy)[CPL], const float (&cz)[CPL],
+                                                   const bool (&live)[CPL], unsigned short *__restrict__ s_hits, int stride, int (&cnt)[CPL],
+                                                   unsigned long long (&um)[PPT], const int lane)
 {
 #pragma unroll
     for (int q = 0; q < CPL; ++q) cnt[q] = live[q] ? 0 : ns;
+    if constexpr (MASK) {
+#pragma unroll
+        for (int i = 0; i < PPT; ++i) um[i] = 0ull;
+    }
 #pragma unroll
     for (int i = 0; i < PPT; ++i) {
         const int base = 64 * i;
@@ -157,16 +162,30 @@ __device__ __forceinline__ void roi_ball_query(int n_scan, int ns, float r2, con
             const float x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(px[i]), l));
             const float y = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(py[i]), l));
             const float z = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pz[i]), l));
+            bool staged = false;
 #pragma unroll
             for (int q = 0; q < CPL; ++q) {
                 const float d2 = sqdist3(cx[q], cy[q], cz[q], x, y, z);
                 if (d2 < r2 && cnt[q] < ns) {
                     s_hits[cnt[q] * stride + lane + 64 * q] = (unsigned short)(base + l);
                     ++cnt[q];
+                    staged = true;
                 }
             }
+            if constexpr (MASK)
+                if (__any(staged)) um[i] |= 1ull << l;
         }
     }
+}
+
+template <int PPT, int CPL>
+__device__ __forceinline__ void roi_ball_query(int n_scan, int ns, float r2, const float (&px)[PPT], const float (&py)[PPT],
+                                               const float (&pz)[PPT], const float (&cx)[CPL], const float (&cy)[CPL], const float (&cz)[CPL],
+                                               const bool (&live)[CPL], unsigned short *__restrict__ s_hits, int stride, int (&cnt)[CPL],
+                                               const int lane)
+{
+    unsigned long long none[PPT];
+    roi_ball_query_any<PPT, CPL, false>(n_scan, ns, r2, px, py, pz, cx, cy, cz, live, s_hits, stride, cnt, none, lane);
 }
 
 // rows of an index tensor out of the staged hit lists: slot s of centre c; slots past the hit count repeat the first hit, an empty ball is
@@ -212,7 +231,8 @@ struct RgPacks {
 // centre that copies an earlier one, else max(hits, 1) -- row p of it = hit p of its staged list (point 0 of an empty ball), in centre
 // order, cut into 64-row tiles drawn from the list's counter; the last tile is filled with copies of centre M - 1's first row (as
 // ball_pack_kernel fills it).  pmap: staged hit -> point of the cloud (null: itself); cmap_*: centre -> point of the cloud.
-template <int M>
+// PAD_LAST (the live-rows form, where centre M - 1 may list nothing): the last tile is filled with copies of the list's last ROW instead.
+template <int M, bool PAD_LAST = false>
 __device__ __forceinline__ void roi_pack_out(int b, int keep_lo, int keep_hi, int tot_lo, int tot_hi, const unsigned short *__restrict__ s_hits,
                                              int stride, int *__restrict__ s_off, const float *__restrict__ cloud,
                                              const int *__restrict__ pmap, const int *__restrict__ cmap, const int *__restrict__ cmap2,
@@ -246,13 +266,14 @@ __device__ __forceinline__ void roi_pack_out(int b, int keep_lo, int keep_hi, in
     for (int r0 = 0; r0 < rows_out; r0 += 64) {
         const int r = r0 + lane;                                  // (every lane stays in the loop: the shuffles below read all of them)
         int c = M - 1, p = 0;
-        if (r < total) {
-            int lo = 0, hi = M - 1;                               // the last centre whose offset is <= r
+        const int rl = PAD_LAST ? min(r, total - 1) : r;          // the listed row this one is (a copy of)
+        if (rl >= 0 && rl < total) {
+            int lo = 0, hi = M - 1;                               // the last centre whose offset is <= rl
             while (lo < hi) {
                 const int mid = (lo + hi + 1) >> 1;
-                if (s_off[mid] <= r) lo = mid; else hi = mid - 1;
+                if (s_off[mid] <= rl) lo = mid; else hi = mid - 1;
             }
-            c = lo; p = r - s_off[lo];
+            c = lo; p = rl - s_off[lo];
         }
         const int t_lo = __shfl(tot_lo, c & 63, 64), t_hi = __shfl(tot_hi, c & 63, 64);
         const int tot = (M > 64 && c >= 64) ? t_hi : t_lo;
@@ -267,11 +288,15 @@ __device__ __forceinline__ void roi_pack_out(int b, int keep_lo, int keep_hi, in
     }
 }
 
+// LIVE (prcnn_rcnn_roi_geometry_live): level 2 runs FIRST -- its sampling and ball query need the 128 centres only -- and says which
+// level-1 centres a row of its list names; level 1's ball query, list and centre rows then cover those centres alone, and used0 gets the
+// pooled points that the kept level-1 rows name.  Both levels' hit lists take turns in s_hits: the same LDS as the other order.
+template <bool LIVE>
 __global__ __launch_bounds__(64) void rcnn_roi_geometry_kernel(
     KeyCodec kc1, KeyCodec kc2, float r1sq, float r2sq, int ns1, int ns2, const float *__restrict__ xyz /* (b, 512, 3) */,
     const int *__restrict__ limit /* (b) */, float *__restrict__ new_xyz1 /* (b,128,3) */, int *__restrict__ idx1 /* (b,128,ns1) */,
     int *__restrict__ rep1 /* (b,128) */, float *__restrict__ new_xyz2 /* (b,32,3) */, int *__restrict__ idx2 /* (b,32,ns2) */,
-    int *__restrict__ rep2 /* (b,32) */, const RgPacks pk /* .rowinfo1 == NULL: no row lists */)
+    int *__restrict__ rep2 /* (b,32) */, const RgPacks pk /* .rowinfo1 == NULL: no row lists */, unsigned int *__restrict__ used0 /* LIVE: (b,16) */)
 {
     // hit lists of the running ball query, [slot][centre], as 16-bit point numbers (< 512): 16.5 KB.  With 32-bit entries the workgroup
     // held 36 KB of LDS -- FOUR single-wave workgroups per CU, one per SIMD, and 1600 RoI clouds took two rounds of a chain that is
@@ -296,7 +321,7 @@ __global__ __launch_bounds__(64) void rcnn_roi_geometry_kernel(
     __syncthreads();
     // the centres that are their own representatives are the first nd1 (distinct picks; what follows are copies of centre 0): listed as
     // rows b * 128 + c for the per-point layer of the level above (prcnn_rows_gemm128_rows), which nobody asks for the other rows
-    if (pk.crows1) {
+    if (!LIVE && pk.crows1) {
         int base = 0;
         if (lane == 0) base = (int)atomicAdd(&pk.hdr_c1[1], (unsigned int)nd1);
         base = __builtin_amdgcn_readfirstlane(base);
@@ -315,7 +340,7 @@ __global__ __launch_bounds__(64) void rcnn_roi_geometry_kernel(
     }
     // ---- ball query of level 1 over the DISTINCT pooled points only (prcnn_ball_query_limit)
     int cnt1[2];
-    {
+    if constexpr (!LIVE) {
         const bool live[2] = {true, true};
         roi_ball_query<8, 2>(lim, ns1, r1sq, px, py, pz, qx, qy, qz, live, s_hits, RG_LD1, cnt1, lane);
     }
@@ -334,11 +359,13 @@ __global__ __launch_bounds__(64) void rcnn_roi_geometry_kernel(
         rep1[(long)b * RG_M1 + lane + 64 * q] = r;
         own1[q] = r == lane + 64 * q;
     }
-    if (idx1) roi_rows_out<RG_M1>(ns1, s_hits, RG_LD1, cnt1[0], cnt1[1], idx1 + (long)b * RG_M1 * ns1, lane);
-    if (pk.rowinfo1) {
-        __syncthreads();                                          // s_first is free: the list's offsets
-        roi_pack_out<RG_M1>(b, own1[0] ? max(cnt1[0], 1) : 0, own1[1] ? max(cnt1[1], 1) : 0, cnt1[0], cnt1[1], s_hits, RG_LD1, s_first, cloud,
-                            nullptr, s_sel1, nullptr, pk.rowinfo1, pk.rowdxyz1, pk.tilecloud1, pk.hdr1, lane);
+    if constexpr (!LIVE) {
+        if (idx1) roi_rows_out<RG_M1>(ns1, s_hits, RG_LD1, cnt1[0], cnt1[1], idx1 + (long)b * RG_M1 * ns1, lane);
+        if (pk.rowinfo1) {
+            __syncthreads();                                      // s_first is free: the list's offsets
+            roi_pack_out<RG_M1>(b, own1[0] ? max(cnt1[0], 1) : 0, own1[1] ? max(cnt1[1], 1) : 0, cnt1[0], cnt1[1], s_hits, RG_LD1, s_first, cloud,
+                                nullptr, s_sel1, nullptr, pk.rowinfo1, pk.rowdxyz1, pk.tilecloud1, pk.hdr1, lane);
+        }
     }
     __syncthreads();                                              // s_hits is reused below
 
@@ -362,22 +389,6 @@ __global__ __launch_bounds__(64) void rcnn_roi_geometry_kernel(
             o[0] = cx[0]; o[1] = cy[0]; o[2] = cz[0];
         }
     }
-    int cnt2[1], cntd2 = 0;
-    {
-        // the scan runs over the nd1 distinct centres; the centres behind them are copies of centre 0: in range together with it, and
-        // then the next hits in index order
-        const bool live[1] = {has};
-        roi_ball_query<2, 1>(nd1, ns2, r2sq, qx, qy, qz, cx, cy, cz, live, s_hits, RG_LD2, cnt2, lane);
-        cntd2 = has ? cnt2[0] : 0;                                // hits among the distinct centres: the rows the level's list keeps
-        const float x0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(qx[0]), 0));
-        const float y0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(qy[0]), 0));
-        const float z0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(qz[0]), 0));
-        if (has && sqdist3(cx[0], cy[0], cz[0], x0, y0, z0) < r2sq)
-            for (int k = nd1; k < RG_M1 && cnt2[0] < ns2; ++k) {
-                s_hits[cnt2[0] * RG_LD2 + lane] = (unsigned short)k;
-                ++cnt2[0];
-            }
-    }
     // representative map of level 2's centres through the map of level 1
     for (int i = lane; i < RG_M1; i += 64) s_first[i] = 0x7fffffff;
     __syncthreads();
@@ -385,7 +396,31 @@ __global__ __launch_bounds__(64) void rcnn_roi_geometry_kernel(
     __syncthreads();
     const int r2own = has ? s_first[src2] : -1;
     if (has) rep2[(long)b * RG_M2 + lane] = r2own;
-    if (idx2) roi_rows_out<RG_M2>(ns2, s_hits, RG_LD2, has ? cnt2[0] : 0, 0, idx2 + (long)b * RG_M2 * ns2, lane);
+    int cnt2[1], cntd2 = 0;
+    unsigned long long um1[2];                                    // LIVE: the level-1 centres (k = 64 i + bit) that a row of level 2's list names
+    {
+        // the scan runs over the nd1 distinct centres; the centres behind them are copies of centre 0: in range together with it, and
+        // then the next hits in index order.  LIVE: no index tensor is written, only the centres that list rows are scanned for, and
+        // every hit staged for one of them is a row of the list (they are among the distinct centres)
+        const bool live[1] = {LIVE ? r2own == lane : has};
+        roi_ball_query_any<2, 1, LIVE>(nd1, ns2, r2sq, qx, qy, qz, cx, cy, cz, live, s_hits, RG_LD2, cnt2, um1, lane);
+        cntd2 = live[0] ? cnt2[0] : 0;                            // hits among the distinct centres: the rows the level's list keeps
+        if constexpr (LIVE) {
+            if (__any(live[0] && cntd2 == 0)) um1[0] |= 1ull;     // point 0 of an empty ball
+        } else {
+            const float x0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(qx[0]), 0));
+            const float y0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(qy[0]), 0));
+            const float z0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(qz[0]), 0));
+            if (has && sqdist3(cx[0], cy[0], cz[0], x0, y0, z0) < r2sq)
+                for (int k = nd1; k < RG_M1 && cnt2[0] < ns2; ++k) {
+                    s_hits[cnt2[0] * RG_LD2 + lane] = (unsigned short)k;
+                    ++cnt2[0];
+                }
+        }
+    }
+    if constexpr (!LIVE) {
+        if (idx2) roi_rows_out<RG_M2>(ns2, s_hits, RG_LD2, has ? cnt2[0] : 0, 0, idx2 + (long)b * RG_M2 * ns2, lane);
+    }
     if (pk.rowinfo1) {
         __syncthreads();
         roi_pack_out<RG_M2>(b, r2own == lane ? max(cntd2, 1) : 0, 0, cntd2, 0, s_hits, RG_LD2, s_first, cloud, s_sel1, s_sel1, s_sel2,
@@ -406,6 +441,43 @@ __global__ __launch_bounds__(64) void rcnn_roi_geometry_kernel(
             pk.rowdxyz3[r] = make_float4(cx[0] - 0.f, cy[0] - 0.f, cz[0] - 0.f, 0.f);
         }
     }
+    if constexpr (LIVE) {
+        // ---- level 1 over the centres that level 2 reads (all of them among the nd1 that are their own representatives; centre 0 is
+        // always one: level 2 samples it first and its ball holds it)
+        __syncthreads();                                          // s_hits and s_first are free again
+        bool use1[2];
+#pragma unroll
+        for (int q = 0; q < 2; ++q) use1[q] = own1[q] && ((um1[q] >> lane) & 1ull);
+        if (pk.crows1) {                                          // ... as rows for level 2's per-point layer, in centre order
+            const unsigned long long u_lo = __ballot(use1[0]), u_hi = __ballot(use1[1]);
+            const int n_lo = __builtin_popcountll(u_lo);
+            int base = 0;
+            if (lane == 0) base = (int)atomicAdd(&pk.hdr_c1[1], (unsigned int)(n_lo + __builtin_popcountll(u_hi)));
+            base = __builtin_amdgcn_readfirstlane(base);
+            const unsigned long long below = (1ull << lane) - 1ull;
+            if (use1[0]) pk.crows1[base + (int)__builtin_popcountll(u_lo & below)] = b * RG_M1 + lane;
+            if (use1[1]) pk.crows1[base + n_lo + (int)__builtin_popcountll(u_hi & below)] = b * RG_M1 + 64 + lane;
+        }
+        unsigned long long um0[8];                                // the pooled points that a kept row of level 1's list names
+        roi_ball_query_any<8, 2, true>(lim, ns1, r1sq, px, py, pz, qx, qy, qz, use1, s_hits, RG_LD1, cnt1, um0, lane);
+#pragma unroll
+        for (int q = 0; q < 2; ++q) cnt1[q] = use1[q] ? cnt1[q] : 0;
+        if (__any((use1[0] && cnt1[0] == 0) || (use1[1] && cnt1[1] == 0))) um0[0] |= 1ull;   // point 0 of an empty ball
+        if (used0) {
+            unsigned int w = 0;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                w = lane == 2 * i ? (unsigned int)um0[i] : w;
+                w = lane == 2 * i + 1 ? (unsigned int)(um0[i] >> 32) : w;
+            }
+            if (lane < RG_N / 32) used0[(long)b * (RG_N / 32) + lane] = w;
+        }
+        if (pk.rowinfo1) {
+            __syncthreads();
+            roi_pack_out<RG_M1, true>(b, use1[0] ? max(cnt1[0], 1) : 0, use1[1] ? max(cnt1[1], 1) : 0, cnt1[0], cnt1[1], s_hits, RG_LD1, s_first,
+                                      cloud, nullptr, s_sel1, nullptr, pk.rowinfo1, pk.rowdxyz1, pk.tilecloud1, pk.hdr1, lane);
+        }
+    }
 }
 
 }  // namespace prcnn
@@ -420,7 +492,7 @@ using namespace prcnn;
  * ns1, ns2 <= 64.  The shape of rcnn_net.py:165-175 under default.yaml (RCNN.NUM_POINTS 512, SA_CONFIG NPOINTS [128, 32, -1]). */
 static int roi_geometry_any(int b, int n, int m1, float r1, int ns1, int m2, float r2, int ns2, const float *xyz,
                             const int *limit, float *new_xyz1, int *idx1, int *rep1, float *new_xyz2, int *idx2, int *rep2,
-                            const prcnn::RgPacks *packs, void *stream)
+                            const prcnn::RgPacks *packs, void *stream, unsigned int *used0 = nullptr, bool live = false)
 {
     PRCNN_REQUIRE(b >= 0 && n == RG_N && m1 == RG_M1 && m2 == RG_M2, "rcnn_roi_geometry: written for 512 -> 128 -> 32 points (got %d -> %d -> %d)", n, m1, m2);
     PRCNN_REQUIRE(ns1 >= 1 && ns1 <= RG_NS && ns2 >= 1 && ns2 <= RG_NS && r1 > 0.f && r2 > 0.f, "rcnn_roi_geometry: nsample must be 1..64, radii positive");
@@ -430,8 +502,8 @@ static int roi_geometry_any(int b, int n, int m1, float r1, int ns1, int m2, flo
     KeyCodec kc1, kc2;
     if (const int rc = fps_codec(RG_N, &kc1)) return rc;
     if (const int rc = fps_codec(RG_M1, &kc2)) return rc;
-    hipLaunchKernelGGL(rcnn_roi_geometry_kernel, dim3(b), dim3(64), 0, (hipStream_t)stream, kc1, kc2, r1 * r1, r2 * r2,
-                       ns1, ns2, xyz, limit, new_xyz1, idx1, rep1, new_xyz2, idx2, rep2, *packs);
+    hipLaunchKernelGGL(live ? rcnn_roi_geometry_kernel<true> : rcnn_roi_geometry_kernel<false>, dim3(b), dim3(64), 0, (hipStream_t)stream,
+                       kc1, kc2, r1 * r1, r2 * r2, ns1, ns2, xyz, limit, new_xyz1, idx1, rep1, new_xyz2, idx2, rep2, *packs, used0);
     return check_launch("rcnn_roi_geometry");
 }
 
@@ -456,12 +528,12 @@ extern "C" int prcnn_rcnn_roi_geometry(int b, int n, int m1, float r1, int ns1, 
  * new_xyz2, origin, ...) in the row-carried form.
  * crows1 / hdr_c1 (optional, b * m1 entries at most): the level-1 centres that are their own representatives as rows cloud * m1 + centre,
  * hdr_c1[1] of them -- for prcnn_rows_gemm128_rows (the per-point layer of level 2 over exactly the rows its lists name). */
-extern "C" int prcnn_rcnn_roi_geometry_packs(int b, int n, int m1, float r1, int ns1, int m2, float r2, int ns2, const float *xyz,
-                                             const int *limit, float *new_xyz1, int *idx1, int *rep1, float *new_xyz2, int *idx2, int *rep2,
-                                             unsigned int *rowinfo1, float *rowdxyz1, int *tilecloud1, unsigned int *hdr1,
-                                             unsigned int *rowinfo2, float *rowdxyz2, int *tilecloud2, unsigned int *hdr2,
-                                             unsigned int *rowinfo3, float *rowdxyz3, unsigned int *hdr3, int *crows1, unsigned int *hdr_c1,
-                                             int hdr_is_zero, void *stream)
+static int roi_geometry_lists(int b, int n, int m1, float r1, int ns1, int m2, float r2, int ns2, const float *xyz,
+                              const int *limit, float *new_xyz1, int *idx1, int *rep1, float *new_xyz2, int *idx2, int *rep2,
+                              unsigned int *rowinfo1, float *rowdxyz1, int *tilecloud1, unsigned int *hdr1,
+                              unsigned int *rowinfo2, float *rowdxyz2, int *tilecloud2, unsigned int *hdr2,
+                              unsigned int *rowinfo3, float *rowdxyz3, unsigned int *hdr3, int *crows1, unsigned int *hdr_c1,
+                              int hdr_is_zero, void *stream, unsigned int *used0, bool live)
 {
     PRCNN_REQUIRE(hdr1 && hdr2, "rcnn_roi_geometry_packs: null header");
     PRCNN_REQUIRE((crows1 != nullptr) == (hdr_c1 != nullptr), "rcnn_roi_geometry_packs: the centre rows come with their header");
@@ -483,5 +555,36 @@ extern "C" int prcnn_rcnn_roi_geometry_packs(int b, int n, int m1, float r1, int
     PRCNN_REQUIRE((((uintptr_t)rowdxyz1 | (uintptr_t)rowdxyz2 | (uintptr_t)rowdxyz3) & 15) == 0, "rcnn_roi_geometry_packs: rowdxyz must be 16-byte aligned");
     const prcnn::RgPacks pk = {rowinfo1, (float4 *)rowdxyz1, tilecloud1, hdr1, rowinfo2, (float4 *)rowdxyz2, tilecloud2, hdr2,
                                rowinfo3, (float4 *)rowdxyz3, hdr3, crows1, hdr_c1};
-    return roi_geometry_any(b, n, m1, r1, ns1, m2, r2, ns2, xyz, limit, new_xyz1, idx1, rep1, new_xyz2, idx2, rep2, &pk, stream);
+    return roi_geometry_any(b, n, m1, r1, ns1, m2, r2, ns2, xyz, limit, new_xyz1, idx1, rep1, new_xyz2, idx2, rep2, &pk, stream, used0, live);
+}
+
+extern "C" int prcnn_rcnn_roi_geometry_packs(int b, int n, int m1, float r1, int ns1, int m2, float r2, int ns2, const float *xyz,
+                                             const int *limit, float *new_xyz1, int *idx1, int *rep1, float *new_xyz2, int *idx2, int *rep2,
+                                             unsigned int *rowinfo1, float *rowdxyz1, int *tilecloud1, unsigned int *hdr1,
+                                             unsigned int *rowinfo2, float *rowdxyz2, int *tilecloud2, unsigned int *hdr2,
+                                             unsigned int *rowinfo3, float *rowdxyz3, unsigned int *hdr3, int *crows1, unsigned int *hdr_c1,
+                                             int hdr_is_zero, void *stream)
+{
+    return roi_geometry_lists(b, n, m1, r1, ns1, m2, r2, ns2, xyz, limit, new_xyz1, idx1, rep1, new_xyz2, idx2, rep2, rowinfo1, rowdxyz1, tilecloud1,
+                              hdr1, rowinfo2, rowdxyz2, tilecloud2, hdr2, rowinfo3, rowdxyz3, hdr3, crows1, hdr_c1, hdr_is_zero, stream, nullptr, false);
+}
+
+/* The "live rows" form of prcnn_rcnn_roi_geometry_packs: the same sampling, maps and centre coordinates, the same level-2 and GroupAll
+ * lists -- and of level 1 only what level 2 reads.  A level-1 centre is LIVE iff a row of the level-2 list names it; list 1 holds the rows
+ * of the live centres only (each as in the full list, in centre order), crows1 the live centres only, and a list with tilecloud fills a
+ * cloud's last tile with copies of the cloud's last listed row.  used0 (b, 16) u32, every word written: bit k of a cloud's 512 <- a row of
+ * its (kept) list 1 names pooled point k; never empty (centre 0 is always live and its ball holds point 0) -- the mask
+ * prcnn_pooled_rows_src_live takes.  The index tensors are never written.  Nothing above level 2 reads a centre that is not live, nothing
+ * reads a pooled point outside used0: the network's results are those of the full lists, bit for bit. */
+extern "C" int prcnn_rcnn_roi_geometry_live(int b, int n, int m1, float r1, int ns1, int m2, float r2, int ns2, const float *xyz,
+                                            const int *limit, float *new_xyz1, int *rep1, float *new_xyz2, int *rep2,
+                                            unsigned int *rowinfo1, float *rowdxyz1, int *tilecloud1, unsigned int *hdr1,
+                                            unsigned int *rowinfo2, float *rowdxyz2, int *tilecloud2, unsigned int *hdr2,
+                                            unsigned int *rowinfo3, float *rowdxyz3, unsigned int *hdr3, int *crows1, unsigned int *hdr_c1,
+                                            unsigned int *used0, int hdr_is_zero, void *stream)
+{
+    PRCNN_REQUIRE(used0 || b == 0, "rcnn_roi_geometry_live: null pointer");
+    return roi_geometry_lists(b, n, m1, r1, ns1, m2, r2, ns2, xyz, limit, new_xyz1, nullptr, rep1, new_xyz2, nullptr, rep2, rowinfo1, rowdxyz1,
+                              tilecloud1, hdr1, rowinfo2, rowdxyz2, tilecloud2, hdr2, rowinfo3, rowdxyz3, hdr3, crows1, hdr_c1, hdr_is_zero, stream,
+                              used0, true);
 }

@@ -515,7 +515,7 @@ _ARANGE = {}
 
 
 def rcnn_roi_geometry_packs_wrapper(xyz, limit, m1, r1, ns1, m2, r2, ns2, hdr1=None, hdr2=None, want_idx=True, row_clouds=False, hdr3=None,
-                                    group_all=False, hdr_c1=None, centre_rows=False):
+                                    group_all=False, hdr_c1=None, centre_rows=False, _live=False):
     """rcnn_roi_geometry_wrapper + the two levels' distinct-row lists out of the same launch (prcnn_rcnn_roi_geometry_packs) ->
     (new_xyz1, idx1, rep1, new_xyz2, idx2, rep2, pack1, pack2): pack1 == ball_pack_wrapper(idx1, xyz, new_xyz1, limit, None, rep1),
     pack2 == ball_pack_wrapper(idx2, new_xyz1, new_xyz2, None, rep1, rep2) -- the same rows per cloud, the same tiles.
@@ -527,11 +527,14 @@ def rcnn_roi_geometry_packs_wrapper(xyz, limit, m1, r1, ns1, m2, r2, ns2, hdr1=N
     GroupAll level above -- every cloud ONE group of its m2 level-2 centres, the copies among them dropped: the BallPack of the index
     tensor (b, 1, m2) = 0 .. m2-1 around the origin with rep = rep2 (sa_wide_fused3_wrapper takes it, with new_xyz = zeros (b, 1, 3)).
     centre_rows=True (hdr_c1 as the other headers): one more value at the end, (rowmap i32, hdr i32[4]) = the level-1 centres that are their
-    own representatives as rows cloud * m1 + centre, hdr[1] of them -- the list rows_gemm128_rows_wrapper takes."""
+    own representatives as rows cloud * m1 + centre, hdr[1] of them -- the list rows_gemm128_rows_wrapper takes.
+    (_live: rcnn_roi_geometry_live_wrapper's call of this body.)"""
     _chk(torch.float32, xyz); _chk(torch.int32, limit)
     b, n, _ = xyz.shape
     dev = xyz.device
     new1 = torch.empty((b, m1, 3), dtype=torch.float32, device=dev)
+    if _live and want_idx:
+        raise ValueError("rcnn_roi_geometry_live: the live-rows form writes no index tensors")
     if want_idx:
         idx1 = torch.empty((b, m1, ns1), dtype=torch.int32, device=dev)
         idx2 = torch.empty((b, m2, ns2), dtype=torch.int32, device=dev)
@@ -586,14 +589,32 @@ def rcnn_roi_geometry_packs_wrapper(xyz, limit, m1, r1, ns1, m2, r2, ns2, hdr1=N
         if hdr_c1 is not None:
             _chk(torch.int32, hdr_c1)
         crows = (torch.empty((b * m1,), dtype=torch.int32, device=dev), hdr_c1 if hdr_c1 is not None else torch.empty((4,), dtype=torch.int32, device=dev))
+    lists = (p1.rowinfo.data_ptr(), p1.rowdxyz.data_ptr(), _lib.ptr(p1.tilecloud), p1.hdr.data_ptr(),
+             p2.rowinfo.data_ptr(), p2.rowdxyz.data_ptr(), _lib.ptr(p2.tilecloud), p2.hdr.data_ptr(),
+             None if p3 is None else p3.rowinfo.data_ptr(), None if p3 is None else p3.rowdxyz.data_ptr(),
+             None if p3 is None else p3.hdr.data_ptr(), None if crows is None else crows[0].data_ptr(),
+             None if crows is None else crows[1].data_ptr())
+    out = (new1, idx1, rep1, new2, idx2, rep2, p1, p2) + ((p3,) if p3 is not None else ()) + ((crows,) if crows is not None else ())
+    if _live:
+        used0 = torch.empty((b, (n + 31) // 32), dtype=torch.int32, device=dev)
+        _lib.call("prcnn_rcnn_roi_geometry_live", b, n, m1, float(r1), ns1, m2, float(r2), ns2, xyz.data_ptr(), limit.data_ptr(), new1.data_ptr(),
+                  rep1.data_ptr(), new2.data_ptr(), rep2.data_ptr(), *lists, used0.data_ptr(), 1 if hdr1 is not None else 0, _lib.current_stream(xyz))
+        return out + (used0,)
     _lib.call("prcnn_rcnn_roi_geometry_packs", b, n, m1, float(r1), ns1, m2, float(r2), ns2, xyz.data_ptr(), limit.data_ptr(), new1.data_ptr(),
               idx1.data_ptr() if want_idx else None, rep1.data_ptr(), new2.data_ptr(), idx2.data_ptr() if want_idx else None, rep2.data_ptr(),
-              p1.rowinfo.data_ptr(), p1.rowdxyz.data_ptr(), _lib.ptr(p1.tilecloud), p1.hdr.data_ptr(),
-              p2.rowinfo.data_ptr(), p2.rowdxyz.data_ptr(), _lib.ptr(p2.tilecloud), p2.hdr.data_ptr(),
-              None if p3 is None else p3.rowinfo.data_ptr(), None if p3 is None else p3.rowdxyz.data_ptr(),
-              None if p3 is None else p3.hdr.data_ptr(), None if crows is None else crows[0].data_ptr(),
-              None if crows is None else crows[1].data_ptr(), 1 if hdr1 is not None else 0, _lib.current_stream(xyz))
-    return (new1, idx1, rep1, new2, idx2, rep2, p1, p2) + ((p3,) if p3 is not None else ()) + ((crows,) if crows is not None else ())
+              *lists, 1 if hdr1 is not None else 0, _lib.current_stream(xyz))
+    return out
+
+
+def rcnn_roi_geometry_live_wrapper(xyz, limit, m1, r1, ns1, m2, r2, ns2, hdr1=None, hdr2=None, row_clouds=False, hdr3=None, group_all=False,
+                                   hdr_c1=None, centre_rows=False):
+    """The "live rows" form of rcnn_roi_geometry_packs_wrapper (prcnn_rcnn_roi_geometry_live): the same values in the same places, the index
+    tensors always shapes only, and one more at the end -- with level 1 cut down to what level 2 reads.  A level-1 centre is live iff a row
+    of pack2 names it: pack1 lists the live centres' rows only (a subset of the full list's rows, in its order), the centre rows are the
+    live centres only, and the last value, used0 (b, 16) i32, is the bit set of the pooled points that pack1's rows name (bit k of a cloud's
+    512 = point k; never empty) -- what pooled_rows_src_live_wrapper takes.  pack2 and the GroupAll list are unchanged."""
+    return rcnn_roi_geometry_packs_wrapper(xyz, limit, m1, r1, ns1, m2, r2, ns2, hdr1, hdr2, False, row_clouds, hdr3, group_all, hdr_c1, centre_rows,
+                                           _live=True)
 
 
 def dup_rep_wrapper(sel, n, limit=None, prev=None):
@@ -1010,6 +1031,28 @@ def pooled_rows_src_wrapper(cnt, rows_per_cloud, src, hdr=None):
         hdr = torch.empty((4,), dtype=torch.int32, device=cnt.device)
     _lib.call("prcnn_pooled_rows_src", clouds, rows_per_cloud, cnt.data_ptr(), src.data_ptr(), rowmap.data_ptr(), featmap.data_ptr(),
               hdr.data_ptr(), int(zero), _lib.current_stream(cnt))
+    return rowmap, hdr, featmap
+
+
+def pooled_rows_src_live_wrapper(cnt, rows_per_cloud, src, used, hdr=None):
+    """pooled_rows_src_wrapper over the rows that `used` names: used (clouds, ceil(rows_per_cloud / 32)) i32, bit j of a cloud's words =
+    row j of it is read (rcnn_roi_geometry_live_wrapper's used0) -> (rowmap, hdr, featmap) of the rows j < max(cnt, 1) whose bit is set
+    (prcnn_pooled_rows_src_live)."""
+    _chk(torch.int32, cnt, src, used)
+    clouds = cnt.numel()
+    if src.numel() != clouds * rows_per_cloud or used.numel() != clouds * ((rows_per_cloud + 31) // 32):
+        raise ValueError("pooled_rows_src_live: src must hold clouds * rows_per_cloud entries, used a bit for each of them")
+    rowmap = torch.empty((max(1, clouds * rows_per_cloud),), dtype=torch.int32, device=cnt.device)
+    featmap = torch.empty_like(rowmap)
+    zero = hdr is not None
+    if zero:
+        _chk(torch.int32, hdr)
+        if hdr.numel() != 4:
+            raise ValueError("pooled_rows_src_live: hdr must hold 4 int32")
+    else:
+        hdr = torch.empty((4,), dtype=torch.int32, device=cnt.device)
+    _lib.call("prcnn_pooled_rows_src_live", clouds, rows_per_cloud, cnt.data_ptr(), used.data_ptr(), src.data_ptr(), rowmap.data_ptr(),
+              featmap.data_ptr(), hdr.data_ptr(), int(zero), _lib.current_stream(cnt))
     return rowmap, hdr, featmap
 
 

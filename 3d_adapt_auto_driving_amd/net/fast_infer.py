@@ -36,6 +36,9 @@ from .. import iou3d_utils
 # The engine's switches: what each selects, and what its other setting is (A/B).  Measurements and history: DESIGN.md section 12.
 USE_ROIPOOL_CANONICAL = True   # RCNN input assembly through roipool3d_canonical_kernel; False: the torch-op sequence
 USE_POOL_BY_NAME = True        # ... its rows name their RPN features, the entrance gathers them at the source; False: the rows carry a copy (same bits)
+# ... and of SA level 1 only what SA level 2 reads: the fused RoI geometry runs level 2 first and lists the live level-1 centres and pooled
+# rows alone (csrc/roi_geometry.hip LIVE, prcnn_pooled_rows_src_live; profiles/r08_live_rows.md); False: every distinct one (same bits)
+USE_LIVE_ROWS = True
 USE_RCNN_POINT_MLP = True      # RCNN entrance chain through csrc/rcnn_entrance.hip; False: library GEMMs + concat
 USE_XYZ_MLP = True             # coordinates-only SA scales through csrc/sa_xyz_mlp.hip; False: the grouped GEMM chain
 # SA levels over the DISTINCT grouped rows only (csrc/sa_packed.hip, same bits); PRCNN_NO_PACK=1: all nsample rows (csrc/sa_mlp_fused.hip)
@@ -1162,6 +1165,14 @@ class FastPointRCNN:
                     and has_entry(rp, "forward_canonical_src") and has_entry(ext, "pooled_rows_wrapper")
                     and has_entry(ext, "pooled_rows_src_wrapper") and has_entry(ext, "rcnn_point_mlp_rows_src_wrapper"))
 
+    def _live_rows_ok(self):
+        """may SA level 1 be cut down to what level 2 reads (rcnn_roi_geometry_live_wrapper, then pooled_rows_src_live_wrapper over the
+        pooled rows that are left)?  Asked where the pooled rows name their features (`_pool_by_name_ok`: the drop-in modules themselves);
+        a proxy or a stand-in in their place is shown the calls of `USE_LIVE_ROWS = False`, in their order."""
+        ext = pu.pointnet2
+        return bool(USE_LIVE_ROWS and isinstance(ext, types.ModuleType) and has_entry(ext, "rcnn_roi_geometry_live_wrapper")
+                    and has_entry(ext, "pooled_rows_src_live_wrapper"))
+
     def _pool_canonical(self, xyz, feats, seg_mask, pts_depth, rois, depth_norm, groups):
         """enlarge + pool + canonical transform + aligned row layout [x',y',z',mask,depth,0,0,0 | feats] in ONE kernel
         -> (pooled (B,M,P,8+C), distinct points per RoI or None, the rows' coordinates as dense clouds, entrance rows, feature rows);
@@ -1203,9 +1214,10 @@ class FastPointRCNN:
         a[:, :nin] = rows[:, :nin]
         return pooled, None, None, a, rows[:, nin:]
 
-    def _roi_geometry_fused(self, cur_xyz, pooled_cnt, zhdr):
+    def _roi_geometry_fused(self, cur_xyz, pooled_cnt, zhdr, live=False):
         """both sampled levels' geometry and row lists for every RoI cloud in ONE launch (csrc/roi_geometry.hip) -> (per level (new_xyz, idx,
-        rep, pack), the GroupAll level's row list or None, the level-1 centre rows or None); (None, None, None): the levels are not covered"""
+        rep, pack), the GroupAll level's row list or None, the level-1 centre rows or None, the set of pooled points that level 1 reads or
+        None); four times None: the levels are not covered.  live: level 1 cut down to what level 2 reads (`_live_rows_ok`)"""
         # a wave per RoI (rcnn_roi_geometry_kernel) instead of FPS, ball query, representative map -- twice -- as six latency-bound launches; and
         # both levels' row lists written by the wave that holds the hit lists (no pack launches for these levels).  The index tensors themselves
         # are not written on the HIP path: the packed kernels read the lists, `idx` is asked for its shape; the lists' rows carry their cloud:
@@ -1214,7 +1226,7 @@ class FastPointRCNN:
         if not (len(sa) >= 2 and sa[0].npoint is not None and sa[1].npoint is not None
                 and has_entry(ext, "rcnn_roi_geometry_packs_wrapper") and USE_PACKED and sa[0].mlp.on_packed and sa[1].mlp.on_packed
                 and ext.rcnn_roi_geometry_supported(cur_xyz.shape[1], sa[0].npoint, sa[0].nsample, sa[1].npoint, sa[1].nsample)):
-            return None, None, None
+            return None, None, None, None
         hd = zhdr() + zhdr()
         rc = sa[0].mlp.packed is not None and sa[1].mlp.packed is not None      # the consumers that read lists whose rows carry their cloud
         # ... and, in that form, the list of the GroupAll level above them (one group per RoI: no clouds merged to fill tiles)
@@ -1225,10 +1237,16 @@ class FastPointRCNN:
         extra = ()
         if hd:
             extra = hd + (False, rc) + ((zhdr()[0], True) if ga else (None, False)) + ((zhdr()[0], True) if cr else ())
-        new1, idx1, rep1, new2, idx2, rep2, pack1, pack2, *rest = ext.rcnn_roi_geometry_packs_wrapper(
-            cur_xyz, pooled_cnt.view(-1), sa[0].npoint, sa[0].radius, sa[0].nsample, sa[1].npoint, sa[1].radius, sa[1].nsample, *extra)
+        used0 = None
+        if live and hd:                                      # (the same protocol without the write-idx flag; one more value at the end)
+            new1, idx1, rep1, new2, idx2, rep2, pack1, pack2, *rest, used0 = ext.rcnn_roi_geometry_live_wrapper(
+                cur_xyz, pooled_cnt.view(-1), sa[0].npoint, sa[0].radius, sa[0].nsample, sa[1].npoint, sa[1].radius, sa[1].nsample,
+                *(extra[:2] + extra[3:]))
+        else:
+            new1, idx1, rep1, new2, idx2, rep2, pack1, pack2, *rest = ext.rcnn_roi_geometry_packs_wrapper(
+                cur_xyz, pooled_cnt.view(-1), sa[0].npoint, sa[0].radius, sa[0].nsample, sa[1].npoint, sa[1].radius, sa[1].nsample, *extra)
         listed, crows = next((x for x in rest if hasattr(x, "rowinfo")), None), next((x for x in rest if isinstance(x, tuple)), None)
-        return ((new1, idx1, rep1, pack1), (new2, idx2, rep2, pack2)), listed, crows
+        return ((new1, idx1, rep1, pack1), (new2, idx2, rep2, pack2)), listed, crows, used0
 
     def _roi_level_geometry(self, level, cur_xyz, limit, rep_in, first, centre_dedup):
         """sampling, ball query, representative map and row list of one sampled RCNN level, launch by launch
@@ -1313,10 +1331,11 @@ class FastPointRCNN:
         zarena = ZeroArena(("rcnn", B, M, P, str(rows.device)), rows.device)
         zhdr = (lambda: (zarena.take((4,), torch.int32),)) if getattr(ext, "IS_HIP_EXTENSION", False) else (lambda: ())   # positional (7th) argument
         rowlist = None
-        if by_name:                            # the distinct pooled rows of all RoIs, back to back, each with the feature row it stands for
+        live = bool(by_name and self._live_rows_ok())                          # the row list waits for the geometry: only the rows SA1 reads
+        if by_name and not live:               # the distinct pooled rows of all RoIs, back to back, each with the feature row it stands for
             rowlist = ext.pooled_rows_src_wrapper(pooled_cnt.view(-1), P, rpn_part[1], *zhdr())
             rpn_part = (rpn_part[0], rowlist[2])
-        elif use_rows:
+        elif use_rows and not by_name:
             rowlist = ext.pooled_rows_wrapper(pooled_cnt.view(-1), P, *zhdr())
         # representative map of the CURRENT level's points (None: every point counts as distinct): which of them are exact copies
         # of one another.  Level 0: pooled point k >= count is a copy of k % count (`limit`); deeper: the centres the sampling
@@ -1325,7 +1344,11 @@ class FastPointRCNN:
         # either (prcnn_ball_pack_rep: 7.5x fewer SA2 rows on LiDAR-shaped scenes, bit-identical results).
         dedup = pooled_cnt is not None and point_mlp
         centre_dedup = bool(dedup and has_entry(ext, "dup_rep_wrapper"))
-        fused_levels, fused_listed, fused_crows = self._roi_geometry_fused(cur_xyz, pooled_cnt, zhdr) if centre_dedup else (None, None, None)
+        fused_levels, fused_listed, fused_crows, used0 = self._roi_geometry_fused(cur_xyz, pooled_cnt, zhdr, live) if centre_dedup else (None,) * 4
+        if live:                               # (the levels were not covered: every distinct row)
+            rowlist = (ext.pooled_rows_src_live_wrapper(pooled_cnt.view(-1), P, rpn_part[1], used0, *zhdr()) if used0 is not None
+                       else ext.pooled_rows_src_wrapper(pooled_cnt.view(-1), P, rpn_part[1], *zhdr()))
+            rpn_part = (rpn_part[0], rowlist[2])
         levels, rep = [], None
         for k, level in enumerate(self.rcnn_sa):
             lev = {"xyz": cur_xyz, "new_xyz": None, "idx": None, "pack": None}

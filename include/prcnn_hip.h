@@ -343,6 +343,20 @@ int prcnn_rcnn_roi_geometry_packs(int b, int n, int m1, float r1, int ns1, int m
                                   unsigned int *rowinfo2, float *rowdxyz2, int *tilecloud2, unsigned int *hdr2,
                                   unsigned int *rowinfo3, float *rowdxyz3, unsigned int *hdr3, int *crows1, unsigned int *hdr_c1,
                                   int hdr_is_zero, void *stream);
+/* The "live rows" form of the same launch: of SA level 1 only what level 2 reads.  Level 2 is sampled and queried first; a level-1 centre
+ * is LIVE iff a row of the level-2 list names it (37.6 of 49.9 distinct centres per RoI on the uniform synthetic scenes, 44.7 of 49.6 on
+ * the LiDAR-shaped ones: profiles/r08_live_rows.md).  new_xyz*, rep*,
+ * list 2 and list 3 are those of prcnn_rcnn_roi_geometry_packs; list 1 holds the live centres' rows only (each centre's rows as in the full
+ * list, in centre order; with a tilecloud, a cloud's last tile is filled with copies of its last listed row), crows1 the live centres only.
+ * used0 (b, 16) u32, every word written: bit k of a cloud's 512 = a row of its list 1 names pooled point k -- never empty (centre 0 is always
+ * live and names point 0 at least); prcnn_pooled_rows_src_live takes it.  The index tensors are not written.  Nothing above level 2 reads a
+ * centre that is not live and nothing reads a pooled point outside used0: the network's results are those of the full lists, bit for bit. */
+int prcnn_rcnn_roi_geometry_live(int b, int n, int m1, float r1, int ns1, int m2, float r2, int ns2, const float *xyz,
+                                 const int *limit, float *new_xyz1, int *rep1, float *new_xyz2, int *rep2,
+                                 unsigned int *rowinfo1, float *rowdxyz1, int *tilecloud1, unsigned int *hdr1,
+                                 unsigned int *rowinfo2, float *rowdxyz2, int *tilecloud2, unsigned int *hdr2,
+                                 unsigned int *rowinfo3, float *rowdxyz3, unsigned int *hdr3, int *crows1, unsigned int *hdr_c1,
+                                 unsigned int *used0, int hdr_is_zero, void *stream);
 /* out_is_zero (this entry, prcnn_sa_xyz_mlp_packed, prcnn_packed_layer_segmax): the results arrive through atomicMax into a
  * zeroed slice; 0 = the entry zeroes out[..., out_col : out_col + width) itself, 1 = the caller has zeroed it (one fill for all
  * the scales of a level instead of one strided fill per scale). */
@@ -505,6 +519,10 @@ int prcnn_rcnn_point_mlp_rows(long r, int ld, int fcol, const float *rows, const
  * prcnn_rcnn_point_mlp's: same bits. */
 int prcnn_pooled_rows_src(int clouds, int rows_per_cloud, const int *cnt, const int *src, int *rowmap, int *featmap, unsigned int *hdr,
                           int hdr_is_zero, void *stream);
+/* ... over the rows that a set names: used (clouds * ceil(rows_per_cloud / 32)) u32, bit j of a cloud's words = row j of it is read
+ * (prcnn_rcnn_roi_geometry_live's used0) -> rows j < max(cnt[c], 1) with their bit set, in row order per cloud; same header, same counter. */
+int prcnn_pooled_rows_src_live(int clouds, int rows_per_cloud, const int *cnt, const unsigned int *used, const int *src, int *rowmap,
+                               int *featmap, unsigned int *hdr, int hdr_is_zero, void *stream);
 int prcnn_rcnn_point_mlp_rows_src(long r, int ld, const float *rows, const float *feats, const float *wu1, const float *bu1,
                                   const float *wu2, const float *bu2, const float *wm, const float *bm, const float *wp,
                                   const float *bp, float *p, const int *rowmap, const int *featmap, const unsigned int *hdr,

@@ -14,7 +14,7 @@ EXP = os.path.join(ROOT, "profiles", "_exp")
 LIB = os.path.join(EXP, "libprcnn_hip_rg_stamps.so")
 FLAGS = "--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math".split()
 PHASES = ["load 512 points", "FPS 512 -> 128", "centres out + ball query 1", "rep map 1", "rows of idx1 out (skipped by the engine)", "row list 1", "FPS 128 -> 32",
-          "centres 2 + ball query 2", "rep map 2", "rows of idx2 out (skipped by the engine)", "row lists 2 and 3"]
+          "centres 2", "rep map 2 + ball query 2", "rows of idx2 out (skipped by the engine)", "row lists 2 and 3"]
 NPH = len(PHASES)
 MAXB = 4096
 
@@ -22,7 +22,7 @@ MAXB = 4096
 def instrument():
     s = open(os.path.join(CSRC, "roi_geometry.hip")).read()
     s = s.replace('#include "fps_common.hpp"', '#include "%s/fps_common.hpp"' % CSRC)      # (its own includes are relative to it)
-    a = s.index("__global__ __launch_bounds__(64) void rcnn_roi_geometry_kernel(")
+    a = s.index("template <bool LIVE>\n__global__ __launch_bounds__(64) void rcnn_roi_geometry_kernel(")   # (the stamps follow the <false> order)
     b = s.index("/* RoI clouds xyz (b,512,3) whose points k >= limit[cloud]")
     k = s[a:b]
 
@@ -34,15 +34,15 @@ def instrument():
         "#define PH { const unsigned long long n_ = __builtin_amdgcn_s_memtime(); if (lane == 0 && b < %d) g_rg_acc[b * %d + ph_] = n_ - t_prev_; t_prev_ = n_; ++ph_; }\n" % (MAXB, NPH))
     put("    const int nd1 = roi_fps_any<8, true>(RG_N, lim, RG_M1, kc1, px, py, pz, s_sel1, lane);\n", "    PH\n    const int nd1 = roi_fps_any<8, true>(RG_N, lim, RG_M1, kc1, px, py, pz, s_sel1, lane);\n    PH\n")
     put("    // representative map of the centres: the first centre sampled from the same source (prcnn_dup_rep)\n", "    PH\n")
-    put("    if (idx1) roi_rows_out<RG_M1>(", "    PH\n    if (idx1) roi_rows_out<RG_M1>(")
-    put("    if (pk.rowinfo1) {\n        __syncthreads();                                          // s_first is free: the list's offsets\n", "    PH\n    if (pk.rowinfo1) {\n        __syncthreads();\n")
+    put("        if (idx1) roi_rows_out<RG_M1>(", "        PH\n        if (idx1) roi_rows_out<RG_M1>(")
+    put("        if (pk.rowinfo1) {\n            __syncthreads();                                      // s_first is free: the list's offsets\n", "        PH\n        if (pk.rowinfo1) {\n            __syncthreads();\n")
     put("    roi_fps_any<2, false>(RG_M1, nd1, RG_M2, kc2, qx, qy, qz, s_sel2, lane);\n", "    PH\n    roi_fps_any<2, false>(RG_M1, nd1, RG_M2, kc2, qx, qy, qz, s_sel2, lane);\n    PH\n")
     put("    // representative map of level 2's centres through the map of level 1\n", "    PH\n")
-    put("    if (idx2) roi_rows_out<RG_M2>(", "    PH\n    if (idx2) roi_rows_out<RG_M2>(")
+    put("        if (idx2) roi_rows_out<RG_M2>(", "        PH\n        if (idx2) roi_rows_out<RG_M2>(")
     # the lists of level 2 and of the GroupAll level, the end of the kernel
     put("    if (pk.rowinfo1) {\n        __syncthreads();\n        roi_pack_out<RG_M2>(", "    PH\n    if (pk.rowinfo1) {\n        __syncthreads();\n        roi_pack_out<RG_M2>(")
-    tail = "            pk.rowdxyz3[r] = make_float4(cx[0] - 0.f, cy[0] - 0.f, cz[0] - 0.f, 0.f);\n        }\n    }\n}\n"
-    put(tail, tail[:-2] + "    PH\n}\n")
+    tail = "    if constexpr (LIVE) {\n        // ---- level 1 over the centres that level 2 reads"
+    put(tail, "    PH\n" + tail)
     k = "}\n__device__ unsigned long long g_rg_acc[%d * %d];\nnamespace prcnn {\n" % (MAXB, NPH) + k
     # the kernel sits inside namespace prcnn: close and reopen it around the symbol so that HIP_SYMBOL finds it at file scope
     s = s[:a] + k + s[b:]
