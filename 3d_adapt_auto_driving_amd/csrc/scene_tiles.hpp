@@ -1,5 +1,5 @@
 // scene_tiles.hpp -- what the ragged-scene data units share (csrc/gt_database.hip, csrc/stat_norm.hip, csrc/aug_scene.hip,
-// csrc/train_input.hip, csrc/road_planes.hip): points of all scenes sit back to back (pt_off), cut into 64-point tiles, one wave per tile (tile_off).
+// csrc/train_input.hip, csrc/road_planes.hip, csrc/beam_resample.hip): points of all scenes sit back to back (pt_off), cut into 64-point tiles, one wave per tile (tile_off).
 //   SceneTile / scene_tile   where a thread stands: scene, tile, lane, point index, whether the tile / the point exists;
 //   tile_exclusive_scan      one workgroup's ordered exclusive scan over a scene's tile counts, in place;
 //   tile_grid                the launch grid of a per-tile kernel: (workgroups that cover max_tiles, ny).

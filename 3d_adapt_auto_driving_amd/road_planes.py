@@ -44,7 +44,7 @@ import os
 import numpy as np
 
 from . import _lib, kitti_io
-from .scene_batch import MAX_IO_WORKERS, as_calib, check_device, pack_scenes
+from .scene_batch import MAX_IO_WORKERS, as_calib, check_device, pack_scenes, upload_arrays as _upload
 
 FALLBACK_REASONS = (None, "fewer than 3 candidates", "no hypothesis survived the tilt and height tests", "best score below min_inliers")
 INFO_FIELDS = ("candidates", "best_hypothesis", "ransac_inliers", "inliers", "rms", "fallback")
@@ -154,21 +154,6 @@ def _plane_cpu(pts, calib, u, p, details):
 
 
 # ------------------------------------------------------------------------------------------------------------------ device path
-def _upload(arrays, device):
-    """Host arrays -> one pinned buffer, ONE asynchronous copy -> (the device buffer, the arrays' device addresses)"""
-    import torch
-    offs, total = [], 0
-    for a in arrays:
-        offs.append(total)
-        total += (a.nbytes + 255) // 256 * 256
-    host = torch.empty(max(total, 256), dtype=torch.uint8, pin_memory=True)
-    view = host.numpy()
-    for a, o in zip(arrays, offs):
-        view[o:o + a.nbytes] = a.reshape(-1).view(np.uint8)
-    buf = host.to(device, non_blocking=True)
-    return buf, [buf.data_ptr() + o for o in offs]
-
-
 def _launch_device(clouds, calibs, draws, p, device):
     """Upload and every launch of a call, NO host read -> (pack, the device arrays by name; ``out`` is what the caller reads)"""
     import torch

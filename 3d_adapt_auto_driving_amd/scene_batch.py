@@ -1,5 +1,6 @@
-"""What the ragged-scene data modules share on the host (gt_database.py, stat_norm.py, aug_scene.py, train_input.py, road_planes.py; the device side is
-csrc/scene_tiles.hpp and csrc/placement.hpp): a batch of scenes packed back to back with its offsets and 64-point tiles, the
+"""What the ragged-scene data modules share on the host (gt_database.py, stat_norm.py, aug_scene.py, train_input.py, road_planes.py, beam_resample.py;
+the device side is csrc/scene_tiles.hpp and csrc/placement.hpp): a batch of scenes packed back to back with its offsets and 64-point tiles,
+the one-copy upload of a call's host arrays, the
 valid-point filter of the reference's loaders in numpy, the small box / database / label helpers of object placement, and the sample
 list of a split (with the few-shot --subsample rule).
 """
@@ -34,6 +35,21 @@ def to_device(device):
     """-> the upload of a host array (made contiguous) to ``device``"""
     import torch
     return lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+
+
+def upload_arrays(arrays, device):
+    """Host arrays -> one pinned buffer, ONE asynchronous copy -> (the device buffer, the arrays' device addresses)"""
+    import torch
+    offs, total = [], 0
+    for a in arrays:
+        offs.append(total)
+        total += (a.nbytes + 255) // 256 * 256
+    host = torch.empty(max(total, 256), dtype=torch.uint8, pin_memory=True)
+    view = host.numpy()
+    for a, o in zip(arrays, offs):
+        view[o:o + a.nbytes] = a.reshape(-1).view(np.uint8)
+    buf = host.to(device, non_blocking=True)
+    return buf, [buf.data_ptr() + o for o in offs]
 
 
 def pack_scenes(clouds, n_boxes, calibs=None, shapes=None):

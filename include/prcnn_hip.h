@@ -1191,6 +1191,34 @@ enum { PRCNN_BEV_SEG = 5, PRCNN_BEV_SEG_CHUNK = 256, PRCNN_BEV_COORD_LO = -8192,
 int prcnn_bev_compose(int n_images, int height, int width, int line_px, int n_palette, const unsigned int *counts, const int *seg_off,
                       const int *segs, const unsigned char *palette, unsigned char *rgb, void *stream);
 
+/* LiDAR beam resampling (csrc/beam_resample.hip, beam_resample.py).  Device pointers, plain pointers and scalars
+ * only.  A ragged batch packed as in prcnn_sn_batch: pt_off / tile_off (n_scenes + 1) i32, velo (sum n, 4) f32 raw .bin rows.  The three
+ * entries run in this order on one stream; none reads on the host.  Every result equals beam_resample.py's device="cpu" path bit for bit.
+ * prcnn_beam_hist: edges (bins + 1) f64, strictly increasing (the host's table).  Per point (x, y, z) = f32 coordinates as f64 minus the
+ *   origin, rho2 = x x + y y (products and sum rounded separately), t = z / sqrt(rho2); point_bin (sum n) i32 = the largest i with
+ *   edges[i] <= t, or -1 (unassigned) for a non-finite coordinate, rho2 == 0, t < edges[0] or t >= edges[bins].  hist (n_scenes, bins)
+ *   u32, zeroed inside the call, filled with u32 atomic adds.  bins <= PRCNN_BEAM_MAX_BINS: table and histogram stay in LDS.
+ * prcnn_beam_lloyd: 1-D Lloyd on each scene's histogram with `beams` clusters (<= PRCNN_BEAM_MAX_K).  Centres start at
+ *   lo + k (hi - lo) / (beams - 1) (lo for one beam), lo / hi the lowest / highest occupied bin; an occupied bin goes to the nearest
+ *   centre, the lower one of equals; a centre becomes (sum count * bin) / (sum count) (integer sums, one f64 division), an empty cluster
+ *   keeps its own; it stops when no bin changes cluster or after PRCNN_BEAM_MAX_ITERS updates.  table (n_scenes, bins) i32 = a bin's
+ *   cluster (-1: no point in it), centres (n_scenes, beams) f64, counts (n_scenes, beams) u32 points per cluster, iters (n_scenes) i32
+ *   updates made, flags (n_scenes) i32 = PRCNN_BEAM_HIT_CAP | PRCNN_BEAM_UNSORTED (the centres left their order: never, by construction).
+ *   A scene with no assigned point: table -1, centres and counts 0, iters 0.
+ * prcnn_beam_select: beam_id (sum n) i32 = table[point_bin] (-1 unassigned); a row is kept when keep_beam[beam_id] (beams bytes) is
+ *   non-zero, an unassigned one when keep_unassigned is.  Count / scan / ordered write over the 64-point tiles: tile_cnt (sum tiles) i32
+ *   work, kept_n (n_scenes) i32, rows (sum n, 4) f32 = a scene's kept rows in their order from row pt_off[scene], each copied as four
+ *   32-bit words. */
+enum { PRCNN_BEAM_MAX_BINS = 4096, PRCNN_BEAM_MAX_K = 128, PRCNN_BEAM_MAX_ITERS = 64, PRCNN_BEAM_HIST_TILES = 64, PRCNN_BEAM_HIT_CAP = 1,
+       PRCNN_BEAM_UNSORTED = 2 };
+int prcnn_beam_hist(int n_scenes, int max_tiles, int bins, const int *pt_off, const float *velo, const double *edges, double ox, double oy,
+                    double oz, int *point_bin, unsigned int *hist, void *stream);
+int prcnn_beam_lloyd(int n_scenes, int bins, int beams, const unsigned int *hist, int *table, double *centres, unsigned int *counts,
+                     int *iters, int *flags, void *stream);
+int prcnn_beam_select(int n_scenes, int max_tiles, int bins, int beams, const int *pt_off, const int *tile_off, const float *velo,
+                      const int *point_bin, const int *table, const unsigned char *keep_beam, int keep_unassigned, int *beam_id,
+                      int *tile_cnt, int *kept_n, float *rows, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
