@@ -16,14 +16,28 @@
 //      <= 16384 64-bit entries in LDS).
 // Sampling rules as the reference: more valid points than npoints -> all far points (at most npoints_faraway of them,
 // chosen at random) + a random subset of the near ones; fewer -> every point + random extra copies.
-// The choice is random, so parity with the host sampler is distributional, not bitwise; the tests check the
-// invariants (valid points only, exact counts per class, no duplicates unless the cloud is too small, determinism
-// in the seed, uniformity).  The transform and the filter ARE bitwise the reference's (round 4): flags and rectified
-// coordinates equal what the reference's own numpy code produced on the fixture scenes (tests/golden g11).
+// Against the reference's np.random the choice is another draw of the same distribution.  Against its OWN rule the sampler
+// is pinned pick for pick: given the class of every raw point and the seed, every output row is determined, and
+// tests/input_stage_ref.py (numpy) is that rule's definition -- tests/test_gpu_input_stage.py compares choice, stats and out
+// with it bit for bit on every branch.  What the definition fixes beyond the steps above:
+//   - copies WITH replacement pick "the taken point of rank (hash mod taken) in ascending raw index": the taken points are
+//     compacted in index order (ballot + prefix) on that branch, never by the arrival order of an LDS atomic;
+//   - a scene in which nothing is taken (npoints_faraway = 0 and more than npoints valid points, all of them far) is an
+//     empty scene: zeros, choice = -1, stats as counted;
+//   - the scope test compares the f32 coordinates with the f64 PC_AREA_SCOPE in double (70.4 is not an f32), as
+//     point_chains.hpp rect_valid_point and kitti_io.valid_flag do;
+//   - the shuffle word sb is fmix32(high seed word ^ 0x9e3779b9), and the loader's seeds (seed + scene id) are below 2^32:
+//     sb is one constant there, so the relative output order of two raw indices is the same in every scene.  Harmless
+//     for the network, and the driver's dumped detections depend on it: it is part of the definition, not a defect.
+// The transform and the filter ARE bitwise the reference's (round 4): flags and rectified coordinates equal what the
+// reference's own numpy code produced on the fixture scenes (tests/golden g11).
 #include "common.hpp"
 #include "point_chains.hpp"
 #include <math.h>
 #include <algorithm>
+#include <mutex>
+#include <string.h>
+#include <vector>
 
 namespace prcnn {
 
@@ -34,6 +48,43 @@ __device__ __forceinline__ unsigned fmix32(unsigned h)
 {
     h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
     return h;                // a bijection on 32-bit words
+}
+
+// The scope rule: the f32 coordinates are compared with the f64 PC_AREA_SCOPE in double, as in rect_valid_point (point_chains.hpp):
+// f32(70.4) > 70.4 is outside.  No f32 lies strictly between a double B and the f32 nearest to it, so for every f32 x (NaN
+// included: all false)   (double)x >= B  <=>  x >= the smallest f32 that is >= B,   (double)x <= B  <=>  x <= the largest f32 that
+// is <= B.  The entries round the six bounds that way on the host and the kernels compare with those six f32 thresholds: the
+// per-point test IS the double comparison and costs what the f32 one did.
+//
+// -> DEVICE pointer to the six thresholds x0, x1, y0, y1, z0, z1 of this scope on the current device (null: set_error was called).
+// A scope is uploaded once, with a blocking copy, the first time it is seen, and kept: a driver has one scope, so no call after the
+// first uploads anything, and no host buffer has to outlive a call.
+static const float *scope_thresholds(const double *scope)
+{
+    struct Slot { int device; double bounds[6]; float *dev; };
+    static std::mutex mu;
+    static std::vector<Slot> slots;
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess) { set_error("input_stage: no current device"); return nullptr; }
+    std::lock_guard<std::mutex> lock(mu);
+    for (const Slot &s : slots)
+        if (s.device == device && memcmp(s.bounds, scope, sizeof(s.bounds)) == 0) return s.dev;
+    float thr[6];
+    for (int k = 0; k < 6; ++k) {
+        float f = (float)scope[k];                                   // nearest f32 (beyond the f32 range: +-inf)
+        if ((k & 1) == 0 && (double)f < scope[k]) f = nextafterf(f, INFINITY);
+        if ((k & 1) == 1 && (double)f > scope[k]) f = nextafterf(f, -INFINITY);
+        thr[k] = f;
+    }
+    Slot s;
+    s.device = device;
+    memcpy(s.bounds, scope, sizeof(s.bounds));
+    if (hipMalloc((void **)&s.dev, sizeof(thr)) != hipSuccess || hipMemcpy(s.dev, thr, sizeof(thr), hipMemcpyHostToDevice) != hipSuccess) {
+        set_error("input_stage: scope upload failed");
+        return nullptr;
+    }
+    slots.push_back(s);
+    return s.dev;
 }
 
 // -> class: 0 = invalid, 1 = near (z < far_depth), 2 = far; x, y, z = rectified coordinates
@@ -92,6 +143,54 @@ __device__ unsigned radix_select(int n, const unsigned *__restrict__ key, const 
     return prefix;
 }
 
+// The with-replacement branch of the sampler: the taken points into entries[0 .. have) in ASCENDING RAW INDEX, then `extra` copies
+// behind them.  The copies address the taken points by position, so the position must be a function of the cloud, not the order in
+// which an LDS atomic is served.  Rounds of IS_THREADS consecutive indices; within a round a ballot orders the lanes of a wave and
+// red[] the waves (the trip count is block-uniform, so the barriers are).  Exactly `have` points pass the take test -- `have` is
+// computed from the same counts and thresholds (keys are distinct) -- so the first `have` entries are all written and every pick
+// reads a real index; have >= 1 (the caller's exit).  Copy e: the taken point of rank (hash(e) mod have); when the pool is one
+// class (extra_cls), picks of the other class are re-drawn, at most 16 times; after that the last pick stands.
+__device__ __forceinline__ void copies_with_replacement(int n, const unsigned *__restrict__ ky, const unsigned char *__restrict__ cl,
+                                                     bool near_on, bool far_on, unsigned thr_near, unsigned thr_far, bool near_thr,
+                                                     bool far_thr, int have, int extra, int extra_cls, unsigned sb, unsigned sc,
+                                                     unsigned long long *entries, int *red)
+{
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    int base = 0;
+    for (int i0 = 0; i0 < n; i0 += IS_THREADS) {
+        const int i = i0 + t;
+        bool take = false;
+        if (i < n) {
+            const int c = cl[i];
+            if (c == 1) take = near_on && (!near_thr || ky[i] <= thr_near);
+            if (c == 2) take = far_on && (!far_thr || ky[i] <= thr_far);
+        }
+        const unsigned long long ballot = __ballot(take);
+        if (lane == 0) red[wave] = __popcll(ballot);
+        __syncthreads();
+        int before = base, total = 0;
+#pragma unroll
+        for (int w = 0; w < IS_THREADS / 64; ++w) {
+            const int cw = red[w];
+            before += (w < wave) ? cw : 0;
+            total += cw;
+        }
+        if (take)
+            entries[before + __popcll(ballot & ((1ull << lane) - 1ull))] = ((unsigned long long)fmix32((unsigned)i ^ sb) << 32) | (unsigned)i;
+        base += total;
+        __syncthreads();      // red[] is rewritten by the next round
+    }
+    for (int e = t; e < extra; e += IS_THREADS) {
+        unsigned h = fmix32((unsigned)e ^ sc);
+        unsigned i = (unsigned)entries[h % (unsigned)have];
+        for (int tries = 0; tries < 16 && extra_cls && cl[i] != extra_cls; ++tries) {
+            h = fmix32(h + 0x632be5abu);
+            i = (unsigned)entries[h % (unsigned)have];
+        }
+        entries[have + e] = ((unsigned long long)fmix32(h ^ sb ^ 0x51ed270bu) << 32) | i;
+    }
+}
+
 __global__ __launch_bounds__(IS_THREADS) void input_stage_kernel(
     int n_max, int stride, int lidar_frame, int image_filter, const int *__restrict__ counts, const float *__restrict__ raw,
     const SceneCalib *__restrict__ calib, const float *__restrict__ scope, int npoints, int npad, float far_depth,
@@ -147,8 +246,10 @@ __global__ __launch_bounds__(IS_THREADS) void input_stage_kernel(
     unsigned thr_near = 0, thr_far = 0, thr_extra = 0;
     bool extra_distinct = false;               // extras = the `extra` smallest keys over all valid points (no replacement)
     int extra_cls = 0;                         // extras with replacement are drawn from this class (0 = any taken point)
+    // how many points are taken: block-uniform, from the counts alone (a cap above npoints would ask for a negative near count)
+    const int far_keep = min(min(n_far, npoints_faraway), npoints);
+    const int have = n_valid > npoints ? far_keep + min(n_near, npoints - far_keep) : n_valid;
     if (n_valid > npoints) {
-        const int far_keep = min(min(n_far, npoints_faraway), npoints);   // (a cap above npoints would ask for a negative near count)
         if (far_keep == 0) far_mode = NONE;
         else if (far_keep < n_far) { far_mode = THR; thr_far = radix_select(n, ky, cl, 1 << 2, far_keep, hist, bcast); }
         const int need_near = npoints - far_keep;
@@ -164,40 +265,39 @@ __global__ __launch_bounds__(IS_THREADS) void input_stage_kernel(
         }
     }
     __syncthreads();
+    // Nothing taken -- npoints_faraway = 0 with more than npoints valid points that are all far (no selection ran above: far_mode
+    // NONE, no near point) -- is the empty scene again: zeros, choice = -1, stats as counted.  Everything below runs with
+    // have >= 1, so no `%` sees a zero.
+    if (have == 0) {
+        for (int j = t; j < npoints * 3; j += IS_THREADS) o[j] = 0.f;
+        if (choice)
+            for (int j = t; j < npoints; j += IS_THREADS) choice[(long)b * npoints + j] = -1;
+        return;
+    }
 
     // ---- 3. compaction into sort entries
     for (int j = t; j < npad; j += IS_THREADS) entries[j] = ~0ull;
     __syncthreads();
-    for (int i = t; i < n; i += IS_THREADS) {
-        const int c = cl[i];
-        if (c == 0) continue;
-        const int mode = (c == 1) ? near_mode : far_mode;
-        const unsigned thr = (c == 1) ? thr_near : thr_far;
-        if (mode == ALL || (mode == THR && ky[i] <= thr)) {
-            const int pos = atomicAdd(&cursor, 1);
-            if (pos < npoints) entries[pos] = ((unsigned long long)fmix32((unsigned)i ^ sb) << 32) | (unsigned)i;
-        }
-        if (extra_distinct && ky[i] <= thr_extra) {
-            const int pos = atomicAdd(&cursor, 1);
-            if (pos < npoints) entries[pos] = ((unsigned long long)fmix32((unsigned)i ^ sc) << 32) | (unsigned)i;
-        }
-    }
-    __syncthreads();
-    if (extra > 0 && !extra_distinct) {
-        // copies WITH replacement: the e-th extra is the (hash(e) mod pool)-th taken entry of the pool class.  The
-        // first base_count entries are exactly the taken points; when the pool is one class, entries of the other
-        // class are skipped by re-drawing (bounded), falling back to any taken entry.
-        const int have = min(cursor, npoints);
-        for (int e = t; e < extra; e += IS_THREADS) {
-            unsigned h = fmix32((unsigned)e ^ sc);
-            int pick = (int)(h % (unsigned)have);
-            for (int tries = 0; tries < 16 && extra_cls && cl[(unsigned)entries[pick]] != extra_cls; ++tries) {
-                h = fmix32(h + 0x632be5abu);
-                pick = (int)(h % (unsigned)have);
+    const bool with_replacement = extra > 0 && !extra_distinct;
+    if (!with_replacement) {
+        // the SET of entries is what matters here (the sort below orders it): slots in the order the LDS atomic serves them
+        for (int i = t; i < n; i += IS_THREADS) {
+            const int c = cl[i];
+            if (c == 0) continue;
+            const int mode = (c == 1) ? near_mode : far_mode;
+            const unsigned thr = (c == 1) ? thr_near : thr_far;
+            if (mode == ALL || (mode == THR && ky[i] <= thr)) {
+                const int pos = atomicAdd(&cursor, 1);
+                if (pos < npoints) entries[pos] = ((unsigned long long)fmix32((unsigned)i ^ sb) << 32) | (unsigned)i;
             }
-            const unsigned i = (unsigned)entries[pick];
-            entries[have + e] = ((unsigned long long)fmix32(h ^ sb ^ 0x51ed270bu) << 32) | i;
+            if (extra_distinct && ky[i] <= thr_extra) {
+                const int pos = atomicAdd(&cursor, 1);
+                if (pos < npoints) entries[pos] = ((unsigned long long)fmix32((unsigned)i ^ sc) << 32) | (unsigned)i;
+            }
         }
+    } else {
+        copies_with_replacement(n, ky, cl, near_mode != NONE, far_mode != NONE, thr_near, thr_far, near_mode == THR,
+                                far_mode == THR, have, extra, extra_cls, sb, sc, entries, red);
     }
     __syncthreads();
 
@@ -216,7 +316,10 @@ __global__ __launch_bounds__(IS_THREADS) void input_stage_kernel(
     // ---- 5. gather
     for (int j = t; j < npoints; j += IS_THREADS) {
         const unsigned long long e = entries[j];
-        if (e == ~0ull) { o[3 * j] = 0.f; o[3 * j + 1] = 0.f; o[3 * j + 2] = 0.f; continue; }   // cannot happen (count == npoints)
+        // Unreachable: exactly npoints entries are written above -- `have` taken points (the thresholds are K-th smallest DISTINCT
+        // keys, so a threshold passes exactly K points) plus npoints - have extras -- and ~0ull sorts behind every real entry, so
+        // slots 0 .. npoints-1 are real.  tests/test_gpu_input_stage.py compares every row with the definition on every branch.
+        if (e == ~0ull) { o[3 * j] = 0.f; o[3 * j + 1] = 0.f; o[3 * j + 2] = 0.f; continue; }
         const unsigned i = (unsigned)e;
         o[3 * j] = rc[3 * (long)i]; o[3 * j + 1] = rc[3 * (long)i + 1]; o[3 * j + 2] = rc[3 * (long)i + 2];
         if (choice) choice[(long)b * npoints + j] = (int)i;
@@ -255,11 +358,12 @@ using namespace prcnn;
 // raw (b, n_max, stride) f32 with stride 3 or 4 (x, y, z[, intensity]) as read from velodyne/*.bin (lidar_frame = 1)
 // or already in the rectified camera frame (lidar_frame = 0: V2C / R0 are ignored); counts (b) i32 = points per scene;
 // image_filter = 0 skips the in-image / depth test (synthetic clouds); calib (b, 35) f32 = V2C (3x4) | R0 (3x3) | P2 (3x4) |
-// image height, width; scope = 6 HOST floats x0,x1,y0,y1,z0,z1
-// (PC_AREA_SCOPE) or NULL; seeds (b) u64 DEVICE.  -> out (b, npoints, 3), stats (b, 3) i32 = #valid, #near, #far,
-// choice (b, npoints) i32 = raw index of every output point (optional, may be NULL; -1 for an empty scene).
+// image height, width; scope = 6 HOST doubles x0,x1,y0,y1,z0,z1
+// (PC_AREA_SCOPE, compared in double: scope_thresholds; read before the call returns) or NULL; seeds (b) u64 DEVICE.  -> out (b, npoints, 3), stats (b, 3) i32 = #valid, #near, #far,
+// choice (b, npoints) i32 = raw index of every output point (optional, may be NULL; -1 for a scene in which nothing is taken:
+// no valid point, or npoints_faraway = 0 with more than npoints valid points that are all far -- out is zeros there).
 extern "C" int prcnn_input_stage(int b, int n_max, int stride, int lidar_frame, int image_filter, const int *counts, const float *raw,
-                                 const float *calib, const float *scope_host, int npoints, float far_depth,
+                                 const float *calib, const double *scope_host, int npoints, float far_depth,
                                  int npoints_faraway, const unsigned long long *seeds, float *out, int *stats, int *choice,
                                  void *stream)
 {
@@ -275,18 +379,11 @@ extern "C" int prcnn_input_stage(int b, int n_max, int stride, int lidar_frame, 
     const size_t o_rect = 0;
     const size_t o_key = o_rect + up256((size_t)b * n_max * 3 * sizeof(float));
     const size_t o_cls = o_key + up256((size_t)b * n_max * sizeof(unsigned));
-    const size_t o_scope = o_cls + up256((size_t)b * n_max);
-    const size_t need = o_scope + 256;
+    const size_t need = o_cls + up256((size_t)b * n_max) + 256;
     char *base = scratch_for(st, need, 5);
     if (!base) { set_error("input_stage: cannot allocate %zu bytes of scratch", need); return PRCNN_ELAUNCH; }
-    float *scope_dev = nullptr;
-    if (scope_host) {
-        scope_dev = (float *)(base + o_scope);
-        if (hipMemcpyAsync(scope_dev, scope_host, 6 * sizeof(float), hipMemcpyHostToDevice, st) != hipSuccess) {
-            set_error("input_stage: scope upload failed");
-            return PRCNN_ELAUNCH;
-        }
-    }
+    const float *scope_dev = nullptr;
+    if (scope_host && !(scope_dev = scope_thresholds(scope_host))) return PRCNN_ELAUNCH;
     const size_t lds = (size_t)npad * sizeof(unsigned long long);
     {
         const int rc = ensure_dynamic_lds((const void *)input_stage_kernel, 140 * 1024, "input_stage");
@@ -304,23 +401,15 @@ extern "C" int prcnn_input_stage(int b, int n_max, int stride, int lidar_frame, 
 // 1 = valid with z < far_depth, 2 = valid beyond (rows >= counts[b]: 0); rect (b, n_max, 3) f32 rectified coordinates (may be
 // NULL).  Bit-identical to the reference's numpy results (float32 np.dot = fma chains; tests/golden g11).
 extern "C" int prcnn_valid_flags(int b, int n_max, int stride, int lidar_frame, int image_filter, const int *counts, const float *raw,
-                                 const float *calib, const float *scope_host, float far_depth, float *rect, unsigned char *cls,
+                                 const float *calib, const double *scope_host, float far_depth, float *rect, unsigned char *cls,
                                  void *stream)
 {
     PRCNN_REQUIRE(b >= 0 && n_max >= 0 && (stride == 3 || stride == 4), "valid_flags: bad sizes (stride 3 or 4)");
     if (b == 0 || n_max == 0) return PRCNN_OK;
     PRCNN_REQUIRE(counts && calib && raw && cls, "valid_flags: null pointer");
     hipStream_t st = (hipStream_t)stream;
-    float *scope_dev = nullptr;
-    if (scope_host) {
-        char *base = scratch_for(st, 256, 5);
-        if (!base) { set_error("valid_flags: cannot allocate scratch"); return PRCNN_ELAUNCH; }
-        scope_dev = (float *)base;
-        if (hipMemcpyAsync(scope_dev, scope_host, 6 * sizeof(float), hipMemcpyHostToDevice, st) != hipSuccess) {
-            set_error("valid_flags: scope upload failed");
-            return PRCNN_ELAUNCH;
-        }
-    }
+    const float *scope_dev = nullptr;
+    if (scope_host && !(scope_dev = scope_thresholds(scope_host))) return PRCNN_ELAUNCH;
     const int gx = (int)std::min<long>(1024, ((long)n_max + 255) / 256);
     hipLaunchKernelGGL(valid_flags_kernel, dim3(gx, b), dim3(256), 0, st, n_max, stride, lidar_frame, image_filter, counts, raw,
                        (const SceneCalib *)calib, scope_dev, far_depth, rect, cls);

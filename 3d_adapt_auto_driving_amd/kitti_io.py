@@ -63,13 +63,15 @@ class Calibration:
 
 def valid_flag(pts_rect, pts_img, depth, img_shape, area_scope=None):
     """In the image, in front of the camera and (optionally) inside PC_AREA_SCOPE
-    (kitti_rcnn_dataset.py:201-222)."""
+    (kitti_rcnn_dataset.py:201-222).  The scope rule of the whole tree: the f32 coordinates are compared with the f64 scope in
+    double (f32(70.4) > 70.4 is outside), as csrc/point_chains.hpp ``rect_valid_point`` and csrc/input_stage.hip ``classify_point``
+    do.  Both sides are widened here, so the rule does not hang on numpy's promotion of a float64 scalar against an f32 array."""
     flag = (pts_img[:, 0] >= 0) & (pts_img[:, 0] < img_shape[1]) & (pts_img[:, 1] >= 0) & (pts_img[:, 1] < img_shape[0])
     flag &= depth >= 0
     if area_scope is not None:
-        (x0, x1), (y0, y1), (z0, z1) = area_scope
-        flag &= (pts_rect[:, 0] >= x0) & (pts_rect[:, 0] <= x1) & (pts_rect[:, 1] >= y0) & (pts_rect[:, 1] <= y1) \
-            & (pts_rect[:, 2] >= z0) & (pts_rect[:, 2] <= z1)
+        scope = np.asarray(area_scope, dtype=np.float64).reshape(3, 2)
+        xyz = np.asarray(pts_rect[:, 0:3], dtype=np.float64)
+        flag &= ((xyz >= scope[:, 0]) & (xyz <= scope[:, 1])).all(axis=1)
     return flag
 
 
@@ -245,7 +247,9 @@ class DeviceInputStage:
     The host only reads files; transform, validity filter and the near/far sampler run as one workgroup per scene.
     ``__call__(raws, calibs, shapes, scene_ids, lidar_frame, image_filter)`` with ``raws`` a list of (n_i, 3|4)
     float32 arrays; returns (pts, stats) device tensors, stats (B,3) = #valid, #near, #far (and the raw index of every
-    output point with ``return_choice``)."""
+    output point with ``return_choice``).  Which rows come out is a function of the points' classes and ``seed + scene id`` alone,
+    defined by tests/input_stage_ref.py.  A scene of which nothing is taken -- no valid point, or ``npoints_faraway = 0`` with more
+    than npoints valid points that are all far -- gives zeros and ``choice = -1``."""
 
     def __init__(self, cfg, device, npoints_faraway=4000, seed=1024, far_depth=40.0):
         import torch
@@ -353,8 +357,8 @@ class DeviceInputStage:
         scope = None
         if cfg.PC_REDUCE_BY_RANGE:
             (x0, x1), (y0, y1), (z0, z1) = cfg.PC_AREA_SCOPE
-            self._scope = (ctypes.c_float * 6)(x0, x1, y0, y1, z0, z1)       # kept alive until the async upload is done
-            scope = ctypes.cast(self._scope, ctypes.c_void_p)
+            keep = (ctypes.c_double * 6)(x0, x1, y0, y1, z0, z1)             # the entry reads it before it returns
+            scope = ctypes.cast(keep, ctypes.c_void_p)
         with torch.cuda.device(dev):
             _lib.call("prcnn_input_stage", B, n_max, stride, int(bool(lidar_frame)), int(bool(image_filter)),
                       counts.data_ptr(), raw.data_ptr(), cal.data_ptr(), scope, npoints, float(self.far_depth),
@@ -383,7 +387,7 @@ def device_valid_flags(cfg, device, raws, calibs, shapes, lidar_frame=True, imag
     scope = None
     if cfg.PC_REDUCE_BY_RANGE:
         (x0, x1), (y0, y1), (z0, z1) = cfg.PC_AREA_SCOPE
-        keep = (ctypes.c_float * 6)(x0, x1, y0, y1, z0, z1)
+        keep = (ctypes.c_double * 6)(x0, x1, y0, y1, z0, z1)
         scope = ctypes.cast(keep, ctypes.c_void_p)
     with torch.cuda.device(dev):
         _lib.call("prcnn_valid_flags", B, n_max, stride, int(bool(lidar_frame)), int(bool(image_filter)), counts.data_ptr(),

@@ -725,14 +725,18 @@ int prcnn_eval_align(int nseg, int n, const int *box_off, const int *q_off, doub
 /* get_lidar + get_valid_flag + the near/far sampler of get_rpn_sample (kitti_rcnn_dataset.py:249-324) with
  * calibration.py:51-71, one workgroup per scene.  raw (b,n_max,stride) f32, stride 3 or 4, as read from velodyne .bin
  * (lidar_frame = 1) or already rectified (0); counts (b) i32; calib (b,PRCNN_CALIB_ROW) f32 = V2C 3x4 | R0 3x3 | P2 3x4 | img h, w;
- * image_filter 0/1 (in-image + depth >= 0 test); scope_host = 6 HOST floats x0,x1,y0,y1,z0,z1 or NULL;
+ * image_filter 0/1 (in-image + depth >= 0 test); scope_host = 6 HOST doubles x0,x1,y0,y1,z0,z1 (the f64 PC_AREA_SCOPE: the f32
+ * coordinates are compared with it in double, as kitti_io.valid_flag does; read before the call returns) or NULL;
  * seeds (b) u64 DEVICE.  -> out (b,npoints,3), stats (b,3) i32 = #valid, #near, #far, choice (b,npoints) i32 = raw
  * index of each output point (may be NULL).  npoints <= 16384.
  * The subset is random (distinct-key selection + key-sorted shuffle): same distribution as the reference's
- * np.random.choice / shuffle, not the same draws; transform and filter are bitwise the reference's (see prcnn_valid_flags). */
+ * np.random.choice / shuffle, not the same draws; transform and filter are bitwise the reference's (see prcnn_valid_flags).
+ * Given the class of every raw point and the seed, every output row is determined: tests/input_stage_ref.py is the definition,
+ * and the kernel equals it pick for pick.  A scene in which nothing is taken -- no valid point, or npoints_faraway = 0 with more
+ * than npoints valid points that are all far -- is an empty scene: out zeros, choice -1, stats as counted. */
 enum { PRCNN_CALIB_ROW = 35 };   /* floats per calibration row, here and in every batch struct below whose `calib` has this layout */
 int prcnn_input_stage(int b, int n_max, int stride, int lidar_frame, int image_filter, const int *counts,
-                      const float *raw, const float *calib, const float *scope_host, int npoints, float far_depth,
+                      const float *raw, const float *calib, const double *scope_host, int npoints, float far_depth,
                       int npoints_faraway, const unsigned long long *seeds, float *out, int *stats, int *choice,
                       void *stream);
 
@@ -742,7 +746,7 @@ int prcnn_input_stage(int b, int n_max, int stride, int lidar_frame, int image_f
  * NULL).  Bit-identical to the reference's numpy results: float32 np.dot is a chain of fused multiply-adds over the inner
  * index, which the kernel reproduces (tests/golden g11, recorded by running the reference's code). */
 int prcnn_valid_flags(int b, int n_max, int stride, int lidar_frame, int image_filter, const int *counts, const float *raw,
-                      const float *calib, const float *scope_host, float far_depth, float *rect, unsigned char *cls,
+                      const float *calib, const double *scope_host, float far_depth, float *rect, unsigned char *cls,
                       void *stream);
 
 /* ---- evaluate/eval2.py: host-side matching of the AP evaluator (HOST pointers, f64 / i64) ---- */
