@@ -56,6 +56,12 @@ model are taken from it, so a whole pretrained PointRCNN goes in through either 
 load_rcnn_part_ckpt that does not exist, so the flag raises there as shipped; this is the meaning eval_rcnn gives it.)  The four flags
 are absent from the namespace unless given: a run without them writes the log_train.txt it always wrote.
 
+Random object scaling (README "Random object scaling"; object_scale.py): --obj_scale LO HI [--obj_scale_prob P] hands both values to
+RpnTrainInput in either train mode: every iteration each labelled object's points and box are rescaled by a factor of its own, drawn from
+a random stream of its own.  One line of log_train.txt names range and probability, and every line of train_log.jsonl gains
+``objects_scaled`` (final gt boxes of the writer's rows whose factor is not 1) and ``objects_without_points`` (those that own no point).
+Both flags are absent from the namespace unless given, and no config key exists for them: a run without them writes what it always wrote.
+
 Out of scope, each raising NotImplementedError with its own name before anything is written: --mgpus (DataParallel inside one process;
 the launcher form above is its counterpart), --train_with_eval,
 --train_mode rcnn_offline, TRAIN.OPTIMIZER 'adam' and 'sgd' (with their LambdaLR and warm-up schedulers).
@@ -134,6 +140,8 @@ def build_parser():
     ap.add_argument("--shuffle_subsample", type=str, default=argparse.SUPPRESS)
     ap.add_argument("--with_replace", action="store_true", default=argparse.SUPPRESS)
     ap.add_argument("--rcnn_ckpt", type=str, default=argparse.SUPPRESS)
+    ap.add_argument("--obj_scale", type=float, nargs=2, metavar=("LO", "HI"), default=argparse.SUPPRESS)
+    ap.add_argument("--obj_scale_prob", type=float, default=argparse.SUPPRESS)
     ap.add_argument("--set", dest="set_cfgs", default=None, nargs=argparse.REMAINDER)
     return ap
 
@@ -181,7 +189,7 @@ def make_cfg(a):
 def logged_args(a):
     """The (key, value) lines of the Start logging block.  The switches named here are logged by lines of their own, and only when set;
     the few-shot flags are absent from the namespace unless given: a run without any of them writes what it always wrote."""
-    return [(k, v) for k, v in vars(a).items() if k not in ("ordered_backward", "fused_layers", "engine_rpn", "dist_backend")]
+    return [(k, v) for k, v in vars(a).items() if k not in ("ordered_backward", "fused_layers", "engine_rpn", "dist_backend", "obj_scale", "obj_scale_prob")]
 
 
 def resolve_sample_ids(a, cfg, group=None):
@@ -219,7 +227,9 @@ def main(argv=None):
         raise ValueError("train_rcnn: --batch_size %d is the GLOBAL batch and does not divide over WORLD_SIZE=%d" % (a.batch_size, world))
     from .pointnet2 import pointnet2_utils, pytorch_utils
     from .net.point_rcnn import PointRCNN
-    from .train_input import RpnTrainInput
+    from .train_input import RpnTrainInput, check_obj_scale, obj_scale_args
+    ros = obj_scale_args(a)                                   # before anything is written
+    check_obj_scale(ros.get("obj_scale"), ros.get("obj_scale_prob", 1.0))
 
     out_dir = a.output_dir or os.path.join("output", a.train_mode, cfg.TAG)
     ckpt_dir = os.path.join(out_dir, "ckpt")
@@ -249,7 +259,10 @@ def main(argv=None):
         sample_ids, list_file = resolve_sample_ids(a, cfg, group)
         src = RpnTrainInput(a.root, cfg, a.gt_database, split=cfg.TRAIN.SPLIT, classes=cfg.CLASSES, npoints=cfg.RPN.NUM_POINTS,
                             npoints_faraway=a.npoints_faraway, with_replace=getattr(a, "with_replace", False),
-                            seed=a.seed + rank if group.active else a.seed, device=a.device, sample_ids=sample_ids)
+                            seed=a.seed + rank if group.active else a.seed, device=a.device, sample_ids=sample_ids, **ros)
+        if ros:
+            log.info("obj_scale %g %g prob %g: every labelled object's points and box are rescaled by a factor of its own per iteration" %
+                     (src.obj_scale + (src.obj_scale_prob,)))
         if sample_ids is not None:
             log.info("subsample %d: %s -> %d ids, %d after the object filter: %s" %
                      (a.subsample, list_file, len(sample_ids), len(src), " ".join("%06d" % i for i in src.sample_id_list)))
@@ -302,6 +315,9 @@ def main(argv=None):
                     opt.step()
                     it += 1
                     line = dict(it=it, epoch=epoch, lr=lr, loss=float(loss.detach()), grad_norm=float(opt.total_norm), **tb_dict)
+                    if ros:
+                        line["objects_scaled"] = sum(1 for rec in src.last_scaled if rec[2] != 1.0)
+                        line["objects_without_points"] = sum(1 for rec in src.last_scaled if rec[3] == 0)
                     if writer:
                         events.write(json.dumps(line) + "\n")
                         events.flush()

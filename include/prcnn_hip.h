@@ -1025,6 +1025,17 @@ int prcnn_train_place(const prcnn_train_batch *batch, void *stream);
 /* the B x npoints output rows (codes / aug / outputs set by the caller after it has read sizes) */
 int prcnn_train_emit(const prcnn_train_batch *batch, void *stream);
 
+/* Random object scaling of a training batch (csrc/object_scale.hip, object_scale.py; the project's own definition).  Device pointers.
+ * pts (b, n, 3) f32 rect points, scaled in place; extra (b, n, extra_channels = 3 | 4) f32 or NULL: its columns 0..2 receive the same
+ * written values (a fourth column is never touched); gt (b, g, 7) f32 [x, y_bottom, z, h, w, l, ry] with counts (b) i32 valid rows per
+ * scene; trig (b, g, 2) f32 = numpy's f32 (cos ry, sin ry); factors (b, g) f64; hits (b, g) u32 (zeroed by the caller) += the points
+ * that box k owns.  The owner of a point is the lowest k < counts[s] with |a| <= l / 2, |b| <= w / 2, 0 <= v <= h for dx = px - x,
+ * dz = pz - z, v = y - py, a = dx cos - dz sin, b = dx sin + dz cos (f64, faces inclusive); with r = factors[s, owner] != 1 the point
+ * becomes (x + (a r cos + b r sin), y - v r, z + (b r cos - a r sin)) rounded to f32, otherwise its bits are kept.  The boxes are not
+ * written.  b = 0 or n = 0 returns before any launch; g = 0 launches nothing. */
+int prcnn_object_scale(int b, int n, int g, float *pts, float *extra, int extra_channels, const float *gt, const int *counts,
+                       const float *trig, const double *factors, unsigned int *hits, void *stream);
+
 /* RCNN training targets (lib/rpn/proposal_target_layer.py; csrc/rcnn_targets.hip, rcnn_targets.py).  Device pointers.
  * (a) rois (b, m, 7), gt (b, g, 7) with trailing zero-sum rows -> per RoI the row maximum of the 3-D IoU (max_ov), the first index
  * that attains it (assign), its list cls (b, m) u8 (0 fg: >= fg_thresh, 1 hard bg: [bg_lo, bg_thresh), 2 easy bg: < bg_lo, 3 none);
